@@ -8,9 +8,14 @@ L=77 x 768, 22 classes, B=2 clips per GPU), synthetic inputs resident in HBM, ra
       data parallel over clips, gradient all-reduce over RCCL inside the timed step)
 
 A "step" = forward + backward of one batch through vilco_amd (HIP kernels via libvilco_hip.so);
-for N > 1 it includes the bucketed gradient all-reduce.  Rank 0 prints ONE JSON line.  Extra objects:
-"roofline" for the dominant kernel (the MFMA GEMM), "cpu_baseline" = the oracle (CPU restatement of
-the reference, kind "port") timed on the host cores on a bounded sample, N=1 only.
+for N > 1 it includes the bucketed gradient all-reduce.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, settles, warms up, times the K steps and prints the headline.  `--full` adds
+the side measurements after the timed region: the gradient-exchange diagnostics (N > 1), "roofline"
+for the dominant kernel (the MFMA GEMM), optimizer step, strict / bf16 / larger-batch runs, target
+kernels, side configurations, NMS, and "cpu_baseline" = the oracle (CPU restatement of the reference,
+kind "port") timed on the host cores on a bounded sample, N=1 only.  `--dump-outputs DIR` writes what
+the last timed step returned (losses, parameter gradients) as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -225,6 +230,30 @@ def pmc_traffic():
     return None
 
 
+DUMP_SAMPLE = 16384         # gradients larger than this are dumped as a fixed sample of this many elements
+
+
+def dump_outputs(path, losses, named_params):
+    """--dump-outputs: what the last timed step handed its caller -- the loss dict and every parameter's gradient -- as
+    float32 `path/loss.<key>.npy` and `path/grad.<parameter>.npy`.  A gradient of more than DUMP_SAMPLE elements is written
+    as DUMP_SAMPLE of them at sorted indices drawn from a generator seeded by the parameter's name: the same elements in
+    every run and every build (8 MB in all at config P)."""
+    import zlib
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for k, v in losses.items():
+        np.save(os.path.join(path, "loss.%s.npy" % k), v.detach().float().cpu().numpy())
+    for name, p in named_params:
+        if p.grad is None:
+            continue
+        g = p.grad.detach().reshape(-1)
+        if g.numel() > DUMP_SAMPLE:
+            rng = np.random.default_rng(zlib.crc32(name.encode()))
+            idx = np.sort(rng.choice(g.numel(), size=DUMP_SAMPLE, replace=False))
+            g = g[torch.from_numpy(idx).to(g.device)]
+        np.save(os.path.join(path, "grad.%s.npy" % name), g.float().cpu().numpy())
+
+
 def dryrun_parts(dev, rank):
     """VILCO_BENCH_DRYRUN=1 (tests/test_dist_cpu.py): the rank / collective protocol of this file with a small torch
     module on CPU + gloo in place of the HIP model, so that `bench.py --gpus N` is known to terminate under torchrun
@@ -234,7 +263,9 @@ def dryrun_parts(dev, rank):
     x = torch.randn(8, 16, generator=torch.Generator().manual_seed(rank))
 
     def fwd_bwd():
-        model(x).pow(2).mean().backward()
+        loss = model(x).pow(2).mean()
+        loss.backward()
+        return {"loss": loss.detach()}
     return model, fwd_bwd
 
 
@@ -271,14 +302,22 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=2, help="clips per GPU (mq_vilco.yaml: 2)")
     ap.add_argument("--precision", default="f16x2", choices=["split3", "split", "bf16", "f16x2"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-targets", action="store_true", help="skip the target-kernel micro-benchmarks and the W / cfg1 side lines")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-targets", action="store_true",
+                    help="--full without the target-kernel micro-benchmarks, the W / cfg1 side lines and the NMS timing")
     ap.add_argument("--extra-batch", type=int, default=8,
-                    help="also time a few steps at this many clips per GPU (reported beside the headline; 0 = skip)")
+                    help="--full: also time a few steps at this many clips per GPU (reported beside the headline; 0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the side measurements (exchange diagnostics, roofline, optimizer, "
+                         "strict / bf16 / larger batch, targets, side configs, NMS, CPU baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the last timed step's losses and parameter gradients as DIR/<name>.npy (float32)")
     ap.add_argument("--cpu-baseline-worker", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.cpu_baseline_worker:
         return cpu_baseline_worker()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # bare `python bench.py --gpus N` (no launcher): start the N ranks as CHILD processes under torch.distributed.run --
         # the launch line of MQ/train_cl.sh:2 -- before this process has made any GPU call, relay their output (rank 0 prints
@@ -320,7 +359,9 @@ def main():
         batch = synth_batch(args.batch, dev, seed=rank)
 
         def fwd_bwd():
-            model(batch, is_training=True)['final_loss'].backward()
+            losses = model(batch, is_training=True)
+            losses['final_loss'].backward()
+            return {k: v.detach() for k, v in losses.items()}
 
     reducer = None
     if distributed:
@@ -337,9 +378,10 @@ def main():
             model.zero_grad(set_to_none=True)
         if reducer is not None:
             reducer.begin()
-        fwd_bwd()
+        losses = fwd_bwd()
         if reducer is not None:
             reducer.finish()
+        return losses
 
     # One rank per GPU, no gradient exchange: the step (forward + backward) is captured once as a hipGraph and replayed
     # (vilco_amd/graph.py) -- ~1500 launches enqueued by the runtime instead of by ~25 ms of Python.  Same kernels, same
@@ -355,7 +397,7 @@ def main():
         graphed = GraphedStep(model, None, eager_steps=2, reducer=reducer)
 
         def step():
-            graphed(batch)
+            return graphed(batch)
         if distributed:
             # Every rank must take the same path (replayed or eager) from the first timed step on: the capture is attempted here,
             # outside any step (a staged capture issues no collective), and the ranks agree on the outcome -- a capture that this
@@ -379,11 +421,14 @@ def main():
             torch.cuda.synchronize()
 
     # A cold process on a cold device runs the first ~40 steps 8 % slower (code objects loading, allocator growth, clock
-    # ramp; same-box A/B, r02): settle for a fixed wall time before the W warm-up steps the contract asks for.  Untimed.
+    # ramp; same-box A/B, r02): settle for ~3 s before the W warm-up steps the contract asks for.  Untimed.  Counted in steps,
+    # not measured on the clock: VILCO_BENCH_SETTLE_S seconds of config-P steps at 50 a second (150 by default), so that the
+    # state the timed steps start from (dropout step word, stochastic-depth draws, loss-normaliser EMA) depends on the
+    # arguments alone, and so does what --dump-outputs writes.
     if not dry:
-        t_settle = time.perf_counter()
-        while time.perf_counter() - t_settle < float(os.environ.get("VILCO_BENCH_SETTLE_S", "3.0")):
-            for _ in range(5):
+        settle = int(round(float(os.environ.get("VILCO_BENCH_SETTLE_S", "3.0")) * 50))
+        for i in range(0, settle, 5):
+            for _ in range(min(5, settle - i)):
                 step()
             torch.cuda.synchronize()
     for _ in range(args.warmup):
@@ -391,7 +436,7 @@ def main():
     fence()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        last = step()
     fence()
     dt = time.perf_counter() - t0
     if distributed:
@@ -400,11 +445,13 @@ def main():
         dt = float(tmax.item())
     ms = dt / args.steps * 1e3
     clips_per_s = world * args.batch * args.steps / dt
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last, model.named_parameters())
 
-    # Diagnostics of the gradient exchange (EVERY rank runs them: they contain collectives): each bucket's all-reduce
+    # --full: diagnostics of the gradient exchange (EVERY rank runs them: they contain collectives): each bucket's all-reduce
     # alone, and the same step without the exchange -- what the exchange costs, and how much of it backward hides.
     multi = None
-    if reducer is not None:
+    if reducer is not None and args.full:
         buckets = reducer.profile_buckets()
         reducer.enabled = False
         for _ in range(2):
@@ -472,12 +519,14 @@ def main():
         if multi is not None:
             out["multi_gpu"] = multi
         if dry:
-            step()                                               # a rank-local step: must not touch the process group
+            if args.full:
+                step()                                           # a rank-local step: must not touch the process group
             out["dryrun"] = True
         else:
             out["step_mode"] = ("hipGraph replay of the captured forward + backward (vilco_amd/graph.py): %d capture(s), %d replays"
                                 % (graphed.stats['captured'], graphed.stats['replayed'])) if graphed is not None else "eager launches"
-            local_sections(out, args, model, step, eager_step, dev, ms, world, batch)
+            if args.full:
+                local_sections(out, args, model, step, eager_step, dev, ms, world, batch)
         print(json.dumps(out), flush=True)
     if distributed:
         dist.barrier()

@@ -132,7 +132,7 @@ def test_replayed_step_exchange_equals_eager_world2():
 
 
 def test_bench_protocol_two_ranks():
-    """`bench.py --gpus 2` under torch.distributed.run terminates and rank 0 prints ONE JSON line: the rank /
+    """`bench.py --gpus 2 --full` under torch.distributed.run terminates and rank 0 prints ONE JSON line: the rank /
     collective protocol of bench.py exercised on CPU + gloo (VILCO_BENCH_DRYRUN swaps the HIP model for a small torch
     module; everything else -- reducer, fences, the rank-local sections after the timed region -- is the real code)."""
     import json
@@ -143,7 +143,7 @@ def test_bench_protocol_two_ranks():
     port = 29500 + ((os.getpid() + 7) % 2000)
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                         "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(root, "bench.py"),
-                        "--gpus", "2", "--steps", "3", "--warmup", "1"], capture_output=True, text=True, timeout=240,
+                        "--gpus", "2", "--steps", "3", "--warmup", "1", "--full"], capture_output=True, text=True, timeout=240,
                        env=env, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -171,6 +171,34 @@ def test_bench_bare_gpus_form_self_launches():
     assert len(lines) == 1, r.stdout
     out = json.loads(lines[0])
     assert out["n_gpus"] == 2 and out["steps"] == 3 and out["value"] > 0
+
+
+def test_bench_dump_outputs_reproducible(tmp_path):
+    """`bench.py --dump-outputs DIR` writes the last timed step's losses and gradients as float32 .npy files, and two runs
+    with the same arguments write the same arrays (VILCO_BENCH_DRYRUN: the small torch module on CPU in place of the HIP
+    model, the rest of the plain path as it runs on the GPU)."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
+    env["VILCO_BENCH_DRYRUN"] = "1"
+    dumps = []
+    for run in range(2):
+        d = str(tmp_path / ("run%d" % run))
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2",
+                            "--dump-outputs", d], capture_output=True, text=True, timeout=240, env=env, cwd=root)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, r.stdout
+        out = json.loads(lines[0])
+        assert out["steps"] == 4 and out["ms_per_step"] > 0 and "roofline" not in out and "cpu_baseline" not in out
+        dumps.append({f: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d))})
+    names = {"loss.loss.npy"} | {"grad.%s.npy" % n for n in ("0.weight", "0.bias", "2.weight", "2.bias")}
+    assert set(dumps[0]) == names
+    for f, a in dumps[0].items():
+        assert a.dtype == np.float32 and np.isfinite(a).all(), f
+        assert np.array_equal(a, dumps[1][f]), f
 
 
 class _FakeDetector(torch.nn.Module):

@@ -1,9 +1,9 @@
-"""gpurun_out/<TAG>_* -> profiles/ (bench line, kernel stats, PMC traffic summary) and a printed recap.  TAG from argv[1] (default r02_z)."""
+"""$OUT/<TAG>_* (tools/run_final.sh) -> profiles/ (bench line, kernel stats, PMC traffic summary) and a printed recap.  TAG from argv[1] (default r02_z)."""
 import json, csv, shutil, os, sys
 TAG = sys.argv[1] if len(sys.argv) > 1 else "r03_z"
 RND = TAG.split("_")[0]
 R = os.path.join(os.path.dirname(os.path.abspath(__file__)), '..')
-g = lambda f: os.path.join(R, 'gpurun_out', f)
+g = lambda f: os.path.join(os.environ.get('OUT', os.path.join(R, 'out')), f)     # tools/run_final.sh's $OUT
 f = json.load(open(g(TAG + '_pmc_fetch.json'))); w = json.load(open(g(TAG + '_pmc_write.json')))
 def agg(rows, key):
     tot = n = 0
