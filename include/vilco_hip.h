@@ -628,6 +628,39 @@ int vilco_softnms_1d(const float* segs, const float* scores, const int64_t* seg_
 int vilco_nms_set_kernel(int32_t kind);
 int vilco_nms_last_kernels(void);
 
+/* ------------------------------------------------------------------------------------------ */
+/* MQ evaluation on the device (evaluate.hip): ANETdetection's AP over tIoU thresholds           */
+/* (MQ/libs/utils/metrics.py:274-393) and evaluation_retrieval's Recall@K                        */
+/* (MQ/libs/utils/get_retrieval_performance.py:116-183).  All arithmetic fp64, match decisions    */
+/* bit-identical; no float atomics (repeated calls are bitwise equal).  Threshold and rank lists   */
+/* are HOST arrays (copied into kernel arguments); every other pointer is device memory.           */
+/* ------------------------------------------------------------------------------------------ */
+/* Detection AP.  pred_*[n_pred]: video index (outside [0, n_vid): no GT, every threshold an FP), */
+/* class index (outside [0, n_cls): ignored), start, end, score.  Ground truth sorted into         */
+/* (class, video) groups, each group's rows in the reference's GT order: gt_start / gt_end[n_gt],  */
+/* grp_off[n_grp + 1] (grp_off[n_grp] == n_gt), grp_cls / grp_vid[n_grp]; cls_npos[n_cls] = GT     */
+/* count per class.  Outputs ap[n_thr][n_cls] and, when tp_flags is not null, the TP flag of every */
+/* prediction [n_thr][n_pred] in input order.  Score ties rank the later row first; tIoU ties      */
+/* match the later GT first.  n_thr <= 16, n_cls < 65536, n_vid < 2^24 - 1 (else UNSUPPORTED).     */
+size_t vilco_det_ap_workspace(int64_t n_pred, int32_t n_gt, int32_t n_thr);
+int vilco_det_ap(const int32_t* pred_vid, const int32_t* pred_cls, const double* pred_start, const double* pred_end,
+                 const double* pred_score, int64_t n_pred, const double* gt_start, const double* gt_end,
+                 const int32_t* grp_off, const int32_t* grp_cls, const int32_t* grp_vid, int32_t n_grp, int32_t n_gt,
+                 const int32_t* cls_npos, int32_t n_cls, int32_t n_vid, const double* thresholds, int32_t n_thr,
+                 double* ap, uint8_t* tp_flags, void* workspace, size_t workspace_bytes, void* stream);
+/* Recall@K.  One group per (video, class name) of the ground truth: its GT rows                  */
+/* gt_*[grp_gt_off[g] .. grp_gt_off[g + 1]) and its predictions, in result order,                 */
+/* pred_*[grp_pred_off[g] .. + grp_pred_cnt[g]).  A GT is retrieved at (threshold t, rank r) when  */
+/* one of the group's first r * n_gt predictions overlaps it by more than t (intersection over     */
+/* the hull).  Outputs hits[n_thr][n_rank] (int64 counts) and *total = number of GT;               */
+/* recall = hits / total.  n_thr <= 16, n_rank <= 8.                                               */
+size_t vilco_retrieval_hits_workspace(int32_t n_grp, int32_t n_thr, int32_t n_rank);
+int vilco_retrieval_hits(const double* pred_start, const double* pred_end, const int32_t* grp_pred_off,
+                         const int32_t* grp_pred_cnt, const double* gt_start, const double* gt_end,
+                         const int32_t* grp_gt_off, int32_t n_grp, const double* thresholds, int32_t n_thr,
+                         const int32_t* ranks, int32_t n_rank, int64_t* hits, int64_t* total, void* workspace,
+                         size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

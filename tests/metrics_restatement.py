@@ -1,0 +1,148 @@
+"""NumPy restatement of the MQ evaluators (MQ/libs/utils/metrics.py:274-393, get_retrieval_performance.py:116-195), written
+from the definitions, with the project's tie rule (the later row first on equal scores / equal tIoU) and the TP flags of every
+prediction.  Test infrastructure only: the product scores on the device (vilco_amd.utils.metrics)."""
+import numpy as np
+
+
+def _desc(x):
+    """the reverse of a stable ascending sort: NaN first, equal keys with the later row first"""
+    return np.argsort(x, kind='stable')[::-1]
+
+
+def det_ap(vidx, cls, ts, te, score, gt_vidx, gt_cls, gt_s, gt_e, n_cls, thresholds):
+    """ap[n_thr, n_cls], tp flags [n_thr, n_pred] (input order).  Predictions with cls outside [0, n_cls) are ignored,
+    those of a video without GT of their class are FPs.  GT rows in the reference's order."""
+    thr = np.asarray(thresholds, dtype=np.float64)
+    n_thr, n = len(thr), len(cls)
+    ap = np.zeros((n_thr, n_cls))
+    tp_all = np.zeros((n_thr, n), dtype=bool)
+    for c in range(n_cls):
+        gsel = np.flatnonzero(gt_cls == c)
+        npos = float(len(gsel))
+        rows = np.flatnonzero(cls == c)
+        if len(rows) == 0:
+            continue
+        rows = rows[_desc(score[rows])]
+        by_video = {}
+        for j in gsel:
+            by_video.setdefault(int(gt_vidx[j]), []).append(j)
+        locked = {v: np.zeros((n_thr, len(js)), dtype=bool) for v, js in by_video.items()}
+        tp = np.zeros((n_thr, len(rows)))
+        for k, r in enumerate(rows):
+            js = by_video.get(int(vidx[r]))
+            if js is None:
+                continue
+            gs, ge = gt_s[js], gt_e[js]
+            inter = (np.minimum(te[r], ge) - np.maximum(ts[r], gs)).clip(0)
+            with np.errstate(invalid='ignore', divide='ignore'):
+                tiou = inter / ((ge - gs) + (te[r] - ts[r]) - inter)
+            order = _desc(tiou)
+            lk = locked[int(vidx[r])]
+            for t in range(n_thr):
+                for j in order:
+                    if tiou[j] < thr[t]:
+                        break
+                    if lk[t, j]:
+                        continue
+                    lk[t, j] = True
+                    tp[t, k] = 1
+                    tp_all[t, r] = True
+                    break
+        fp = 1 - tp
+        tpc, fpc = np.cumsum(tp, axis=1), np.cumsum(fp, axis=1)
+        rec, prec = tpc / npos, tpc / (tpc + fpc)
+        for t in range(n_thr):
+            mprec = np.hstack([[0], prec[t], [0]])
+            mrec = np.hstack([[0], rec[t], [1]])
+            mprec = np.maximum.accumulate(mprec[::-1])[::-1]
+            idx = np.flatnonzero(mrec[1:] != mrec[:-1]) + 1
+            ap[t, c] = np.sum((mrec[idx] - mrec[idx - 1]) * mprec[idx])
+    return ap, tp_all
+
+
+def overlap(ps, pe, gs, ge):
+    """get_retrieval_performance.py:186-195: intersection over the hull, [n_pred, n_gt]"""
+    inter = np.maximum(0.0, np.minimum(pe[:, None], ge[None, :]) - np.maximum(ps[:, None], gs[None, :]))
+    union = np.maximum(0.0, np.maximum(pe[:, None], ge[None, :]) - np.minimum(ps[:, None], gs[None, :]))
+    with np.errstate(invalid='ignore', divide='ignore'):
+        return 1.0 * inter / union
+
+
+def retrieval_hits(groups, tious=(0.1, 0.2, 0.3, 0.4, 0.5), ranks=(1, 5)):
+    """groups: [(pred [n, 2], gt [m, 2])] -> (hits[n_thr, n_rank], total)"""
+    hits = np.zeros((len(tious), len(ranks)), dtype=np.int64)
+    total = 0
+    for pred, gt in groups:
+        pred, gt = np.asarray(pred, np.float64).reshape(-1, 2), np.asarray(gt, np.float64).reshape(-1, 2)
+        m = len(gt)
+        total += m
+        if len(pred) == 0:
+            continue
+        ov = overlap(pred[:, 0], pred[:, 1], gt[:, 0], gt[:, 1])
+        for i, t in enumerate(tious):
+            for j, r in enumerate(ranks):
+                hits[i, j] += int((ov[:r * m] > t).any(axis=0).sum())
+    return hits, total
+
+
+# ----------------------------------------------------------------------------------------------- golden-case plumbing
+GOLDENS = ("json", "large", "cl", "formats")
+
+
+def golden(name):
+    import os
+    return np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "metrics_%s.npz" % name))
+
+
+def ann_file(g, tmp_path):
+    """the case's annotation file (CL: the pickle) under tmp_path"""
+    import json
+    import pickle
+    ann = json.loads(str(g['ann']))
+    if bool(g['use_cl']):
+        p = tmp_path / "ann.pkl"
+        p.write_bytes(pickle.dumps(ann))
+    else:
+        p = tmp_path / "ann.json"
+        p.write_text(json.dumps(ann))
+    return str(p)
+
+
+def preds(g, e):
+    return {'video-id': [str(x) for x in g['pred%d_vid' % e]], 't-start': g['pred%d_ts' % e], 't-end': g['pred%d_te' % e],
+            'label': g['pred%d_label' % e], 'score': g['pred%d_score' % e]}
+
+
+def task(g, e):
+    t = int(g['task%d' % e])
+    return None if t < 0 else t
+
+
+def restated_det(path, g, e):
+    """the restatement on the host columns the product packs (vilco_amd.utils.metrics' loaders / remap, no GPU)"""
+    from vilco_amd.utils import metrics as M
+    use_cl = bool(g['use_cl'])
+    gt, ai = M.load_gt_seg_from_json(path, split=str(g['split']) or None, use_cl=use_cl)
+    t = task(g, e)
+    if use_cl:
+        gt, ai = gt[t], ai[t]
+    vindex = {v: i for i, v in enumerate(sorted(set(gt['video-id'])))}
+    gvid = np.array([vindex[v] for v in gt['video-id']], dtype=np.int64)
+    p = preds(g, e)
+    cls = p['label'] if use_cl else M._remap(p['label'], ai)
+    vidx = M._video_index(np.asarray(p['video-id'], dtype=object), vindex)
+    return det_ap(vidx, cls, p['t-start'], p['t-end'], p['score'], gvid, gt['label'], gt['t-start'], gt['t-end'], len(ai),
+                  g['thr'])
+
+
+def restated_recall(path, g, e):
+    import json
+    from vilco_amd.utils import metrics as M
+    mr = M.Moment_Retrieval.__new__(M.Moment_Retrieval)
+    mr.use_cl = bool(g['use_cl'])
+    mr.ground_truth = M._load_retrieval_gt(path, str(g['split']), mr.use_cl)
+    mr.prediction = M._load_retrieval_pred(json.loads(str(g['rjson%d' % e])))
+    ps, pe, poff, pcnt, gs, ge, goff = mr.pack(task(g, e))
+    groups = [(np.stack([ps[o:o + c], pe[o:o + c]], 1), np.stack([gs[goff[k]:goff[k + 1]], ge[goff[k]:goff[k + 1]]], 1))
+              for k, (o, c) in enumerate(zip(poff, pcnt))]
+    return retrieval_hits(groups)

@@ -182,6 +182,12 @@ SIGNATURES = {
                                    c_fp, sz, c_fp]),
     "vilco_nms_set_kernel": (C.c_int, [i32]),
     "vilco_nms_last_kernels": (C.c_int, []),
+    "vilco_det_ap_workspace": (sz, [i64, i32, i32]),
+    "vilco_det_ap": (C.c_int, [c_fp, c_fp, c_fp, c_fp, c_fp, i64, c_fp, c_fp, c_fp, c_fp, c_fp, i32, i32, c_fp, i32, i32,
+                               C.POINTER(C.c_double), i32, c_fp, c_fp, c_fp, sz, c_fp]),
+    "vilco_retrieval_hits_workspace": (sz, [i32, i32, i32]),
+    "vilco_retrieval_hits": (C.c_int, [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, i32, C.POINTER(C.c_double), i32,
+                                       C.POINTER(i32), i32, c_fp, c_fp, c_fp, sz, c_fp]),
 }
 
 _lib = None
