@@ -660,6 +660,24 @@ int vilco_retrieval_hits(const double* pred_start, const double* pred_end, const
                          const int32_t* grp_gt_off, int32_t n_grp, const double* thresholds, int32_t n_thr,
                          const int32_t* ranks, int32_t n_rank, int64_t* hits, int64_t* total, void* workspace,
                          size_t workspace_bytes, void* stream);
+/* NLQ Recall@K over IoU and mIoU (ReferringRecall).  Query q has one ground-truth window           */
+/* gt[q] = (start, end), fp64, and pred_cnt[q] predictions pred[q][0 .. cnt) = (start, end) in        */
+/* result order, 0 <= cnt <= k_cap; rows past the count are never read.  pred is fp32 when            */
+/* pred_fp32 != 0, else fp64; gt must be 16-byte aligned, pred 8 (fp32) or 16 (fp64).  seg_id[q] in   */
+/* [0, n_seg) is the segment (template, task) of the query; null: one segment; ids outside the        */
+/* range are counted nowhere.  mode 0: fp64, intersection and hull clamped at 0 (NumPy               */
+/* compute_IoU); mode 1: operands rounded to fp32, intersection clamped, hull not, correctly          */
+/* rounded fp32 quotient widened to fp64 (torch _iou).  A 0/0 IoU is NaN and NaN is not > t.          */
+/* Outputs: hits[n_seg][n_thr][n_rank] = queries of the segment for which one of the first            */
+/* min(ranks[r], cnt) predictions has IoU > thresholds[t]; n[n_seg] = queries per segment;            */
+/* top1[n_query] = IoU of the first prediction (NaN when cnt == 0); top1_sum[n_seg] = its sum per     */
+/* segment in a fixed order (repeated calls are bit-equal); flags (optional)                          */
+/* [n_query][n_thr][n_rank].  n_thr <= 16, n_rank <= 8 (else UNSUPPORTED), ranks >= 1, k_cap >= 1.    */
+size_t vilco_nlq_recall_workspace(int64_t n_query, int32_t n_rank);
+int vilco_nlq_recall(const void* pred, int32_t pred_fp32, const int32_t* pred_cnt, int32_t k_cap, const double* gt,
+                     const int32_t* seg_id, int64_t n_query, int32_t n_seg, const double* thresholds, int32_t n_thr,
+                     const int32_t* ranks, int32_t n_rank, int32_t mode, int64_t* hits, int64_t* n, double* top1,
+                     double* top1_sum, uint8_t* flags, void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -2,7 +2,14 @@
 thresholds, 4 000 videos.  Prints one JSON line: the device time of vilco_det_ap (HIP events, after warm-up), the host
 preparation time of ANETdetection.evaluate (id / label mapping and column packing), the whole evaluate(), and the NumPy
 restatement's CPU time on the same inputs for scale (--no-cpu skips it).
-Run:  python tools/eval_bench.py [--preds 400000] [--no-cpu]"""
+Run:  python tools/eval_bench.py [--preds 400000] [--no-cpu]
+
+--nlq times the NLQ scorer instead (vilco_nlq_recall): 5 000 queries x 5 rows in 13 segments, about the Ego4D NLQ validation
+set under the shipped config.  One JSON line: the device time of one launch over the whole stream, the host preparation of
+record dicts (key lookup and row packing), `evaluate()` end to end for dicts and for the device-resident stream,
+`evaluate_segments` (all 13 cumulative tables), the 13 prefix evaluations of the dict path, and the NumPy restatement on the
+CPU for the same input.
+Run:  python tools/eval_bench.py --nlq [--queries 5000] [--rows 5] [--segments 13]"""
 import argparse
 import ctypes as C
 import json
@@ -26,7 +33,13 @@ def main():
     ap.add_argument("--videos", type=int, default=4000)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--nlq", action="store_true")
+    ap.add_argument("--queries", type=int, default=5000)
+    ap.add_argument("--rows", type=int, default=5)
+    ap.add_argument("--segments", type=int, default=13)
     a = ap.parse_args()
+    if a.nlq:
+        return nlq(a)
     from vilco_amd import _lib
     from vilco_amd.utils import metrics as M
     rng = np.random.default_rng(0)
@@ -96,6 +109,83 @@ def main():
                            ev.ground_truth['t-end'], gt.n_cls, thr)
         res["restatement_cpu_s"] = round(time.perf_counter() - t0, 2)
         res["max_abs_ap_diff_vs_restatement"] = float(np.abs(ap_r - ev.ap).max())
+    print(json.dumps(res))
+
+
+def nlq(a):
+    import contextlib
+    import io
+    import nlq_metrics_restatement as R
+    from vilco_amd.utils import make_nlq_evaluator, metrics_nlq as M
+    rng = np.random.default_rng(5)
+    n_clip = max(a.queries // 6, 1)
+    clips = []
+    for c in range(n_clip):
+        qs = []
+        for _ in range(6):
+            s = round(float(rng.uniform(0, 400)), 3)
+            qs.append({"clip_start_sec": s, "clip_end_sec": round(s + float(rng.uniform(1, 60)), 3)})
+        clips.append({"clip_uid": "c%d" % c, "annotations": [{"annotation_uid": "a%d" % c, "language_queries": qs}]})
+    gt = {"videos": [{"clips": clips}]}
+    win = R.gt_windows(gt)
+    recs, seg = [], []
+    for q in range(a.queries):
+        c, i = int(rng.integers(0, n_clip)), int(rng.integers(0, 6))
+        s, e = win[("c%d" % c, "a%d" % c)][i]
+        x = s + rng.normal(0, 0.6 * (e - s), a.rows)
+        y = e + rng.normal(0, 0.6 * (e - s), a.rows)
+        rows = np.stack([np.minimum(x, y), np.maximum(x, y), rng.uniform(size=a.rows)], axis=1).astype(np.float32)
+        recs.append({"query_idx": i, "annotation_uid": "a%d" % c, "predicted_times": rows.tolist(), "clip_uid": "c%d" % c})
+        seg.append(q * a.segments // a.queries)
+    with tempfile.TemporaryDirectory() as tmp:
+        ev = make_nlq_evaluator(R.write_ego4d(gt, tmp))
+    st = ev.new_stream()
+    for r, s in zip(recs, seg):
+        t = torch.tensor(r['predicted_times'])                     # host rows, as the model's postprocessing leaves them
+        st.append((r['clip_uid'], r['annotation_uid'], r['query_idx']), t[:, :2], t[:, 2], s)
+
+    def timed(fn, reps=5):
+        with contextlib.redirect_stdout(io.StringIO()):
+            fn()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(reps):
+                out = fn()
+            torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / reps, out
+
+    def prep():
+        gi = [ev._gt.index((p["clip_uid"], p["annotation_uid"], p["query_idx"])) for p in recs]
+        return gi, M._pack_records([p["predicted_times"] for p in recs], 10)
+    t_prep, _ = timed(prep)
+    t_dict, (tab_d, _) = timed(lambda: ev.evaluate(recs, verbose=True))
+    t_stream, (tab_s, _) = timed(lambda: ev.evaluate(st, verbose=True))
+    t_segs, tabs = timed(lambda: ev.evaluate_segments(st, verbose=True))
+    t_prefix, _ = timed(lambda: [ev.evaluate([r for r, s in zip(recs, seg) if s <= k], verbose=True) for k in range(a.segments)],
+                        reps=2)
+    assert tab_d.tobytes() == tab_s.tobytes() == tabs[-1][0].tobytes()
+    pred, cnt, gi, sg = st.device_columns()
+    gtd = ev._gt.device()[gi]
+    run = lambda: M.nlq_recall_device(pred, cnt, gtd, ev.thresholds, ev.topK, 0, seg_id=sg, n_seg=a.segments)   # noqa: E731
+    for _ in range(3):
+        run()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(a.iters):
+        run()
+    e1.record()
+    torch.cuda.synchronize()
+    res = {"queries": a.queries, "rows": a.rows, "segments": a.segments,
+           "device_ms": round(e0.elapsed_time(e1) / a.iters, 4), "host_prep_dicts_ms": round(t_prep * 1e3, 2),
+           "evaluate_dicts_ms": round(t_dict * 1e3, 2), "evaluate_stream_ms": round(t_stream * 1e3, 2),
+           "evaluate_segments_ms": round(t_segs * 1e3, 2), "prefix_evaluations_dicts_ms": round(t_prefix * 1e3, 2),
+           "R": [[round(float(x), 4) for x in row] for row in tab_s]}
+    if not a.no_cpu:
+        t0 = time.perf_counter()
+        flags, _ = R.evaluate(recs, win)
+        res["restatement_cpu_ms"] = round((time.perf_counter() - t0) * 1e3, 1)
+        assert np.array_equal(R.recall(flags) * 100, tab_s)
     print(json.dumps(res))
 
 

@@ -1,4 +1,4 @@
-// MQ evaluation on the device: detection AP over tIoU thresholds (MQ/libs/utils/metrics.py:274-393) and Recall@K over tIoU
+// MQ and NLQ evaluation on the device: detection AP over tIoU thresholds (MQ/libs/utils/metrics.py:274-393) and Recall@K over tIoU
 // (MQ/libs/utils/get_retrieval_performance.py:116-183).  Every tIoU, precision and recall value is fp64 in the reference's
 // expression order and this file is compiled with -ffp-contract=off, so match decisions are bit-identical.
 //
@@ -13,6 +13,7 @@
 //   ap       one workgroup per (class, threshold): integer prefix counts of the TP flags in rank order, fp64 precision /
 //            recall, the reverse running maximum and the sum of interpolated_prec_rec, in fixed order.
 // No float atomics, no allocation, no host synchronisation; workgroups meet only at launch boundaries.
+// NLQ Recall@K over IoU and mIoU (NLQ/libs/utils/metrics.py:47-68, 107-177): see the section further down.
 #include "common.h"
 
 namespace {
@@ -372,6 +373,129 @@ __global__ __launch_bounds__(64) void ev_hits_kernel(const double* __restrict__ 
   }
 }
 
+// ------------------------------------------------------------------------------------------------ NLQ Recall@K and mIoU
+// NLQ/libs/utils/metrics.py ReferringRecall: one ground-truth window per query, the query's predictions in result order.
+//   mode 0  compute_IoU (:47-68, NumPy, fp64): intersection and hull both clamped at 0, overlap = 1.0 * inter / union
+//   mode 1  _iou (:142-147, torch, fp32): operands rounded to fp32, intersection clamped, hull not, fp32 quotient widened
+// query kernel    one lane per query: IoU of its first min(cnt, max K) rows, top1[q], one 16-bit word of threshold bits per
+//                 (rank, query) into the workspace, optionally the flags [q][t][r]
+// segment kernel  one workgroup per segment: integer sums of the words' bits, the query count and the sum of top1, each
+//                 thread over its queries in index order, then a fixed tree -- no atomics, repeated calls are bit-equal.
+//                 It reads n_seg * n_query segment ids; n_seg is the number of query templates (13 in the benchmark).
+enum { NLQ_NUMPY64 = 0, NLQ_TORCH32 = 1 };
+
+// np.maximum / np.minimum and torch.max / torch.min: NaN propagates
+__device__ __forceinline__ double nmax(double a, double b) { return (a >= b || a != a) ? a : b; }
+__device__ __forceinline__ double nmin(double a, double b) { return (a <= b || a != a) ? a : b; }
+__device__ __forceinline__ float nmaxf(float a, float b) { return (a >= b || a != a) ? a : b; }
+__device__ __forceinline__ float nminf(float a, float b) { return (a <= b || a != a) ? a : b; }
+
+__device__ __forceinline__ double nlq_iou64(double ps, double pe, double gs, double ge) {
+  const double inter = nmax(0.0, nmin(pe, ge) - nmax(ps, gs));
+  const double uni = nmax(0.0, nmax(pe, ge) - nmin(ps, gs));
+  return 1.0 * inter / uni;
+}
+
+__device__ __forceinline__ double nlq_iou32(float ps, float pe, float gs, float ge) {
+  const float inter = nminf(pe, ge) - nmaxf(ps, gs);
+  const float uni = nmaxf(pe, ge) - nminf(ps, gs);
+  const float cl = (inter < 0.0f) ? 0.0f : inter;              // clamp(min=0); NaN stays NaN
+  // the fp32 quotient, correctly rounded: 53 >= 2 * 24 + 2 bits, so rounding the fp64 quotient again is exact rounding
+  const float q = (float)((double)cl / (double)uni);
+  return (double)q;
+}
+
+template <typename T2>
+__global__ __launch_bounds__(RT) void ev_nlq_query_kernel(const T2* __restrict__ pred, const int* __restrict__ pred_cnt,
+                                                          int k_cap, const double2* __restrict__ gt, int n, Thr thr, int n_thr,
+                                                          Ranks rk, int n_rank, int mode, double* __restrict__ top1,
+                                                          unsigned short* __restrict__ words,
+                                                          unsigned char* __restrict__ flags) {
+  const int q = blockIdx.x * RT + threadIdx.x;
+  if (q >= n) return;
+  int rmax = 1;
+  for (int r = 0; r < n_rank; ++r) rmax = rk.r[r] > rmax ? rk.r[r] : rmax;
+  int cnt = pred_cnt[q];
+  cnt = cnt < 0 ? 0 : (cnt > k_cap ? k_cap : cnt);              // rows past the count (and past k_cap) are never read
+  const int m = cnt < rmax ? cnt : rmax;
+  const double2 g = gt[q];
+  const float gsf = (float)g.x, gef = (float)g.y;
+  const T2* rows = pred + (long)q * k_cap;
+  unsigned hit[MAX_RANK];                                       // bit t: one of the first K rows has IoU > threshold t
+#pragma unroll
+  for (int r = 0; r < MAX_RANK; ++r) hit[r] = 0u;
+  double first = __longlong_as_double(0x7ff8000000000000ll);    // a query without rows has no first IoU
+  for (int i = 0; i < m; ++i) {
+    const T2 p = rows[i];
+    const double ov = mode == NLQ_TORCH32 ? nlq_iou32((float)p.x, (float)p.y, gsf, gef)
+                                          : nlq_iou64((double)p.x, (double)p.y, g.x, g.y);
+    if (i == 0) first = ov;
+    unsigned bits = 0u;
+    for (int t = 0; t < n_thr; ++t) bits |= (ov > thr.t[t]) ? (1u << t) : 0u;
+#pragma unroll
+    for (int r = 0; r < MAX_RANK; ++r)
+      if (r < n_rank && i < rk.r[r]) hit[r] |= bits;
+  }
+  top1[q] = first;
+#pragma unroll
+  for (int r = 0; r < MAX_RANK; ++r)
+    if (r < n_rank) {
+      words[(long)r * n + q] = (unsigned short)hit[r];
+      if (flags)
+        for (int t = 0; t < n_thr; ++t) flags[((long)q * n_thr + t) * n_rank + r] = (unsigned char)((hit[r] >> t) & 1u);
+    }
+}
+
+// block-wide integer sum (RT threads); every thread gets the total
+__device__ __forceinline__ long long block_sum_rt(long long v, long long* lds /* >= RT/64 */) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
+  __syncthreads();
+  long long s = 0;
+  for (int w = 0; w < RT / 64; ++w) s += lds[w];
+  return s;
+}
+
+__global__ __launch_bounds__(RT) void ev_nlq_segment_kernel(const unsigned short* __restrict__ words,
+                                                            const double* __restrict__ top1, const int* __restrict__ seg_id,
+                                                            int n, int n_thr, int n_rank, long long* __restrict__ hits,
+                                                            long long* __restrict__ n_out, double* __restrict__ sum_out) {
+  __shared__ long long li[RT / 64];
+  __shared__ double sd[RT];
+  const int s = blockIdx.x, tid = threadIdx.x;
+  for (int r = 0; r < n_rank; ++r) {
+    int c[MAX_THR];
+#pragma unroll
+    for (int t = 0; t < MAX_THR; ++t) c[t] = 0;
+    for (int q = tid; q < n; q += RT) {
+      if ((seg_id ? seg_id[q] : 0) != s) continue;              // ids outside [0, n_seg) belong to no segment
+      const unsigned w = words[(long)r * n + q];
+#pragma unroll
+      for (int t = 0; t < MAX_THR; ++t) c[t] += (int)((w >> t) & 1u);
+    }
+#pragma unroll
+    for (int t = 0; t < MAX_THR; ++t)
+      if (t < n_thr) {
+        const long long tot = block_sum_rt((long long)c[t], li);
+        if (tid == 0) hits[((long)s * n_thr + t) * n_rank + r] = tot;
+      }
+  }
+  int cnt = 0;
+  double acc = 0.0;
+  for (int q = tid; q < n; q += RT)
+    if ((seg_id ? seg_id[q] : 0) == s) { ++cnt; acc += top1[q]; }
+  const long long tot = block_sum_rt((long long)cnt, li);
+  sd[tid] = acc;
+  __syncthreads();
+  for (int o = RT / 2; o >= 1; o >>= 1) {
+    if (tid < o) sd[tid] = sd[tid] + sd[tid + o];
+    __syncthreads();
+  }
+  if (tid == 0) { n_out[s] = tot; sum_out[s] = sd[0]; }
+}
+
 struct DetWs {
   int *a, *b, *c, *pos1, *cls1, *hist, *tot;
   unsigned long long* key2;
@@ -496,5 +620,46 @@ extern "C" int vilco_retrieval_hits(const double* pred_start, const double* pred
   if (n_grp > 0)
     hipLaunchKernelGGL(ev_hits_kernel, dim3(n_grp), dim3(64), 0, s, pred_start, pred_end, grp_pred_off, grp_pred_cnt, gt_start,
                        gt_end, grp_gt_off, thr, (int)n_thr, rk, (int)n_rank, h);
+  return vilco_launch_status();
+}
+
+extern "C" size_t vilco_nlq_recall_workspace(int64_t n_query, int32_t n_rank) {
+  if (n_query < 0 || n_query > 0x7ffffffeL || n_rank < 1 || n_rank > MAX_RANK) return 0;
+  return al256((size_t)(n_query > 0 ? n_query : 1) * n_rank * sizeof(unsigned short)) + 256;
+}
+
+extern "C" int vilco_nlq_recall(const void* pred, int32_t pred_fp32, const int32_t* pred_cnt, int32_t k_cap, const double* gt,
+                                const int32_t* seg_id, int64_t n_query, int32_t n_seg, const double* thresholds, int32_t n_thr,
+                                const int32_t* ranks, int32_t n_rank, int32_t mode, int64_t* hits, int64_t* n, double* top1,
+                                double* top1_sum, uint8_t* flags, void* workspace, size_t workspace_bytes, void* stream) {
+  if (n_query < 0 || n_seg < 1 || n_thr < 0 || n_rank < 0 || k_cap < 1) return VILCO_ERR_BADARG;
+  if (!thresholds || !ranks || !hits || !n || !top1 || !top1_sum || !workspace) return VILCO_ERR_BADARG;
+  if (n_query > 0 && (!pred || !pred_cnt || !gt)) return VILCO_ERR_BADARG;
+  if (reinterpret_cast<uintptr_t>(gt) % 16 || reinterpret_cast<uintptr_t>(pred) % (pred_fp32 ? 8 : 16))
+    return VILCO_ERR_BADARG;                                   // rows are read as whole vectors
+  if (n_thr < 1 || n_thr > MAX_THR || n_rank < 1 || n_rank > MAX_RANK || n_query > 0x7ffffffeL) return VILCO_ERR_UNSUPPORTED;
+  if (mode != NLQ_NUMPY64 && mode != NLQ_TORCH32) return VILCO_ERR_UNSUPPORTED;
+  for (int r = 0; r < n_rank; ++r)
+    if (ranks[r] < 1) return VILCO_ERR_BADARG;
+  if (workspace_bytes < vilco_nlq_recall_workspace(n_query, n_rank)) return VILCO_ERR_WORKSPACE;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  unsigned short* words = reinterpret_cast<unsigned short*>((reinterpret_cast<uintptr_t>(workspace) + 255) / 256 * 256);
+  Thr thr{};
+  Ranks rk{};
+  for (int t = 0; t < n_thr; ++t) thr.t[t] = thresholds[t];
+  for (int r = 0; r < n_rank; ++r) rk.r[r] = ranks[r];
+  const int nq = (int)n_query;
+  if (nq > 0) {
+    const dim3 grid((unsigned)((nq + RT - 1) / RT));
+    const double2* g2 = reinterpret_cast<const double2*>(gt);
+    if (pred_fp32)
+      hipLaunchKernelGGL(ev_nlq_query_kernel<float2>, grid, dim3(RT), 0, s, reinterpret_cast<const float2*>(pred), pred_cnt,
+                         (int)k_cap, g2, nq, thr, (int)n_thr, rk, (int)n_rank, (int)mode, top1, words, flags);
+    else
+      hipLaunchKernelGGL(ev_nlq_query_kernel<double2>, grid, dim3(RT), 0, s, reinterpret_cast<const double2*>(pred), pred_cnt,
+                         (int)k_cap, g2, nq, thr, (int)n_thr, rk, (int)n_rank, (int)mode, top1, words, flags);
+  }
+  hipLaunchKernelGGL(ev_nlq_segment_kernel, dim3(n_seg), dim3(RT), 0, s, words, top1, seg_id, nq, (int)n_thr, (int)n_rank,
+                     reinterpret_cast<long long*>(hits), reinterpret_cast<long long*>(n), top1_sum);
   return vilco_launch_status();
 }

@@ -2,3 +2,5 @@ from .nms import batched_nms, nms_1d_cpu  # noqa: F401
 from .train_utils import (fix_random_seed, make_optimizer, make_scheduler, save_checkpoint,  # noqa: F401
                           train_step)
 from .metrics import ANETdetection  # noqa: F401
+from .metrics_nlq import (NLQRecordStream, ReferringRecall, evaluate_nlq_performance,  # noqa: F401
+                          make_nlq_evaluator)

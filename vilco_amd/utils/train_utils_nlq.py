@@ -12,7 +12,9 @@ What differs from the MQ glue (utils/train_utils.py):
   * `make_scheduler` knows the "constant" schedule (WarmupLRScheduler).
   * validation produces the evaluator's NLQ record format: a list of
     {'query_idx', 'annotation_uid', 'predicted_times': [[start, end, score], ...], 'clip_uid'} for the ego4d datasets,
-    {'query_id', 'predicted_times', 'video_id'} otherwise (:735-757).
+    {'query_id', 'predicted_times', 'video_id'} otherwise (:735-757).  With an evaluator that offers the stream interface
+    (`new_stream`, `evaluate_segments`: utils/metrics_nlq.py) the records go to a device-resident NLQRecordStream instead and
+    a whole validation is scored in one launch; `valid_one_epoch_nlq_singlegpu` (:610-700) is the non-CL validation.
 The optimizer is the same `FusedOptimizer` (multi-tensor clip + AdamW / SGD kernels, per-group learning rates and decay)."""
 import warnings
 
@@ -160,6 +162,55 @@ def _eval_mode(model):
         b.eval()
 
 
+def _segment_tables(evaluator, stream, n_sets):
+    """the table `evaluator.evaluate(accumulated records, verbose=True)` returns after each of the n_sets templates"""
+    return [t for t, _ in evaluator.evaluate_segments(stream, verbose=True, n_seg=n_sets)]
+
+
+def _valid_cl_stream(val_qilDatasetList, model, current_task_id, evaluator):
+    """valid_one_epoch_cl_single_gpu with the records kept on the device (NLQRecordStream) and one scoring launch"""
+    stream = evaluator.new_stream()
+    val_sets = val_qilDatasetList.get_valSet_by_taskNum(current_task_id + 1)
+    num_queries = 1
+    for n_task, (val_loader, num_queries) in enumerate(val_sets):
+        for video_list in val_loader:
+            output = model(video_list, task_id=current_task_id, is_training=False)
+            stream.extend(video_list, output, seg_id=n_task)
+    performance = _segment_tables(evaluator, stream, len(val_sets))[-1]
+    total = AverageMeter()
+    total.update(performance[0, 0], num_queries)
+    return total.avg
+
+
+@torch.no_grad()
+def valid_one_epoch_nlq_singlegpu(val_loader, model, curr_epoch, evaluator=None, output_file=None, tb_writer=None,
+                                  print_freq=20):
+    """:610-700 -- the non-CL validation: (performance, score_str) of the evaluator over the whole loader; with output_file
+    the Ego4D challenge submission is written as well (every `predicted_times` cut to 10 rows).  With an evaluator that
+    offers the stream interface the records stay on the device; the one host copy of the stream is made only when a file is
+    asked for."""
+    assert (evaluator is not None) or (output_file is not None)
+    from .metrics_nlq import submission
+    model.eval()
+    dataset = evaluator.dataset if evaluator is not None else "ego4d"
+    stream = evaluator.new_stream() if hasattr(evaluator, 'new_stream') else None
+    results = []
+    for video_list in val_loader:
+        output = model(video_list, is_training=False)
+        if stream is not None:
+            stream.extend(video_list, output)
+        else:
+            results.extend(prediction_records(video_list, output, dataset))
+    if output_file is not None:
+        import json
+        with open(output_file, "w") as f:
+            json.dump(submission(stream.records() if stream is not None else results), f)
+    if evaluator is None:                   # only the file was asked for (the reference stops here with an AttributeError)
+        return None, None
+    assert evaluator.dataset == "ego4d"
+    return evaluator.evaluate(stream if stream is not None else results, verbose=True)
+
+
 @torch.no_grad()
 def valid_one_epoch_cl_single_gpu(val_qilDatasetList, model, current_epoch, current_task_id, evaluator=None,
                                   output_file=None, tb_writer=None, print_freq=20, dataset_name='ego4d_cl'):
@@ -167,6 +218,8 @@ def valid_one_epoch_cl_single_gpu(val_qilDatasetList, model, current_epoch, curr
     evaluator sees the running list each time; the returned R@1 is that of the LAST evaluation (the reference updates its
     meter once, after the loop: :776)."""
     _eval_mode(model)
+    if hasattr(evaluator, 'new_stream'):
+        return _valid_cl_stream(val_qilDatasetList, model, current_task_id, evaluator)
     results, performance, num_queries = [], None, 1
     for val_loader, num_queries in val_qilDatasetList.get_valSet_by_taskNum(current_task_id + 1):
         for video_list in val_loader:
@@ -188,12 +241,26 @@ def final_validate(val_qilDatasetList, model, current_epoch, current_task_id, ev
         list_val_recall_ii = {'val': [], 'test': []}
     _eval_mode(model)
     total, bwf, results = AverageMeter(), AverageMeter(), []
-    for n_task, (val_loader, num_queries) in enumerate(val_qilDatasetList.get_valSet_by_taskNum(current_task_id + 1)):
-        for video_list in val_loader:
-            output = model(video_list, task_id=current_task_id, is_training=False, val_qilDatasetList=val_qilDatasetList)
-            results.extend(prediction_records(video_list, output, evaluator.dataset))
+    val_sets = val_qilDatasetList.get_valSet_by_taskNum(current_task_id + 1)
+    tables = None
+    if hasattr(evaluator, 'new_stream'):
+        # records stay on the device, ONE scoring launch; the table after each template follows from prefix sums
         assert evaluator.dataset == "ego4d_cl"
-        performance, _ = evaluator.evaluate(results, verbose=True)
+        stream = evaluator.new_stream()
+        for n_task, (val_loader, num_queries) in enumerate(val_sets):
+            for video_list in val_loader:
+                output = model(video_list, task_id=current_task_id, is_training=False, val_qilDatasetList=val_qilDatasetList)
+                stream.extend(video_list, output, seg_id=n_task)
+        tables = _segment_tables(evaluator, stream, len(val_sets))
+    for n_task, (val_loader, num_queries) in enumerate(val_sets):
+        if tables is not None:
+            performance = tables[n_task]
+        else:
+            for video_list in val_loader:
+                output = model(video_list, task_id=current_task_id, is_training=False, val_qilDatasetList=val_qilDatasetList)
+                results.extend(prediction_records(video_list, output, evaluator.dataset))
+            assert evaluator.dataset == "ego4d_cl"
+            performance, _ = evaluator.evaluate(results, verbose=True)
         if n_task == current_task_id:
             list_val_recall_ii[type_val].append(performance[0, 0])
         elif n_task < current_task_id:
