@@ -679,6 +679,41 @@ int vilco_nlq_recall(const void* pred, int32_t pred_fp32, const int32_t* pred_cn
                      const int32_t* ranks, int32_t n_rank, int32_t mode, int64_t* hits, int64_t* n, double* top1,
                      double* top1_sum, uint8_t* flags, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------ */
+/* Herding exemplar selection for the replay memory (herding.hip).  Replaces the reference's      */
+/* commented-out, unfinished branch MQ/libs/modeling/meta_archs.py:973-1043 (two pdb.set_trace(),  */
+/* a norm over the wrong axis, features[idx] indexed across levels); the random sampling that      */
+/* runs instead is :1046-1052.  A clip's descriptor is its feature pyramid, phi[i][l] = level-l    */
+/* map / its Frobenius norm (what `classify`, :1061-1131, averages).  With G[l] = Phi[l] Phi[l]^T: */
+/*   mu[l] = mean_i phi[i][l] / its norm,   a_i = mu . phi_i = rowsum_i(G) / sqrt(sum(G)),          */
+/*   mu . (phi_i + S) = a_i + sum_{j in sel} a_j,                                                  */
+/*   ||phi_i + S||^2 = G_ii + 2 sum_{j in sel} G_ij + sum_{j,j' in sel} G_jj',                      */
+/*   cost(i) = sum_l ( 2 - 2 (mu . (phi_i + S)) / ||phi_i + S|| ).                                 */
+/* No allocation, no host synchronisation, no float atomics; repeated calls are bit-equal.         */
+/* ------------------------------------------------------------------------------------------ */
+/* inv_norm[r] = 1 / ||x[r, 0:D]||_2 for the rows of fp32 x[rows][ld] (rows <= 65535, ld >= D):    */
+/* fp32 squares, per-thread fp32 sums, fixed trees and the sum over segments in fp64.              */
+size_t vilco_frob_scale_workspace(int64_t rows, int64_t D);
+int vilco_frob_scale(const float* x, int64_t rows, int64_t D, int64_t ld, float* inv_norm, void* workspace,
+                     size_t workspace_bytes, void* stream);
+/* G[N][N] = diag(row_scale) X X^T diag(row_scale) for fp32 X[N][ld] (row_scale null: ones).       */
+/* Exact fp32 products and fp32 accumulation (v_mfma_f32_32x32x2_f32) inside each of the K slabs   */
+/* the chip is split over, the slabs' partials added in slab order in fp64; G is written as fp32   */
+/* (g_fp64 == 0) or fp64 and is exactly symmetric.  Row offsets are 64-bit: N * D is not limited   */
+/* to 2^31 bytes as a vilco_gemm operand is.  N <= 32767.  The workspace holds the partials.       */
+size_t vilco_gram_workspace(int64_t N, int64_t D);
+int vilco_gram(const float* x, int64_t N, int64_t D, int64_t ld, const float* row_scale, void* g, int32_t g_fp64,
+               void* workspace, size_t workspace_bytes, void* stream);
+/* Greedy herding order.  grams: fp64 [n_cls][L][N][N] (every class N candidates, L levels),        */
+/* sel: int32 [n_cls][min(m, N)].  One workgroup per class, all arithmetic fp64 without            */
+/* contraction in the order written above: rowsum_i = sum_j G[i][j] in index order, sum(G) = the    */
+/* row sums in index order, cost = the levels in order; after a pick p: s += 2 r_p + G_pp,          */
+/* t += a_p, r_i += G[p][i].  Smallest cost wins, ties (and NaN, ranked as +inf) go to the smallest */
+/* index.  L <= 16, N <= 4096 (else UNSUPPORTED).                                                  */
+size_t vilco_herd_select_workspace(int32_t n_cls, int32_t L, int32_t N);
+int vilco_herd_select(const double* grams, int32_t n_cls, int32_t L, int32_t N, int32_t m, int32_t* sel,
+                      void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

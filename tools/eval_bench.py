@@ -9,7 +9,13 @@ set under the shipped config.  One JSON line: the device time of one launch over
 record dicts (key lookup and row packing), `evaluate()` end to end for dicts and for the device-resident stream,
 `evaluate_segments` (all 13 cumulative tables), the 13 prefix evaluations of the dict path, and the NumPy restatement on the
 CPU for the same input.
-Run:  python tools/eval_bench.py --nlq [--queries 5000] [--rows 5] [--segments 13]"""
+Run:  python tools/eval_bench.py --nlq [--queries 5000] [--rows 5] [--segments 13]
+
+--herding times the herding exemplar selection (csrc/herding.hip) for one class of --clips candidates whose descriptors have
+config P's level sizes (2304 .. 72 tokens x 1024 channels): device times of vilco_frob_scale, vilco_gram and
+vilco_herd_select, the level-0 Gram product alone with its fraction of the HBM peak in bytes of X read, and the same selection
+done as the literal greedy loop in torch ops on the device.
+Run:  python tools/eval_bench.py --herding [--clips 96] [--keep 10]"""
 import argparse
 import ctypes as C
 import json
@@ -37,9 +43,14 @@ def main():
     ap.add_argument("--queries", type=int, default=5000)
     ap.add_argument("--rows", type=int, default=5)
     ap.add_argument("--segments", type=int, default=13)
+    ap.add_argument("--herding", action="store_true")
+    ap.add_argument("--clips", type=int, default=96)
+    ap.add_argument("--keep", type=int, default=10)
     a = ap.parse_args()
     if a.nlq:
         return nlq(a)
+    if a.herding:
+        return herding(a)
     from vilco_amd import _lib
     from vilco_amd.utils import metrics as M
     rng = np.random.default_rng(0)
@@ -187,6 +198,63 @@ def nlq(a):
         res["restatement_cpu_ms"] = round((time.perf_counter() - t0) * 1e3, 1)
         assert np.array_equal(R.recall(flags) * 100, tab_s)
     print(json.dumps(res))
+
+
+HBM_PEAK = 8.0e12          # bytes / s, MI355X
+
+
+def herding(a):
+    from vilco_amd import ops
+    dev = torch.device("cuda:0")
+    N, m, C_ = a.clips, a.keep, 1024
+    dims = [t * C_ for t in (2304, 1152, 576, 288, 144, 72)]
+    g = torch.Generator(device=dev).manual_seed(0)
+    base = [torch.randn(d, device=dev, generator=g) for d in dims]
+    bufs = [b[None, :] + 0.6 * torch.randn(N, d, device=dev, generator=g) for b, d in zip(base, dims)]
+
+    def timed(fn, iters):
+        fn()
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(iters):
+            out = fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / iters, out
+
+    t_frob, invs = timed(lambda: [ops.frob_scale(b) for b in bufs], a.iters)
+    t_gram, grams = timed(lambda: torch.stack([ops.gram(b, i, torch.float64) for b, i in zip(bufs, invs)]), a.iters)
+    t_gram0, _ = timed(lambda: ops.gram(bufs[0], invs[0], torch.float64), a.iters)
+    t_sel, sel = timed(lambda: ops.herd_select(grams, m), a.iters)
+
+    def literal():
+        phis = [b * i[:, None] for b, i in zip(bufs, invs)]
+        mus = [p.mean(0) for p in phis]
+        mus = [u / u.norm() for u in mus]
+        S = [torch.zeros_like(u) for u in mus]
+        taken = torch.zeros(N, dtype=torch.bool, device=dev)
+        out = []
+        for _ in range(min(m, N)):
+            cost = torch.zeros(N, device=dev)
+            for p, u, s_ in zip(phis, mus, S):
+                v = p + s_[None, :]
+                v = v / v.norm(dim=1, keepdim=True)
+                cost = cost + (u[None, :] - v).pow(2).sum(1)
+            k = torch.argmin(cost.masked_fill(taken, float("inf")))
+            taken[k] = True
+            S = [s_ + p[k] for s_, p in zip(S, phis)]
+            out.append(k)
+        return torch.stack(out)
+    t_lit, sel_lit = timed(literal, 2)
+    x0 = 4.0 * N * dims[0]
+    print(json.dumps({"clips": N, "keep": m, "levels": len(dims), "floats_per_clip": sum(dims),
+                      "frob_scale_ms": round(t_frob, 3), "gram_all_levels_ms": round(t_gram, 3),
+                      "gram_level0_ms": round(t_gram0, 3), "gram_level0_bytes_x": int(x0),
+                      "gram_level0_fraction_of_hbm_peak": round(x0 / (t_gram0 * 1e-3) / HBM_PEAK, 3),
+                      "herd_select_ms": round(t_sel, 3), "herding_device_ms": round(t_frob + t_gram + t_sel, 3),
+                      "literal_torch_loop_ms": round(t_lit, 1), "same_selection": sel.tolist() == sel_lit.tolist(),
+                      "selection": sel.tolist()}))
 
 
 def gt_vids(ev):

@@ -1061,10 +1061,71 @@ class PtTransformer(nn.Module):
     def add_samples_to_mem(self, cilsettask, data, m):
         """random replay-memory sampling: merge the episode's {class: videos} into the memory, shuffle
         each class in place and keep m per class ('ALL' keeps everything) (meta_archs.py:1046-1052)."""
+        if self.type_sampling == 'herding':
+            return self._herd_samples_to_mem(cilsettask, data, m)
         import random
         self.memory = {**self.memory, **data}
         for class_id, videos in self.memory.items():
             random.shuffle(videos)
             self.memory[class_id] = videos[:m] if m != 'ALL' else videos
+        for class_id, videos in self.memory.items():
+            print('Memory... Class: {}, num videos: {}'.format(class_id, len(videos)))
+
+    @torch.no_grad()
+    def herding_order(self, cilsettask, class_id, videos, m):
+        """iCaRL's herding over the candidates of one class -> (clips in loader order, device int32 [min(m, N)] of the
+        selected positions, in selection order).  The descriptor of a clip is what `classify` averages: every level map
+        of `_pyramid_features` (eval mode) divided by its Frobenius norm.  Greedy step: the clip whose addition brings the
+        normalised sum of the selected descriptors closest to the normalised class mean, summed over the levels; ties go
+        to the earlier clip.  The reference's own branch (meta_archs.py:973-1043) is commented out and unfinished; the
+        definition is spelled out in include/vilco_hip.h and DESIGN.md 3.10.
+        The level maps go into one preallocated [N, T_l * C] buffer per level; vilco_frob_scale, vilco_gram (the row scale
+        folded into the product) and vilco_herd_select do the rest, the indices stay on the device."""
+        batches = list(cilsettask.get_dataloader({class_id: videos}, sample_frame=True))
+        for b in batches:
+            if len(b) != 1:
+                raise ValueError("herding needs one-clip batches, got a batch of %d for class %r" % (len(b), class_id))
+        N = len(batches)
+        dev = next(self.parameters()).device
+        if N == 0:
+            return [], torch.empty(0, dtype=torch.int32, device=dev)
+        was_training = self.training
+        self.eval()
+        try:
+            bufs, shapes = None, None
+            for i, vl in enumerate(batches):
+                f = self._pyramid_features(vl)
+                if bufs is None:
+                    shapes = [tuple(t.shape) for t in f]
+                    need = 4 * N * sum(t.numel() for t in f)
+                    free = torch.cuda.mem_get_info(dev)[0] + torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)
+                    if need > free:
+                        raise RuntimeError("herding class %r: the descriptors of its %d clips need %d bytes, %d bytes of "
+                                           "device memory are free" % (class_id, N, need, free))
+                    bufs = [torch.empty(N, t.numel(), dtype=torch.float32, device=dev) for t in f]
+                elif [tuple(t.shape) for t in f] != shapes:
+                    raise ValueError("herding class %r: clip %r has level shapes %s, the class's first clip %s"
+                                     % (class_id, vl[0].get('video_id', i), [tuple(t.shape) for t in f], shapes))
+                for buf, t in zip(bufs, f):
+                    buf[i].copy_(t.reshape(-1))
+        finally:
+            self.train(was_training)
+        grams = torch.stack([ops.gram(buf, ops.frob_scale(buf), torch.float64) for buf in bufs], dim=0)
+        return [b[0] for b in batches], ops.herd_select(grams, N if m == 'ALL' else m)
+
+    def _herd_samples_to_mem(self, cilsettask, data, m):
+        """type_sampling 'herding' (beyond the reference, which samples at random whatever the setting): every class of
+        `data` becomes its clips in herding order, a priority list, so a class already in memory shrinks by videos[:m]
+        without reshuffling (what meta_archs.py:1043 intended).  m == 'ALL' keeps every clip, still in herding order."""
+        if cilsettask is None:
+            raise ValueError("type_sampling 'herding' needs the task stream (get_dataloader) to compute the descriptors")
+        memory = {**self.memory, **data}
+        for class_id, videos in memory.items():
+            if class_id in data:
+                clips, sel = self.herding_order(cilsettask, class_id, videos, m)
+                memory[class_id] = [clips[i] for i in sel.tolist()]
+            else:
+                memory[class_id] = videos[:m] if m != 'ALL' else videos
+        self.memory = memory
         for class_id, videos in self.memory.items():
             print('Memory... Class: {}, num videos: {}'.format(class_id, len(videos)))

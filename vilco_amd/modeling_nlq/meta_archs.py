@@ -165,6 +165,11 @@ class PtTransformer(mq.PtTransformer):
             video_list = self._with_labels(video_list)
         return super().prepare(video_list, is_training, gt_pad)
 
+    def add_samples_to_mem(self, cilsettask, data, m):
+        if self.type_sampling == 'herding':       # the pyramid descriptor path is only held to a contract on the MQ model
+            raise NotImplementedError("type_sampling 'herding' is implemented for the MQ model only")
+        return super().add_samples_to_mem(cilsettask, data, m)
+
     def forward(self, video_list, task_id=-1, ensemble=False, hidden_state=False, is_training=True,
                 prev_out_cls_logits=None, get_emb=False, val_qilDatasetList=None):
         if self.training and not get_emb:

@@ -1981,6 +1981,57 @@ def decode(logits, offsets, points, level_row0, level_len, topk, pre_nms_thresh,
     return segs[:n], scores[:n], labels[:n]
 
 
+# ---------------------------------------------------------------------------------------- herding exemplar selection
+def frob_scale(x):
+    """vilco_frob_scale: 1 / ||row||_2 of every row of fp32 x [N, D] -> [N] fp32."""
+    _chk(x)
+    lib = _lib.load()
+    N, D = x.shape
+    inv = torch.empty(N, dtype=torch.float32, device=x.device)
+    nws = lib.vilco_frob_scale_workspace(N, D)
+    ws = _ws(nws, x.device)
+    _lib.check(lib.vilco_frob_scale(x.data_ptr(), N, D, D, inv.data_ptr(), ws.data_ptr(), nws, _stream()))
+    return inv
+
+
+def gram(x, row_scale=None, out_dtype=torch.float32):
+    """vilco_gram: G = diag(row_scale) x x^T diag(row_scale) for fp32 x [N, D] -> [N, N] fp32 or fp64 (exact fp32
+    products, fp32 accumulation per K slab, slabs added in fp64 in a fixed order; exactly symmetric)."""
+    _chk(x, row_scale)
+    if out_dtype not in (torch.float32, torch.float64):
+        raise RuntimeError("gram writes fp32 or fp64, not %s" % out_dtype)
+    lib = _lib.load()
+    N, D = x.shape
+    if row_scale is not None and tuple(row_scale.shape) != (N,):
+        raise RuntimeError("row_scale must have one entry per row")
+    g = torch.empty(N, N, dtype=out_dtype, device=x.device)
+    nws = lib.vilco_gram_workspace(N, D)
+    ws = _ws(nws, x.device)
+    _lib.check(lib.vilco_gram(x.data_ptr(), N, D, D, _p(row_scale), g.data_ptr(), int(out_dtype == torch.float64),
+                              ws.data_ptr(), nws, _stream()))
+    return g
+
+
+def herd_select(grams, m):
+    """vilco_herd_select: the greedy herding order of one class from its per-level Gram matrices.  grams: [L, N, N] (a
+    tensor or a list of L [N, N] tensors; fp32 is widened), m: how many to pick -> int32 [min(m, N)] on the device."""
+    if not torch.is_tensor(grams):
+        grams = torch.stack([g.to(torch.float64) for g in grams], dim=0)
+    if not grams.is_cuda:
+        raise RuntimeError("vilco_amd ops run on the HIP device only (got a %s tensor); there is no CPU fallback" % grams.device)
+    if grams.dim() != 3 or grams.shape[1] != grams.shape[2]:
+        raise RuntimeError("grams must be [L, N, N]")
+    grams = grams.to(torch.float64).contiguous()
+    lib = _lib.load()
+    L, N = int(grams.shape[0]), int(grams.shape[1])
+    m = max(int(m), 0)
+    sel = torch.empty(min(m, N), dtype=torch.int32, device=grams.device)
+    nws = lib.vilco_herd_select_workspace(1, L, N)
+    ws = _ws(nws, grams.device)
+    _lib.check(lib.vilco_herd_select(grams.data_ptr(), 1, L, N, m, sel.data_ptr(), ws.data_ptr(), nws, _stream()))
+    return sel
+
+
 # ---------------------------------------------------------------------------------------- fused ln1 -> q/k/v pre-projection
 def qkv_pre_supported(Cn):
     return bool(_lib.load().vilco_qkv_pre_supported(int(Cn)))

@@ -134,7 +134,7 @@ def run_episodes(cfg, model, train_stream, validate=None, ckpt_folder=None, gpu_
         # replay memory for the next task (train_cl.py:343-361)
         n_cls = model.cls_head.cls_head.conv.out_channels
         if memory_size != 0:
-            model.add_samples_to_mem(None, data, memory_quota(memory_size, n_cls))
+            model.add_samples_to_mem(train_stream, data, memory_quota(memory_size, n_cls))
         train_stream.memory = model.memory
         model.n_known = len(model.memory)
         if ckpt_folder is not None:

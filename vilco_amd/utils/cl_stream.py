@@ -10,6 +10,7 @@ what the episode loop consumes is only this contract, which `InMemoryQILStream` 
                        by video 'id' dropped, 'is_memory' set on every dict               (:80-85, ego4d.py:453-458)
     num_next_classes = #classes of the following task, None after the last                 (:91-95)
   stream.memory is assigned by the driver after every task (train_cl.py:355);  stream.num_tasks.
+  stream.get_dataloader(data, batch_size=1, memory=None, sample_frame=False) -> batches over the given classes (:128-139)
 
 `DistributedBatchLoader` is the sampler side of torchrun + DistributedSampler (datasets.py:24): every rank walks a
 disjoint, equally long shard of the same seeded permutation, re-drawn by `sampler.set_epoch`.
@@ -98,3 +99,12 @@ class InMemoryQILStream:
 
     def set_memory(self, memory):
         self.memory = memory
+
+    def get_dataloader(self, data, batch_size=1, memory=None, sample_frame=False):
+        """a loader over {class_id: videos} outside the task sequence (cl_benchmark.py:128-139): 'is_memory' is set to
+        `sample_frame` on the clips of `data` and to True on those of `memory`, which come first; batches of `batch_size`
+        in dataset order.  `classify` and the herding selection walk it as one-clip batches."""
+        comp = self._tag(data, bool(sample_frame))
+        if memory is not None:
+            comp = {**self._tag(memory, True), **comp}
+        return DistributedBatchLoader(self.flatten(comp), batch_size, shuffle=False, drop_last=False)
