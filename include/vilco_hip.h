@@ -36,10 +36,6 @@ enum vilco_status {
 const char* vilco_status_str(int status);
 /* library / target identification: "vilco_hip <ver> gfx950" */
 const char* vilco_version(void);
-/* With VILCO_GRID_SYNC=1 in the environment two-stage reductions (column sums, amax -> pack) finish inside one      */
-/* launch through a grid-wide barrier whose spin is bounded; this returns how many barriers gave up since the library */
-/* was loaded (0 in a healthy process).  Synchronises the device.  Default: the two-launch forms (measured faster).   */
-int vilco_sync_timeouts_read(void);
 
 /* ------------------------------------------------------------------------------------------ */
 /* GEMM family: every 1x1 conv, k=3 conv, nn.Linear, einsum projection and (round 1) the        */
@@ -139,18 +135,6 @@ int vilco_gemm_group(const vilco_gemm_desc* descs, int32_t n, void* stream);
 /* Tuning override: force the tile height (128 | 192 | 256; 0 = cost model) and split-K count (0 = heuristic) of every
  * following vilco_gemm in this process.  Initial values: environment VILCO_GEMM_BM / VILCO_GEMM_KS, read once. */
 int vilco_gemm_force(int32_t bm, int32_t ks);
-/* Split-K finish of every following vilco_gemm: 1 = inside the launch (the last-arriving split workgroup of a tile sums
- * the partial accumulators in split order and runs the epilogue), 0 = fp32 slabs + a reduce launch (default: measured
- * faster, gemm.hip).  Same summation order either way.  Initial value: environment VILCO_GEMM_FIXUP=1 enables. */
-int vilco_gemm_set_fixup(int32_t on);
-/* Main kernel of the fp16 x2 products (precision 3 / 4) of every following vilco_gemm: 1 = gemm_gl_kernel (round 5: 64-element
- * K chunks staged by LDS-DMA in whole 128-byte lines; default), 0 = gemm_pp_kernel (rounds 1-4: 32-element K-steps staged through
- * registers).  Initial value: environment VILCO_GEMM_GL=0 selects the old kernel. */
-int vilco_gemm_set_gl(int32_t on);
-/* Round 5: a two-part product of 257..512 192-row tiles (between one and two rounds on the 256 CUs) is launched as ONE full round */
-/* of 192-row tiles over its first rows + one round of 128-row tiles over the rest (same arithmetic per tile, disjoint rows).   */
-/* 0 (default: measured, no gain in the step) / 1; env VILCO_GEMM_TAIL128.                                                     */
-int vilco_gemm_set_tail128(int32_t on);
 /* Round 6: few-row NT products of the default precision (M <= 640 token rows: the pyramid levels at T' <= 288, the 77 text tokens, every
  * level of BASELINE configs[0]; reference: the nn.Linear / 1x1 MaskedConv1D calls of blocks.py:191-269 at those levels) run as ONE
  * launch of gemm_skinny_kernel (the eight waves of a workgroup split K, fragments straight from the operand planes, partial tiles
@@ -158,7 +142,7 @@ int vilco_gemm_set_tail128(int32_t on);
  * VILCO_GEMM_SKINNY_M = the largest M that takes it (640).  Same arithmetic per product (two fp16 parts, three MFMAs, fp32
  * accumulation); the summation order over K differs from the tiled kernels'. */
 int vilco_gemm_set_skinny(int32_t on);
-/* Generation of the process-wide GEMM configuration: bumped by vilco_gemm_force / _set_fixup / _set_gl / _set_tail128 / _set_skinny.  The host
+/* Generation of the process-wide GEMM configuration: bumped by vilco_gemm_force / vilco_gemm_set_skinny.  The host
  * side keys captured hipGraphs on it (a replay runs the plan that was recorded, not the current configuration). */
 int64_t vilco_gemm_config_gen(void);
 /* floats written to desc->amax_out by vilco_gemm(desc) (depends on the tile / split-K plan); 0: not available */

@@ -1,6 +1,5 @@
 """Round 6: the single-part weight-gradient shapes of a P step (TN: A = dY [K tok][M Cout], B = X [K tok][N Cin], precision 4) under
-forced tile heights / split counts, on the kernel this process selects (VILCO_GEMM_GL_SINGLE=1: gemm_gl_kernel<.., SINGLE>; default:
-gemm_pp_kernel K2).  Operands packed once; 20 calls per point; kernel + split-K finish."""
+forced tile heights / split counts (gemm_pp_kernel, K2).  Operands packed once; 20 calls per point; kernel + split-K finish."""
 import os, sys
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', '..'))
 import torch
@@ -12,7 +11,7 @@ shapes = [(1024, 3072, 9082), (1024, 1024, 4608), (1024, 4096, 4608), (4096, 102
           (1024, 1024, 2304), (1024, 1024, 9216)]
 if len(sys.argv) > 1:
     shapes = shapes[:int(sys.argv[1])]
-tag = "gl-single" if os.environ.get("VILCO_GEMM_GL_SINGLE") == "1" else "pp-K2"
+tag = "pp-K2"
 for M, N, K in shapes:
     A = torch.randn(K, M, device=dev); B = torch.randn(K, N, device=dev)
     C = torch.empty(M, N, device=dev)

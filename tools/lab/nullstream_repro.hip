@@ -13,7 +13,7 @@
 // launch stream, an in-place "collective" on a SECOND stream behind an event (5: that stream blocking, 6: NON-BLOCKING, as torch's and
 // RCCL's streams are), graph 2 launched on the launch stream while the collective runs, then the wait for the collective, the copy
 // back into the gradient's own memory and the check;
-// 7 / 8 / 9 what the torch-level bisect left (tools/lab/dp_staged_dbg2.py with VILCO_DP_DEBUG_NO_COLLECTIVE=2 fails on the null stream
+// 7 / 8 / 9 what the torch-level bisect left (tools/lab/dp_staged_dbg2.py with the collective replaced by torch streams and events alone fails on the null stream
 // WITHOUT any RCCL call): as 6 but NOTHING runs on the second stream -- it only waits for the launch stream's event and records the end
 // event the launch stream then waits for; the second stream is high-priority non-blocking (torch's pool); 8: the two events are created
 // and destroyed every iteration, as torch.cuda.Event objects are; 9: as 7 with the end event queried from a second host thread while

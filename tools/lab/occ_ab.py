@@ -1,6 +1,5 @@
 """Kernel-only time (operands packed once) of the step's many-tile GEMM shapes under forced tile heights, for one library
-build (VILCO_HIP_LIB selects it).  Used for the two-workgroups-per-CU experiment: a -DVILCO_GEMM_WPE=4 build holds the 128-row
-kernel at <= 128 VGPRs, so two of its 64 KB workgroups share a CU."""
+build (VILCO_HIP_LIB selects it): compares two builds of the library on one box."""
 import os, sys
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', '..'))
 import torch

@@ -1,5 +1,5 @@
 """cfg1 (BASELINE configs[0]: the P graph at T = 256, every node tiny) replayed under whatever HIP runtime knobs the environment
-sets: ms per step = the per-node floor of a replayed step.  tools/lab/r6_rtflags.sh runs it per setting."""
+sets: ms per step = the per-node floor of a replayed step.  Run it once per setting."""
 import os, sys
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", ".."))
 import torch

@@ -1,5 +1,5 @@
 """Same-box A/B of a bench.py side configuration (cfg1 / W) under environment toggles given as arguments:
-python tools/lab/side_ab.py cfg1 VILCO_GEMM_GL=0 VILCO_GEMM_GL=1 ...   (each toggle runs in a child process, interleaved twice)"""
+python tools/lab/side_ab.py cfg1 VILCO_GEMM_SKINNY=0 VILCO_GEMM_SKINNY=1 ...   (each toggle runs in a child process, interleaved twice)"""
 import os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 name, toggles = sys.argv[1], sys.argv[2:]

@@ -67,7 +67,6 @@ class PackItem(C.Structure):
 SIGNATURES = {
     "vilco_status_str": (C.c_char_p, [C.c_int]),
     "vilco_version": (C.c_char_p, []),
-    "vilco_sync_timeouts_read": (C.c_int, []),
     "vilco_defer_set": (C.c_int, [i32]),
     "vilco_defer_pending": (i64, []),
     "vilco_defer_flush": (C.c_int, [c_fp]),
@@ -76,9 +75,6 @@ SIGNATURES = {
     "vilco_gemm_group": (C.c_int, [C.POINTER(GemmDesc), i32, c_fp]),
     "vilco_gemm_amax_parts": (i32, [C.POINTER(GemmDesc)]),
     "vilco_gemm_force": (C.c_int, [i32, i32]),
-    "vilco_gemm_set_fixup": (C.c_int, [i32]),
-    "vilco_gemm_set_gl": (C.c_int, [i32]),
-    "vilco_gemm_set_tail128": (C.c_int, [i32]),
     "vilco_gemm_set_skinny": (C.c_int, [i32]),
     "vilco_gemm_config_gen": (i64, []),
     "vilco_gemm_profile_begin": (C.c_int, []),

@@ -24,7 +24,6 @@
 // P^T / dS^T are packed stores: dV^T = dO^T P, dK^T = Q^T dS).  No atomics: results are bitwise reproducible.
 #include <type_traits>
 #include "common.h"
-#define VILCO_TU "attn"
 #include "pack.h"
 
 typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
@@ -1157,8 +1156,6 @@ __global__ __launch_bounds__(ATT_THREADS) void attn_bwd_dq_kernel(AttnArgs a) {
 // mask, probability dropout) plus the dS store the position-term gradients are derived from (a.dbias, [B,H,Tq,Tk])
 // delta_i = dO_i . O_i of query qi, head h (64 channels), as the four lanes {l, l^16, l^32, l^48} of the fast-path kernels
 // compute it: lane group g4 sums channels ks*32 + 8 g4 .. +7, the groups are combined as (g0 + g1) + (g2 + g3).
-// ONE function for attn_bwd_dq64_kernel and attn_delta64_kernel: both must produce the same bits (a captured step may take
-// delta from the latter, the eager step from the former; tests/test_graph_gpu.py compares them bit for bit).
 __device__ __forceinline__ float delta64(const AttnArgs& a, int b, int h, int qi, int g4) {
   float delta_i = 0.f;
   if (qi < a.Tq) {
@@ -1174,16 +1171,6 @@ __device__ __forceinline__ float delta64(const AttnArgs& a, int b, int h, int qi
       }
   }
   return quad16_sum(delta_i);
-}
-
-// delta alone (16 queries per wave, the lane layout of the kernels above): lets attn_bwd_dkdv64 start without waiting for
-// attn_bwd_dq64 when the two run on different streams (launch_bwd: fork)
-__global__ __launch_bounds__(256) void attn_delta64_kernel(AttnArgs a) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int h = blockIdx.y, b = blockIdx.z;
-  const int qi = blockIdx.x * 64 + wave * 16 + (lane & 15);
-  const float d = delta64(a, b, h, qi, lane >> 4);
-  if ((lane >> 4) == 0 && qi < a.Tq) a.delta[(long)(b * a.H + h) * a.Tq + qi] = d;
 }
 
 template <bool XL>
@@ -2030,29 +2017,6 @@ int launch_fwd(const AttnArgs& a, hipStream_t s) {
   return vilco_launch_status();
 }
 
-struct ForkCtx { hipStream_t s2; hipEvent_t e0, e1; };
-
-// the side stream + events of the dQ || dK-dV fork, or null: VILCO_ATTN_FORK != 1 (the default: same-box A/B of the replayed P
-// step, round 4: 25.16 / 25.23 ms without, 25.27 / 25.12 ms with -- no gain), or `s` is not capturing.  The stream and the
-// events are created by the first call that finds `s` NOT capturing (resource creation inside a capture is not safe in every
-// capture mode); a process's first backward is always eager (graph.py captures after eager_steps >= 1 iterations).
-inline ForkCtx* attn_fork(hipStream_t s) {
-  static const bool enabled = [] { const char* e = getenv("VILCO_ATTN_FORK"); return e && e[0] == '1'; }();      // off by default
-  if (!enabled) return nullptr;
-  hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(s, &st) != hipSuccess) return nullptr;
-  static ForkCtx ctx;
-  static int state = 0;                 // 0: not created, 1: ready, -1: creation failed
-  if (st != hipStreamCaptureStatusActive) {
-    if (state == 0)
-      state = (hipStreamCreateWithFlags(&ctx.s2, hipStreamNonBlocking) == hipSuccess &&
-               hipEventCreateWithFlags(&ctx.e0, hipEventDisableTiming) == hipSuccess &&
-               hipEventCreateWithFlags(&ctx.e1, hipEventDisableTiming) == hipSuccess) ? 1 : -1;
-    return nullptr;
-  }
-  return state == 1 ? &ctx : nullptr;
-}
-
 template <int HDP, int NP, bool F16 = false>
 int launch_bwd(const AttnArgs& a, hipStream_t s) {
   static const bool once = [] {
@@ -2067,7 +2031,6 @@ int launch_bwd(const AttnArgs& a, hipStream_t s) {
   (void)once;
   dim3 gq((a.Tq + 63) / 64, a.H, a.B), gk((a.Tk + 63) / 64, a.H, a.B);
   const size_t lq = dq_lds<HDP, NP>(), lk = dkdv_lds<HDP, NP>();
-  (void)attn_fork(s);                   // (creates the fork resources on the first eager call)
   bool fast = false;
   if constexpr (HDP == 64 && NP == 2 && F16)
     fast = fast64(a, 3);
@@ -2075,21 +2038,6 @@ int launch_bwd(const AttnArgs& a, hipStream_t s) {
     if constexpr (HDP == 64 && NP == 2 && F16) {
       constexpr size_t l64 = 2 * 2 * PL64 * sizeof(__bf16);
       const dim3 gq64((a.Tq + F64_Q - 1) / F64_Q, a.H, a.B);
-      // dQ and dK/dV are independent once delta exists.  At the long levels neither grid fills the chip in whole rounds
-      // (T = 2304, B H = 32: 576 and 1152 workgroups on 512 resident slots -> 2 and 3 rounds for 1.125 and 2.25 rounds of
-      // work); on two streams the runtime packs them together.  Only inside a stream capture (a replayed graph has no host
-      // in the loop; an eager second queue made step times erratic, DESIGN_LOG.md 3.6) and only where there is a tail to fill.
-      ForkCtx* f = (long)gq64.x * gq64.y * gq64.z > 512 ? attn_fork(s) : nullptr;
-      if (f) {
-        hipLaunchKernelGGL(attn_delta64_kernel, dim3((a.Tq + 63) / 64, a.H, a.B), dim3(256), 0, s, a);
-        hipEventRecord(f->e0, s);
-        hipStreamWaitEvent(f->s2, f->e0, 0);
-        hipLaunchKernelGGL(attn_bwd_dq64_kernel<false>, gq64, dim3(ATT_THREADS), l64, s, a);      // (writes the same delta again)
-        hipLaunchKernelGGL(attn_bwd_dkdv64_kernel<false>, gk, dim3(ATT_THREADS), l64, f->s2, a);
-        hipEventRecord(f->e1, f->s2);
-        hipStreamWaitEvent(s, f->e1, 0);
-        return vilco_launch_status();
-      }
       hipLaunchKernelGGL(attn_bwd_dq64_kernel<false>, gq64, dim3(ATT_THREADS), l64, s, a);
       hipLaunchKernelGGL(attn_bwd_dkdv64_kernel<false>, gk, dim3(ATT_THREADS), l64, s, a);
       return vilco_launch_status();
@@ -2218,38 +2166,15 @@ void use_external_amax(ScaleWs& sw, const vilco_attn_amax_in* in, int nops) {
     if (p[i] && n[i] > 0) { sw.parts[i] = const_cast<float*>(p[i]); sw.n[i] = n[i]; sw.ext[i] = true; }
 }
 
-// all queued packs of one attention call: [amax +] natural packs in one launch, transposing packs in another
+// all queued packs of one attention call: the amax pass, natural packs in one launch, transposing packs in another
 void flush_packs(PackQueue& pq, ScaleWs& sw, bool f16, int NP, int nbatch, hipStream_t s) {
   if (f16) {
-    PackArgs fa[4];
-    AmaxOp fm[4];
-    int nf = 0;
-    bool covered[4] = {false, false, false, false};
-    for (int i = 0; i < pq.n; ++i)
-      for (int j = 0; j < sw.nops; ++j)
-        if (pq.a.a[i].amax == sw.parts[j]) { fa[nf] = pq.a.a[i]; fm[nf] = sw.am.op[j]; covered[j] = true; ++nf; break; }
-    bool ok = nf == pq.n;
-    for (int j = 0; j < sw.nops && ok; ++j) {
-      if (covered[j]) continue;
-      if (nf == 4) { ok = false; break; }
-      PackArgs d = {};                          // amax only: a pack of zero rows that still leaves {1/s, s}
-      d.Kp = 8; d.nbi = 1; d.tapC = 1; d.tapT = 1; d.out_rows = 0;
-      d.amax = sw.parts[j]; d.inv_scale = sw.out + 2 * j;
-      fa[nf] = d; fm[nf] = sw.am.op[j]; ++nf;
-    }
-    for (int j = 0; j < sw.nops; ++j) ok = ok && !sw.ext[j];
-    if (ok && dispatch_pack_fused(NP, fa, fm, nf, nbatch, s, VILCO_SITE_ATTNPACK)) {
-      for (int i = 0; i < pq.nt; ++i) pq.t.a[i].namax = fa[0].namax;      // every operand got gx * nbatch partials
-    } else {
-      AmaxArgs am;
-      int nam = 0;
-      for (int j = 0; j < sw.nops; ++j) if (!sw.ext[j]) am.op[nam++] = sw.am.op[j];
-      if (nam) launch_amax(am, nam, s);
-      if (pq.n) dispatch_pack_multi(NP, pq.a, pq.n, s, nbatch);
-    }
-  } else if (pq.n) {
-    dispatch_pack_multi(NP, pq.a, pq.n, s, nbatch);
+    AmaxArgs am;
+    int nam = 0;
+    for (int j = 0; j < sw.nops; ++j) if (!sw.ext[j]) am.op[nam++] = sw.am.op[j];
+    if (nam) launch_amax(am, nam, s);
   }
+  if (pq.n) dispatch_pack_multi(NP, pq.a, pq.n, s, nbatch);
   if (pq.nt) dispatch_pack_tr_multi(NP, pq.t, pq.nt, s, nbatch);
 }
 

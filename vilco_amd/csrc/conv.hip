@@ -86,8 +86,7 @@ __global__ __launch_bounds__(EW_THREADS) void dwconv3_bwd_dx_kernel(
 // partial dw: block handles a slab of output rows; thread = 4 channels; ws[block][C*3]
 __global__ __launch_bounds__(EW_THREADS) void dwconv3_bwd_dw_kernel(
     const float* __restrict__ dy, const float* __restrict__ x, const int* __restrict__ in_len,
-    float* __restrict__ ws, int B, int Tin, int Tout, int C, int stride, int rows_per_block, float* __restrict__ dw,
-    unsigned* sync) {
+    float* __restrict__ ws, int B, int Tin, int Tout, int C, int stride, int rows_per_block) {
   const int C4 = C >> 2;
   const long r0 = (long)blockIdx.x * rows_per_block;
   long r1 = r0 + rows_per_block;
@@ -114,9 +113,8 @@ __global__ __launch_bounds__(EW_THREADS) void dwconv3_bwd_dw_kernel(
     }
     float* o = ws + (long)blockIdx.x * C * 3 + c * 3;
 #pragma unroll
-    for (int k = 0; k < 12; ++k) vilco_st_agent(o + k, acc[k]);      // crosses the in-launch barrier: write-through
+    for (int k = 0; k < 12; ++k) vilco_st_agent(o + k, acc[k]);
   }
-  if (sync) vilco_finish_colsum(ws, dw, nullptr, (int)gridDim.x, C * 3, C * 3, sync, blockIdx.x, gridDim.x);
 }
 
 __device__ __forceinline__ float4 max4(float4 a, float4 b) {
@@ -231,10 +229,9 @@ extern "C" int vilco_dwconv3_bwd(const float* dy, const float* x, const float* w
     const int nb = dw_blocks(rows);
     const int rpb = (int)((rows + nb - 1) / nb);
     float* ws = reinterpret_cast<float*>(workspace);
-    unsigned* sync = vilco_sync_counter(s, VILCO_SITE_DWCONV);          // nb <= 512 blocks: co-resident
     hipLaunchKernelGGL(dwconv3_bwd_dw_kernel, dim3(nb), dim3(EW_THREADS), 0, s, dy, x, in_len, ws, B, Tin,
-                       Tout, C, stride, rpb, dw, sync);
-    if (!sync) vilco_reduce_rows(ws, dw, nullptr, nb, C * 3, C * 3, s);
+                       Tout, C, stride, rpb);
+    vilco_reduce_rows(ws, dw, nullptr, nb, C * 3, C * 3, s);
   }
   return vilco_launch_status();
 }

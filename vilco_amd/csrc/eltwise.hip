@@ -129,7 +129,7 @@ __global__ __launch_bounds__(EW_THREADS) void scale_add_bwd_kernel(
     const float* __restrict__ dout, const float* __restrict__ bval, const float* __restrict__ colscale,
     const float* __restrict__ rowscale, const int* __restrict__ len, int mask_a, float* __restrict__ da,
     float* __restrict__ db, float* __restrict__ ws, int B, int T, int C, int rows_per_block,
-    float* __restrict__ dcolscale, unsigned* sync, float* __restrict__ db_amax) {
+    float* __restrict__ db_amax) {
   __shared__ float amax_red[EW_THREADS / 64];
   float amax = 0.f;          // max |db| of this block: db is the upstream gradient of the branch's last layer (see act_bwd_kernel<true>)
   const long R = (long)B * T;
@@ -172,8 +172,6 @@ __global__ __launch_bounds__(EW_THREADS) void scale_add_bwd_kernel(
     if (threadIdx.x == 0)
       db_amax[blockIdx.y * gridDim.x + blockIdx.x] = fmaxf(fmaxf(amax_red[0], amax_red[1]), fmaxf(amax_red[2], amax_red[3]));
   }
-  if (sync) vilco_finish_colsum(ws, dcolscale, nullptr, (int)gridDim.x, C, C, sync, blockIdx.y * gridDim.x + blockIdx.x,
-                                gridDim.x * gridDim.y);
 }
 
 __global__ __launch_bounds__(EW_THREADS) void axpby_kernel(float* __restrict__ out,
@@ -241,8 +239,8 @@ template <bool PLANES>
 __global__ __launch_bounds__(EW_THREADS) void act_bwd_kernel(
     const float* __restrict__ dy, const float* __restrict__ aux, float* __restrict__ dz,
     float* __restrict__ ws, int act, const int* __restrict__ len, int T, long rows, int C,
-    int rows_per_block, uint32_t drop_thresh, uint32_t drop_seed, float drop_inv_keep, float* __restrict__ dbias,
-    unsigned* sync, float* __restrict__ amax_parts, const uint32_t* __restrict__ seed_word, PlaneOut po,
+    int rows_per_block, uint32_t drop_thresh, uint32_t drop_seed, float drop_inv_keep,
+    float* __restrict__ amax_parts, const uint32_t* __restrict__ seed_word, PlaneOut po,
     const float* __restrict__ row_mask) {
   if (drop_thresh) drop_seed = vilco_step_seed(drop_seed, seed_word);
   __shared__ float amax_red[EW_THREADS / 64];
@@ -301,8 +299,6 @@ __global__ __launch_bounds__(EW_THREADS) void act_bwd_kernel(
     if (threadIdx.x == 0)
       amax_parts[blockIdx.y * gridDim.x + blockIdx.x] = fmaxf(fmaxf(amax_red[0], amax_red[1]), fmaxf(amax_red[2], amax_red[3]));
   }
-  if (sync) vilco_finish_colsum(ws, dbias, nullptr, (int)gridDim.x, C, C, sync, blockIdx.y * gridDim.x + blockIdx.x,
-                                gridDim.x * gridDim.y);
 }
 
 // The same op, four columns per lane (C % 4 == 0, 16-byte aligned rows): a wave covers 256 columns of one row with one
@@ -313,8 +309,8 @@ template <bool PLANES>
 __global__ __launch_bounds__(EW_THREADS) void act_bwd_vec_kernel(
     const float* __restrict__ dy, const float* __restrict__ aux, float* __restrict__ dz,
     float* __restrict__ ws, int act, const int* __restrict__ len, int T, long rows, int C,
-    int rows_per_block, uint32_t drop_thresh, uint32_t drop_seed, float drop_inv_keep, float* __restrict__ dbias,
-    unsigned* sync, float* __restrict__ amax_parts, const uint32_t* __restrict__ seed_word, PlaneOut po,
+    int rows_per_block, uint32_t drop_thresh, uint32_t drop_seed, float drop_inv_keep,
+    float* __restrict__ amax_parts, const uint32_t* __restrict__ seed_word, PlaneOut po,
     const float* __restrict__ row_mask) {
   typedef _Float16 h4 __attribute__((ext_vector_type(4)));
   if (drop_thresh) drop_seed = vilco_step_seed(drop_seed, seed_word);
@@ -402,14 +398,11 @@ __global__ __launch_bounds__(EW_THREADS) void act_bwd_vec_kernel(
     if (threadIdx.x == 0)
       amax_parts[blockIdx.y * gridDim.x + blockIdx.x] = fmaxf(fmaxf(amax_red[0], amax_red[1]), fmaxf(amax_red[2], amax_red[3]));
   }
-  if (sync) vilco_finish_colsum(ws, dbias, nullptr, (int)gridDim.x, C, C, sync, blockIdx.y * gridDim.x + blockIdx.x,
-                                gridDim.x * gridDim.y);
 }
 
 __global__ __launch_bounds__(EW_THREADS) void colsum_partial_kernel(const float* __restrict__ x,
                                                                     float* __restrict__ ws, long rows,
-                                                                    int C, int rows_per_block, float* __restrict__ out,
-                                                                    unsigned* sync) {
+                                                                    int C, int rows_per_block) {
   const long r0 = (long)blockIdx.x * rows_per_block;
   long r1 = r0 + rows_per_block;
   if (r1 > rows) r1 = rows;
@@ -427,8 +420,6 @@ __global__ __launch_bounds__(EW_THREADS) void colsum_partial_kernel(const float*
     for (; r < r1; ++r) acc += x[r * C + c];
     vilco_st_agent(ws + (long)blockIdx.x * C + c, acc);
   }
-  if (sync) vilco_finish_colsum(ws, out, nullptr, (int)gridDim.x, C, C, sync, blockIdx.y * gridDim.x + blockIdx.x,
-                                gridDim.x * gridDim.y);
 }
 
 __global__ __launch_bounds__(EW_THREADS) void mask_rows_kernel(float* __restrict__ x,
@@ -497,11 +488,12 @@ int col_blocks(long rows) {
 }
 
 // row blocks of the 2-D (row chunk, 256-column group) reductions: as col_blocks, but never more than
-// VILCO_SYNC_MAX_BLOCKS blocks in total, so that the in-launch finish (grid barrier) is safe
-int col_blocks_sync(long rows, int C) {
+// COLSUM_MAX_BLOCKS blocks in total (the block count is the number of partial sums, and so the summation order)
+constexpr int COLSUM_MAX_BLOCKS = 1024;
+int col_blocks_2d(long rows, int C) {
   const int gy = (C + EW_THREADS - 1) / EW_THREADS;
   int nb = col_blocks(rows);
-  if ((long)nb * gy > VILCO_SYNC_MAX_BLOCKS) nb = VILCO_SYNC_MAX_BLOCKS / gy;
+  if ((long)nb * gy > COLSUM_MAX_BLOCKS) nb = COLSUM_MAX_BLOCKS / gy;
   return nb < 1 ? 1 : nb;
 }
 
@@ -591,15 +583,14 @@ extern "C" int vilco_scale_add_bwd_amax(const float* dout, const float* bval, co
   if (rows == 0) return VILCO_OK;
   if (dcolscale && (!workspace || workspace_bytes < vilco_colsum_workspace(rows, C))) return VILCO_ERR_WORKSPACE;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const int nb = col_blocks_sync(rows, C);
+  const int nb = col_blocks_2d(rows, C);
   const int rpb = (int)((rows + nb - 1) / nb);
   float* ws = dcolscale ? reinterpret_cast<float*>(workspace) : nullptr;
-  unsigned* sync = (dcolscale && C <= 256 * VILCO_SYNC_MAX_BLOCKS) ? vilco_sync_counter(s, VILCO_SITE_COLSUM) : nullptr;
   const bool emit = db && db_amax_parts && n_parts;
   if (emit) *n_parts = nb * ((C + EW_THREADS - 1) / EW_THREADS);
   hipLaunchKernelGGL(scale_add_bwd_kernel, dim3(nb, (C + EW_THREADS - 1) / EW_THREADS), dim3(EW_THREADS), 0, s, dout, bval, colscale, rowscale,
-                     len, mask_a, da, db, ws, B, T, C, rpb, dcolscale, sync, emit ? db_amax_parts : nullptr);
-  if (dcolscale && !sync) vilco_reduce_rows(ws, dcolscale, nullptr, nb, C, C, s);
+                     len, mask_a, da, db, ws, B, T, C, rpb, emit ? db_amax_parts : nullptr);
+  if (dcolscale) vilco_reduce_rows(ws, dcolscale, nullptr, nb, C, C, s);
   return vilco_launch_status();
 }
 
@@ -722,10 +713,9 @@ extern "C" int vilco_act_bwd_planes_seq(const float* dy, const float* aux, float
   if (rows == 0) return VILCO_OK;
   if (dbias && (!workspace || workspace_bytes < vilco_colsum_workspace(rows, C))) return VILCO_ERR_WORKSPACE;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const int nb = col_blocks_sync(rows, C);
+  const int nb = col_blocks_2d(rows, C);
   const int rpb = (int)((rows + nb - 1) / nb);
   float* ws = dbias ? reinterpret_cast<float*>(workspace) : nullptr;
-  unsigned* sync = (dbias && C <= 256 * VILCO_SYNC_MAX_BLOCKS) ? vilco_sync_counter(s, VILCO_SITE_COLSUM) : nullptr;
   const bool emit = amax_parts && n_parts;
   if (emit) *n_parts = nb * ((C + EW_THREADS - 1) / EW_THREADS);
   static const bool vec_on = [] { const char* e = getenv("VILCO_ACT_BWD_VEC"); return !(e && e[0] == '0'); }();
@@ -733,12 +723,12 @@ extern "C" int vilco_act_bwd_planes_seq(const float* dy, const float* aux, float
   const dim3 grid(nb, (C + EW_THREADS - 1) / EW_THREADS);
 #define ACT_BWD_LAUNCH(K)                                                                                                        \
   hipLaunchKernelGGL(K, grid, dim3(EW_THREADS), 0, s, dy, aux, dz, ws, act, len, T, (long)rows, C, rpb,                          \
-                     vilco_drop_threshold_host(drop_p), drop_seed, 1.f / (1.f - drop_p), dbias, sync,                            \
+                     vilco_drop_threshold_host(drop_p), drop_seed, 1.f / (1.f - drop_p),                                         \
                      emit ? amax_parts : nullptr, vilco_seed_word_dev(), po, row_mask)
   if (planes) { if (vec) ACT_BWD_LAUNCH(act_bwd_vec_kernel<true>); else ACT_BWD_LAUNCH(act_bwd_kernel<true>); }
   else { if (vec) ACT_BWD_LAUNCH(act_bwd_vec_kernel<false>); else ACT_BWD_LAUNCH(act_bwd_kernel<false>); }
 #undef ACT_BWD_LAUNCH
-  if (dbias && !sync) vilco_reduce_rows(ws, dbias, nullptr, nb, C, C, s);
+  if (dbias) vilco_reduce_rows(ws, dbias, nullptr, nb, C, C, s);
   return vilco_launch_status();
 }
 
@@ -748,13 +738,11 @@ extern "C" int vilco_colsum(const float* x, float* out, int64_t rows, int32_t C,
   if (!workspace || workspace_bytes < vilco_colsum_workspace(rows, C)) return VILCO_ERR_WORKSPACE;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   if (rows == 0) return hipMemsetAsync(out, 0, sizeof(float) * C, s) == hipSuccess ? VILCO_OK : VILCO_ERR_LAUNCH;
-  const int nb = col_blocks_sync(rows, C);
+  const int nb = col_blocks_2d(rows, C);
   const int rpb = (int)((rows + nb - 1) / nb);
   float* ws = reinterpret_cast<float*>(workspace);
-  unsigned* sync = C <= 256 * VILCO_SYNC_MAX_BLOCKS ? vilco_sync_counter(s, VILCO_SITE_COLSUM) : nullptr;
-  hipLaunchKernelGGL(colsum_partial_kernel, dim3(nb, (C + EW_THREADS - 1) / EW_THREADS), dim3(EW_THREADS), 0, s, x, ws, (long)rows, C, rpb,
-                     out, sync);
-  if (!sync) vilco_reduce_rows(ws, out, nullptr, nb, C, C, s);
+  hipLaunchKernelGGL(colsum_partial_kernel, dim3(nb, (C + EW_THREADS - 1) / EW_THREADS), dim3(EW_THREADS), 0, s, x, ws, (long)rows, C, rpb);
+  vilco_reduce_rows(ws, out, nullptr, nb, C, C, s);
   return vilco_launch_status();
 }
 

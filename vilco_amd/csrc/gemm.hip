@@ -17,12 +17,9 @@
 // 3 = two fp16 parts of the per-tensor scaled operands ("f16x2": 22 bits, 3 MFMAs; pack.h; the default).
 // Reference arithmetic replaced: see include/vilco_hip.h (vilco_gemm).
 #include <cstdlib>
-#include <mutex>
 #include <utility>
 #include <vector>
-#include <type_traits>
 #include "common.h"
-#define VILCO_TU "gemm"
 #include "pack.h"
 
 namespace {
@@ -72,10 +69,8 @@ struct GArgs {
   int batch_inner;
   long sCo, sCi;
   int tiles_n, ntiles;
-  int tm0;                // first row tile of this launch (a product launched as two row ranges of different tile heights)
   int ksplit, kchunk;   // kchunk = K-steps per split
   long split_stride;    // elements between split slabs
-  unsigned* tile_ctr;   // split-K fix-up: arrival counter per (batch, tile); null = partial slabs + splitk_reduce_kernel
   const float* inv_a;       // fp16 x2 format: {1/s, s} of each operand, left by the pack kernels
   const float* inv_b;
   int vec_out;              // N, ldc, batch strides multiples of 4 and every epilogue pointer 16-byte aligned
@@ -114,11 +109,7 @@ __device__ __forceinline__ float store_out4(const GArgs& g, long idx, int n, con
   const Epi& e = g.e;
   f32x4 v = acc * e.alpha;
   if (e.bias) v += *reinterpret_cast<const f32x4*>(e.bias + n);
-#ifndef VILCO_GEMM_NO_NT_C
   if (e.preact) __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(e.preact + idx));      // (read again only in backward)
-#else
-  if (e.preact) *reinterpret_cast<f32x4*>(e.preact + idx) = v;
-#endif
   if (e.act == VILCO_ACT_RELU) {
 #pragma unroll
     for (int k = 0; k < 4; ++k) v[k] = fmaxf(v[k], 0.f);
@@ -139,12 +130,7 @@ __device__ __forceinline__ float store_out4(const GArgs& g, long idx, int n, con
   // Round 6: C leaves as STREAMING (nontemporal) stores.  The output of a launch is 9-75 MB written once by the whole grid and read
   // next by another kernel through the memory-side cache; keeping it out of the L2 write path measured -0.1 ... -0.15 ms on the
   // replayed P step (five same-box alternations, profiles/r06_ab_nt_c.txt: 20.51 -> 20.37 ms; GEMM family 12.07 -> 11.85 ms).
-  // -DVILCO_GEMM_NO_NT_C: ordinary stores.
-#ifndef VILCO_GEMM_NO_NT_C
   __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(g.cfinal + idx));
-#else
-  *reinterpret_cast<f32x4*>(g.cfinal + idx) = v;
-#endif
   return fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3])));
 }
 
@@ -205,31 +191,11 @@ __device__ __forceinline__ bf16x8 tr_frag(const __bf16* p, int rs4) {     // row
   return __builtin_bit_cast(bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
 }
 
-// Split-K fix-up inside the launch.  Every split workgroup stores its accumulators -- in their REGISTER layout, one
-// 16-byte piece per lane and 16 x 16 block, 1 KB per wave instruction -- to its slot of the workspace with `sc1`
-// (write-through) stores, waits for them, and one lane bumps the tile's arrival counter (agent-scope atomic).  The
-// workgroup whose add came last (it learns so from the value the add returned) loads the other splits' pieces with
-// `sc1` loads, sums them IN SPLIT ORDER (its own piece from registers: the result does not depend on who was last, and
-// equals what splitk_reduce_kernel computes, bit for bit), resets the counter and runs the ordinary epilogue.  This is
-// the hand-off row "one lane of each storing workgroup adds to ONE counter / the workgroup whose add came last" of
-// MI355X_MICROARCH.md (stores and loads all sc1, 16 bytes).  No second launch, no fp32 slab in the output's layout.
-__device__ __forceinline__ void st_sc1(f32x4* p, const f32x4& v) {
-  asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(p), "v"(v) : "memory");
-}
-__device__ __forceinline__ void ld_sc1(f32x4& v, const f32x4* p) {
-  asm volatile("global_load_dwordx4 %0, %1, off sc1" : "=v"(v) : "v"(p) : "memory");
-}
-// the loads above are invisible to the compiler's vmcnt bookkeeping: wait here, and tie the four registers to the wait
-__device__ __forceinline__ void wait_sc1(f32x4& a, f32x4& b, f32x4& c, f32x4& d) {
-  asm volatile("s_waitcnt vmcnt(0)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d)::"memory");
-}
-
-
 // ---- epilogue shared by the MFMA kernels: accumulators of the 4 x 2 wave layout (wave tile 16 MI x 64) -> C through LDS.
 // Each wave transposes its 16 x 64 accumulator blocks so that a lane owns 4 consecutive columns of one row and the
 // stores / residual loads are 16 bytes per lane, 256 contiguous bytes per row, instead of 4-byte scatters (measured
 // before: 24k of a 112k-cycle block at K = 1024).  The pipeline buffers must be dead when this is called.
-template <int MI, bool F16, bool FIXUP>
+template <int MI, bool F16>
 __device__ __forceinline__ void gemm_epilogue(const GArgs& g, f32x4 (&acc)[MI][4], unsigned char* smem_raw, int tid, int lane,
                                               int wave, int wm, int wn, int m0, int n0, int bid, int ks, int zo, int zi,
                                               int zidx) {          // zidx: batch index of this workgroup (0 in a grouped launch)
@@ -246,50 +212,7 @@ __device__ __forceinline__ void gemm_epilogue(const GArgs& g, f32x4 (&acc)[MI][4
   // the stores / residual loads are 16 bytes per lane, 256 contiguous bytes per row, instead of 4-byte scatters
   // (measured before: 24k of a 112k-cycle block at K = 1024).
   const long coff = zo * g.sCo + zi * g.sCi;
-  if constexpr (FIXUP) if (g.ksplit > 1 && g.tile_ctr) {
-    __shared__ unsigned arrived;
-    constexpr long PIECES = MI * 4 * 64;                        // f32x4 pieces per wave
-    const long tile = (long)zidx * g.ntiles + bid;
-    f32x4* mine = reinterpret_cast<f32x4*>(g.c) + ((tile * g.ksplit + ks) * 8 + wave) * PIECES + lane;
-#pragma unroll
-    for (int i = 0; i < MI; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) st_sc1(mine + (i * 4 + j) * 64, acc[i][j]);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");            // every storing wave, before the barrier the signal is behind
-    __syncthreads();
-    if (tid == 0) arrived = __hip_atomic_fetch_add(g.tile_ctr + tile, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __syncthreads();
-    if (arrived != (unsigned)(g.ksplit - 1)) return;
-    if (tid == 0) __hip_atomic_store(g.tile_ctr + tile, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // next launch
-    const f32x4* all = reinterpret_cast<const f32x4*>(g.c) + (tile * g.ksplit * 8 + wave) * PIECES + lane;
-    const long sstride = 8 * PIECES;
-    // every piece of one other split is requested before the first is used (one memory round trip per split, not per
-    // piece); two splits are in flight at a time.  The running sums start from split 0 and take the splits in order.
-    constexpr int NPC = MI * 4;
-    f32x4 sum[NPC];
-#pragma unroll
-    for (int q = 0; q < NPC; ++q) sum[q] = f32x4{0.f, 0.f, 0.f, 0.f};
-    for (int s0 = 0; s0 < g.ksplit; s0 += 2) {
-      f32x4 va[NPC], vb[NPC];
-      const bool ha = s0 != ks, hb = s0 + 1 < g.ksplit && s0 + 1 != ks;
-#pragma unroll
-      for (int q = 0; q < NPC; ++q) {
-        va[q] = sum[q]; vb[q] = sum[q];
-        if (ha) ld_sc1(va[q], all + (long)s0 * sstride + q * 64);
-        if (hb) ld_sc1(vb[q], all + (long)(s0 + 1) * sstride + q * 64);
-      }
-#pragma unroll
-      for (int q = 0; q < NPC; q += 2) wait_sc1(va[q], va[q + 1], vb[q], vb[q + 1]);
-#pragma unroll
-      for (int q = 0; q < NPC; ++q) {
-        sum[q] += ha ? va[q] : acc[q / 4][q % 4];
-        if (s0 + 1 < g.ksplit) sum[q] += hb ? vb[q] : acc[q / 4][q % 4];
-      }
-    }
-#pragma unroll
-    for (int q = 0; q < NPC; ++q) acc[q / 4][q % 4] = sum[q];
-  }
-  const bool partial = g.ksplit > 1 && !g.tile_ctr;
+  const bool partial = g.ksplit > 1;
   float* cp = g.c + (partial ? (long)ks * g.split_stride : 0);
   // (round 5) ALL of the wave's blocks are staged first, then ONE rolled loop finishes them: the unrolled form was ~10 k
   // instructions per kernel, more than the instruction cache keeps -- every launch re-fetched its set-up and epilogue code
@@ -303,7 +226,7 @@ __device__ __forceinline__ void gemm_epilogue(const GArgs& g, f32x4 (&acc)[MI][4
     for (int j = 0; j < 4; ++j)
 #pragma unroll
       for (int rr = 0; rr < 4; ++rr) stg[(i * 16 + (lane >> 4) * 4 + rr) * EPI_LD + j * 16 + (lane & 15)] = acc[i][j][rr];
-  // (Round 6, in-kernel stamps of one workgroup, tools/lab/r6_epi.sh: this loop takes 11 k cycles plain, 13 k with a bias, 24 k with
+  // (Round 6, in-kernel stamps of one workgroup, tools/lab/gl_stamps.py with EPI=...: this loop takes 11 k cycles plain, 13 k with a bias, 24 k with
   // GELU + pre-activation and 28 k with bias + residual, against 65 k for the K loop of a 4608 x 1024 x 1024 tile.  It is the
   // chip's write path, not a latency chain: the 192 workgroups of a single-round launch finish together and put 18.9 MB of C --
   // plus 18.9 MB of residual reads / pre-activation writes -- through the fabric at once, 4-5 TB/s.  Requesting a row's residual
@@ -316,11 +239,8 @@ __device__ __forceinline__ void gemm_epilogue(const GArgs& g, f32x4 (&acc)[MI][4
     if (m >= g.M || n >= g.N) continue;
     const long idx = coff + (long)m * g.ldc + n;
     if (partial) {
-#ifndef VILCO_GEMM_NO_NT_C      // (split-K slabs stream out too: the deferred sums read them at the end of backward; R6.11)
+      // (split-K slabs stream out too: the deferred sums read them at the end of backward; R6.11)
       if (g.vec_out) __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(cp + idx));
-#else
-      if (g.vec_out) *reinterpret_cast<f32x4*>(cp + idx) = v;
-#endif
       else
 #pragma unroll
         for (int e = 0; e < 4; ++e) if (n + e < g.N) cp[idx + e] = v[e];
@@ -343,7 +263,7 @@ __device__ __forceinline__ void gemm_epilogue(const GArgs& g, f32x4 (&acc)[MI][4
       float m = red[0];
 #pragma unroll
       for (int w = 1; w < 8; ++w) m = fmaxf(m, red[w]);
-      g.amax_out[(long)zidx * gridDim.x + blockIdx.x] = m;     // (split-K fix-up: one last arriver per tile)
+      g.amax_out[(long)zidx * gridDim.x + blockIdx.x] = m;
     }
   }
 }
@@ -354,11 +274,7 @@ __device__ __forceinline__ void gemm_epilogue(const GArgs& g, f32x4 (&acc)[MI][4
 // part and 32 elements per interval the loop was bound by its MEM phase (16 MFMAs per wave against ~1000 cycles of
 // reads, stores and loads: ~2000 cycles per 32 k, MFMA pipe 25 % busy); the interval's fixed cost now buys twice the K.
 template <int BM, int NP, bool F16, bool AKM, bool BKM, bool K2 = false>
-#ifdef VILCO_GEMM_WPE            // (lab: 4 holds every instantiation at <= 128 VGPRs, tools/lab/occ_ab.py)
-__global__ __launch_bounds__(512, VILCO_GEMM_WPE) void gemm_pp_kernel(GArgs g) {
-#else
 __global__ __launch_bounds__(512) void gemm_pp_kernel(GArgs g) {
-#endif
   static_assert(!K2 || (NP == 2 && F16), "K2: two slots, fp16 parts");
   constexpr int NT = 512;
   constexpr int MI = BM / 64;                    // 16-row A fragments per wave (wave tile = 16*MI x 64)
@@ -496,38 +412,6 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(GArgs g) {
   const int kt0b = kb;
   const int nk = kt1 - kt0b;
 
-#ifndef VILCO_GEMM_DEPTH2
-#define VILCO_GEMM_DEPTH2 1
-#endif
-  // D2: staging loads issued TWO K-steps ahead into a second register set (tiles alternate between the sets); every load
-  // is unconditional (the K offset is clamped to the last tile) so that the compiler's vmcnt model sees no join between a
-  // load and its use and leaves exactly the younger tile's loads in flight at the wait.
-  constexpr bool D2 = VILCO_GEMM_DEPTH2 && !K2 && BM <= 192 && NP == 2 && F16;
-  bf16x8 stA2[D2 ? NP : 1][D2 ? RA : 1], stB2[D2 ? NP : 1][D2 ? RB : 1];
-  auto gload2 = [&](int kt, auto& sa_, auto& sb_) {
-    if (kt > kt1 - 1) kt = kt1 - 1;
-#pragma unroll
-    for (int q = 0; q < NP; ++q) {
-      const int sa = (int)(2 * (long)kt * stepA), sb = (int)(2 * (long)kt * stepB);
-#pragma unroll
-      for (int r = 0; r < RA; ++r)
-        sa_[q][r] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rsA[q], (int)voffA[r], sa, 0));
-#pragma unroll
-      for (int r = 0; r < RB; ++r)
-        sb_[q][r] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rsB[q], (int)voffB[r], sb, 0));
-    }
-  };
-  auto lstore2 = [&](int st, const auto& sa_, const auto& sb_) {
-    __bf16* s = smem + st * NP * TILE;
-#pragma unroll
-    for (int q = 0; q < NP; ++q) {
-#pragma unroll
-      for (int r = 0; r < RA; ++r)
-        if (r + 1 < RA || tailA) *reinterpret_cast<bf16x8*>(s + q * TILE + ldsA[r]) = sa_[q][r];
-#pragma unroll
-      for (int r = 0; r < RB; ++r) *reinterpret_cast<bf16x8*>(s + q * TILE + ldsB[r]) = sb_[q][r];
-    }
-  };
   bf16x8 stA[NP][RA], stB[NP][RB];
   auto gload = [&](int kt) {
 #pragma unroll
@@ -556,16 +440,7 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(GArgs g) {
     }
   };
 
-  if constexpr (D2) {
-    if (nk > 0) {                          // tile 0 -> LDS; tiles 1 (set "stA2") and 2 (set "stA") in flight
-      gload2(kt0b, stA, stB);
-      lstore2(0, stA, stB);
-      gload2(kt0b + 1, stA2, stB2);
-      __builtin_amdgcn_sched_barrier(0);   // the two tiles' loads stay in tile order (the loop's vmcnt waits count on it)
-      gload2(kt0b + 2, stA, stB);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-  } else if (nk > 0) {
+  if (nk > 0) {
     gload(kt0b);
     lstore(0);
     if (nk > 1) gload(kt0b + 1);
@@ -573,17 +448,9 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(GArgs g) {
   __syncthreads();
   STAMPX(1);
 
-// Loop variants (lab builds: -DVILCO_GEMM_VARIANT=n, tools/lab/gemm_variants.sh).  3 (default since r03): a wave's
-// fragment reads of tile t are issued FIRST in its MEM phase, so their latency runs under the staging stores and the global
-// loads of the same phase, and the MFMA phase starts on the compiler's counted lgkmcnt waits instead of a full drain:
+// A wave's fragment reads of tile t are issued FIRST in its MEM phase, so their latency runs under the staging stores and the
+// global loads of the same phase, and the MFMA phase starts on the compiler's counted lgkmcnt waits instead of a full drain:
 // +3...6 % on every shape of the step (same box: 4608x1024x1024 41.1 -> 38.8 us, 9216x1024x1024 81.3 -> 76.8 us).
-// 0 = r02's order (stores, loads, reads, s_waitcnt lgkmcnt(0)); 1 = 0 without the drain; 2 = reads first with the drain.
-#ifndef VILCO_GEMM_VARIANT
-#define VILCO_GEMM_VARIANT 3
-#endif
-#ifndef VILCO_GEMM_PRIO      // 1: MFMA phase at priority 1 (default); 0: no s_setprio; 2: MEM phase above the MFMA phase
-#define VILCO_GEMM_PRIO 1
-#endif
   bf16x8 fa[NP][MI], fb[NP][4];
   auto frag_reads = [&](int t) {
     const __bf16* s = smem + (t & 1) * NP * TILE;
@@ -598,10 +465,8 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(GArgs g) {
     }
   };
   auto mem_phase = [&](int t) {          // stage tile t+1, re-issue tile t+2, fetch this wave's fragments of tile t
-#if VILCO_GEMM_VARIANT == 2 || VILCO_GEMM_VARIANT == 3
-    frag_reads(t);                       // (lab) fragment reads first: their latency runs under the staging traffic
+    frag_reads(t);                       // fragment reads first: their latency runs under the staging traffic
     __builtin_amdgcn_sched_barrier(0);
-#endif
     if (t + 1 < nk) lstore((t + 1) & 1);
 #ifdef VILCO_LAB_FINE
     STAMP(1);
@@ -610,16 +475,9 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(GArgs g) {
 #ifdef VILCO_LAB_FINE
     STAMP(2);
 #endif
-#if !(VILCO_GEMM_VARIANT == 2 || VILCO_GEMM_VARIANT == 3)
-    frag_reads(t);
-#endif
   };
   auto mfma_phase = [&]() {
-#if VILCO_GEMM_PRIO == 1
     __builtin_amdgcn_s_setprio(1);
-#elif VILCO_GEMM_PRIO == 2
-    __builtin_amdgcn_s_setprio(0);
-#endif
 #pragma unroll
     for (int i = 0; i < MI; ++i)
 #pragma unroll
@@ -648,77 +506,13 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(GArgs g) {
           acc[i][j] = mma<F16>(fa[2][i], fb[0][j], acc[i][j]);
         }
     }
-#if VILCO_GEMM_PRIO == 1
     __builtin_amdgcn_s_setprio(0);
-#elif VILCO_GEMM_PRIO == 2
-    __builtin_amdgcn_s_setprio(2);       // (lab) the MEM phase that follows outranks the partner's MFMA stream
-#endif
   };
 
-  // D2 MEM phase of K-step t (odd tiles live in stA2 / stB2, even ones in stA / stB): tile t+1 -> LDS from its set, then
-  // that set takes tile t+3.  Past the end the last tile is loaded / stored again: its LDS stage is never read.
-  auto mem_phase2 = [&](int t, auto odd_) {
-    const bool odd = decltype(odd_)::value;
-    frag_reads(t);
-    __builtin_amdgcn_sched_barrier(0);
-    if (odd) { lstore2((t + 1) & 1, stA, stB); gload2(kt0b + t + 3, stA, stB); }
-    else { lstore2((t + 1) & 1, stA2, stB2); gload2(kt0b + t + 3, stA2, stB2); }
-  };
-  if constexpr (D2) {
-    // pairs of K-steps with NO conditional inside the loop body (a skipped second half would reach the loop header with
-    // the two register sets' loads in the opposite age order, and the compiler's vmcnt model would drain both); an odd
-    // last K-step runs after the loop
-    int t = 0;
-    if (!late) {
-      for (; t + 1 < nk; t += 2) {
-        mem_phase2(t, std::false_type{});
-        __builtin_amdgcn_sched_barrier(0);
-        mfma_phase();
-        __builtin_amdgcn_sched_barrier(0);
-        __syncthreads();
-        mem_phase2(t + 1, std::true_type{});
-        __builtin_amdgcn_sched_barrier(0);
-        mfma_phase();
-        __builtin_amdgcn_sched_barrier(0);
-        __syncthreads();
-      }
-      if (t < nk) {
-        mem_phase2(t, std::false_type{});
-        __builtin_amdgcn_sched_barrier(0);
-        mfma_phase();
-        __builtin_amdgcn_sched_barrier(0);
-        __syncthreads();
-      }
-    } else {
-      for (; t + 1 < nk; t += 2) {
-        if (t > 0) mfma_phase();
-        __builtin_amdgcn_sched_barrier(0);
-        mem_phase2(t, std::false_type{});
-        __builtin_amdgcn_sched_barrier(0);
-        __syncthreads();
-        mfma_phase();
-        __builtin_amdgcn_sched_barrier(0);
-        mem_phase2(t + 1, std::true_type{});
-        __builtin_amdgcn_sched_barrier(0);
-        __syncthreads();
-      }
-      if (t < nk) {
-        if (t > 0) mfma_phase();
-        __builtin_amdgcn_sched_barrier(0);
-        mem_phase2(t, std::false_type{});
-        __builtin_amdgcn_sched_barrier(0);
-        __syncthreads();
-      }
-      if (nk > 0) mfma_phase();
-    }
-  } else
   if (!late) {
     for (int t = 0; t < nk; ++t) {
       STAMP(0);
       mem_phase(t);
-#if VILCO_GEMM_VARIANT == 0 || VILCO_GEMM_VARIANT == 2
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#endif
       __builtin_amdgcn_sched_barrier(0);
       STAMP(3);
       mfma_phase();
@@ -734,9 +528,6 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(GArgs g) {
       __builtin_amdgcn_sched_barrier(0);
       STAMP(3);
       mem_phase(t);
-#if VILCO_GEMM_VARIANT == 0 || VILCO_GEMM_VARIANT == 2
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#endif
       __builtin_amdgcn_sched_barrier(0);
       STAMP(5);
       __syncthreads();
@@ -746,14 +537,13 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(GArgs g) {
   }
   STAMPX(2);
 
-  gemm_epilogue<MI, F16, true>(g, acc, smem_raw, tid, lane, wave, wm, wn, m0, n0, bid, ks, zo, zi, (int)blockIdx.z);
+  gemm_epilogue<MI, F16>(g, acc, smem_raw, tid, lane, wave, wm, wn, m0, n0, bid, ks, zo, zi, (int)blockIdx.z);
   STAMPX(3);
 }
 
 
 // ------------------------------------------------------------------------------------------ LDS-DMA kernel (round 5)
-// gemm_gl_kernel: the fp16 x2 products (precision 3: two parts, three MFMAs per fragment pair; SINGLE = precision 4: the
-// leading parts only) with the staging rebuilt around what round 5's load-path probe measured (tools/lab/ldpath.hip, one
+// gemm_gl_kernel: the fp16 x2 products (precision 3: two parts, three MFMAs per fragment pair) with the staging rebuilt around what round 5's load-path probe measured (tools/lab/ldpath.hip, one
 // workgroup per CU streaming an L2-resident operand): 1-KiB load instructions made of 64-byte row segments -- the BK = 32
 // K-steps of gemm_pp_kernel -- move 29 B / clk / CU, whole 128-byte lines 50 (to registers) to 58 (LDS-DMA).  A 192 x 128
 // tile needs 40 KB per 32 k: 1400 cycles of the ~2400 a K-step took were the address path alone.  Here:
@@ -775,17 +565,16 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(GArgs g) {
 //     rows of the upper half and all of B), the late waves the A rows only they read, one phase later.  Each group waits for
 //     its own DMAs (vmcnt(0)) just before the barrier that precedes their first reader ("read a staged buffer one phase after
 //     the wait that retires it", cdna_hip_programming.md 5).
-// SINGLE keeps the two slots and fills them with part 0 of two consecutive 64-element chunks (128 k per interval).
 // (Measured and removed, round 5: an L2 prefetch of every wave's own operand lines three chunks ahead -- one 4-byte load per
 // 128-byte line, never waited for -- against the 25 % the step's cold launches lose to back-to-back ones: the replayed P step
 // went 22.5 -> 23.4 ms, GEMM time 12.66 -> 13.7 ms.  The cold share is not load latency.  DESIGN_LOG.md R5.)
-template <int BM, bool AKM, bool BKM, bool SINGLE>
+template <int BM, bool AKM, bool BKM>
 __device__ __forceinline__ void gemm_gl_body(const GArgs& g, const int z) {
   constexpr int MI = BM / 64;
   constexpr int A_BYTES = BM * 128, B_BYTES = BN * 128;       // one slot of one operand
   constexpr int SLOT = A_BYTES + B_BYTES, STAGE = 2 * SLOT;
   constexpr int KSLOT = 64;                                   // k per slot
-  constexpr int KINT = SINGLE ? 128 : 64;                     // k per barrier interval
+  constexpr int KINT = 64;                                    // k per barrier interval
   // pieces (1 KiB = 8 panel rows): A has BM / 8, B has 16.  The early group takes the A pieces its own waves read.
   constexpr int NA0 = AKM ? 8 * ((BM / 2 + 63) / 64) : BM / 16;
   constexpr int NA1 = BM / 8 - NA0;
@@ -809,7 +598,7 @@ __device__ __forceinline__ void gemm_gl_body(const GArgs& g, const int z) {
     const int nwg = g.ntiles, q = nwg >> 3, r = nwg & 7, x = bid & 7;
     bid = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (bid >> 3);
   }
-  const int tm = bid / g.tiles_n + g.tm0, tn = bid % g.tiles_n;
+  const int tm = bid / g.tiles_n, tn = bid % g.tiles_n;
   const int m0 = tm * BM, n0 = tn * BN;
   const int zo = z / g.batch_inner, zi = z % g.batch_inner;
   const int ks = blockIdx.y;
@@ -822,8 +611,8 @@ __device__ __forceinline__ void gemm_gl_body(const GArgs& g, const int z) {
     const unsigned nb = g.b.bytes > 0xffffffffL ? 0xffffffffu : (unsigned)g.b.bytes;
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
-      rsA[q] = __builtin_amdgcn_make_buffer_rsrc(const_cast<__bf16*>(pa + (SINGLE ? 0 : q * g.a.plane_stride)), 0, na, 0x00020000);
-      rsB[q] = __builtin_amdgcn_make_buffer_rsrc(const_cast<__bf16*>(pb + (SINGLE ? 0 : q * g.b.plane_stride)), 0, nb, 0x00020000);
+      rsA[q] = __builtin_amdgcn_make_buffer_rsrc(const_cast<__bf16*>(pa + q * g.a.plane_stride), 0, na, 0x00020000);
+      rsB[q] = __builtin_amdgcn_make_buffer_rsrc(const_cast<__bf16*>(pb + q * g.b.plane_stride), 0, nb, 0x00020000);
     }
   }
   STAMPX(5);
@@ -921,8 +710,7 @@ __device__ __forceinline__ void gemm_gl_body(const GArgs& g, const int z) {
     unsigned char* sbase = smem_raw + st * STAGE;
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
-      const int kc64 = SINGLE ? 2 * ci + u : ci;              // which 64-k chunk goes into slot u
-      const int sa = kc64 * kstepA, sb = kc64 * kstepB;
+      const int sa = ci * kstepA, sb = ci * kstepB;
       if (!late) {
 #pragma unroll
         for (int j = 0; j < NP0; ++j)
@@ -956,29 +744,25 @@ __device__ __forceinline__ void gemm_gl_body(const GArgs& g, const int z) {
         }
       }
   };
-  // nsub: valid k32 sub-steps of this interval (sub-step s = slot u, half h: SINGLE s = 2 u + h; two parts: s = h)
+  // nsub: valid k32 sub-steps of this interval (sub-step = half h of both slots)
   auto mfmas = [&](int nsub) {
     __builtin_amdgcn_s_setprio(1);
 #pragma unroll
-    for (int u = 0; u < (SINGLE ? 2 : 1); ++u)
+    for (int h = 0; h < 2; ++h) {
+      if (h < nsub) {
 #pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        if ((SINGLE ? 2 * u + h : h) < nsub) {
+        for (int i = 0; i < MI; ++i)
 #pragma unroll
-          for (int i = 0; i < MI; ++i)
+          for (int j = 0; j < 4; ++j) acc[i][j] = mma<true>(fa[0][h][i], fb[0][h][j], acc[i][j]);
 #pragma unroll
-            for (int j = 0; j < 4; ++j) acc[i][j] = mma<true>(fa[u][h][i], fb[u][h][j], acc[i][j]);
-          if constexpr (!SINGLE) {
+        for (int i = 0; i < MI; ++i)
 #pragma unroll
-            for (int i = 0; i < MI; ++i)
-#pragma unroll
-              for (int j = 0; j < 4; ++j) {
-                acc[i][j] = mma<true>(fa[0][h][i], fb[1][h][j], acc[i][j]);
-                acc[i][j] = mma<true>(fa[1][h][i], fb[0][h][j], acc[i][j]);
-              }
+          for (int j = 0; j < 4; ++j) {
+            acc[i][j] = mma<true>(fa[0][h][i], fb[1][h][j], acc[i][j]);
+            acc[i][j] = mma<true>(fa[1][h][i], fb[0][h][j], acc[i][j]);
           }
-        }
       }
+    }
     __builtin_amdgcn_s_setprio(0);
   };
 #define GL_BARRIER()                                  \
@@ -1047,13 +831,13 @@ __device__ __forceinline__ void gemm_gl_body(const GArgs& g, const int z) {
 #undef GL_WAIT_DMA
 #undef GL_WAIT_LDS
   STAMPX(2);
-  gemm_epilogue<MI, true, false>(g, acc, smem_raw, tid, lane, wave, wm, wn, m0, n0, bid, ks, zo, zi, z);
+  gemm_epilogue<MI, true>(g, acc, smem_raw, tid, lane, wave, wm, wn, m0, n0, bid, ks, zo, zi, z);
   STAMPX(3);
 }
 
-template <int BM, bool AKM, bool BKM, bool SINGLE>
+template <int BM, bool AKM, bool BKM>
 __global__ __launch_bounds__(512) void gemm_gl_kernel(GArgs g) {
-  gemm_gl_body<BM, AKM, BKM, SINGLE>(g, (int)blockIdx.z);
+  gemm_gl_body<BM, AKM, BKM>(g, (int)blockIdx.z);
 }
 
 // Grouped launch (round 5): up to four INDEPENDENT products of one shape -- the q / k / v projections of an attention block,
@@ -1062,7 +846,7 @@ __global__ __launch_bounds__(512) void gemm_gl_kernel(GArgs g) {
 struct GArgsN { GArgs g[4]; };
 template <int BM, bool AKM, bool BKM>
 __global__ __launch_bounds__(512) void gemm_gl_group_kernel(GArgsN gg) {
-  gemm_gl_body<BM, AKM, BKM, false>(gg.g[blockIdx.z], 0);
+  gemm_gl_body<BM, AKM, BKM>(gg.g[blockIdx.z], 0);
 }
 
 
@@ -1279,20 +1063,10 @@ struct Plan {
   long split_stride;
   bool tapkm;                     // k=3 conv weight gradient as a k-major x k-major product over zero-padded token rows (make_plan)
   bool k2;                        // precision 4: a barrier interval of the kernel covers two K-steps (64 elements of K)
-  bool fixup;                     // split-K finished inside the launch (tile counters) instead of by splitk_reduce_kernel
   bool gl;                        // gemm_gl_kernel (LDS-DMA staging, 64-element chunks): the fp16 x2 products
   bool skinny;                    // gemm_skinny_kernel (few rows, NT, precision 3): BM = its rows per workgroup (16 | 32)
 };
 
-// Arrival counters of the split-K fix-up: persistent, zero at load, reset by each tile's last arriver.  One region per
-// stream (launches of one stream are ordered; different streams may run GEMMs at the same time).
-constexpr int FIX_TILES = 4096, FIX_STREAMS = 32;
-__device__ unsigned vilco_tile_counters[FIX_STREAMS * FIX_TILES];
-// Default OFF.  Measured on MI355X (r03, same box, hipGraph replay of the whole step; tools/fixup_ab.sh): config P
-// 27.49 ms with the fix-up against 27.59 ms with the reduce launch (noise), the T = 256 configuration 10.97 ms against
-// 10.43 ms.  The chain sc1 stores -> vmcnt(0) -> atomic round trip -> sc1 loads costs the last arriver ~6 us, a dependent
-// second launch ~5 us: device-scope hand-offs go through the memory side of the 8 XCDs (DESIGN_LOG.md 3.6 found the same for
-// grid barriers).  Kept (tested bit-exact against the reduce kernel) behind VILCO_GEMM_FIXUP=1 / vilco_gemm_set_fixup.
 inline bool& skinny_enabled() {
   static bool on = [] { const char* e = getenv("VILCO_GEMM_SKINNY"); return !(e && e[0] == '0'); }();
   return on;
@@ -1311,38 +1085,6 @@ inline int skinny_max_k() {
   static const int v = [] { const char* e = getenv("VILCO_GEMM_SKINNY_K"); const int x = e ? atoi(e) : 768; return x > 0 ? x : 768; }();
   return v;
 }
-inline bool& fixup_enabled() {
-  static bool on = [] { const char* e = getenv("VILCO_GEMM_FIXUP"); return e && e[0] == '1'; }();
-  return on;
-}
-unsigned* tile_counters(hipStream_t s) {
-  static std::mutex mu;
-  static hipStream_t streams[FIX_STREAMS];
-  static int n = 0;
-  static unsigned* base = nullptr;
-  std::lock_guard<std::mutex> lk(mu);
-  if (!base) {
-    void* q = nullptr;
-    if (hipGetSymbolAddress(&q, HIP_SYMBOL(vilco_tile_counters)) != hipSuccess || !q) return nullptr;
-    base = reinterpret_cast<unsigned*>(q);
-  }
-  for (int i = 0; i < n; ++i)
-    if (streams[i] == s) return base + (long)i * FIX_TILES;
-  if (n >= FIX_STREAMS) return nullptr;
-  streams[n] = s;
-  return base + (long)(n++) * FIX_TILES;
-}
-
-inline bool& gl_enabled() {      // VILCO_GEMM_GL=0 / vilco_gemm_set_gl(0): the fp16 x2 products stay on gemm_pp_kernel (rounds 1-4)
-  static bool v = [] { const char* e = getenv("VILCO_GEMM_GL"); return !(e && e[0] == '0'); }();
-  return v;
-}
-
-inline bool& tail128_enabled() {      // VILCO_GEMM_TAIL128=1 / vilco_gemm_set_tail128(1): see gemm_impl (off by default: measured, no gain)
-  static bool v = [] { const char* e = getenv("VILCO_GEMM_TAIL128"); return e && e[0] == '1'; }();
-  return v;
-}
-
 inline bool tapkm_enabled() {
   static const bool v = [] { const char* e = getenv("VILCO_CONV_DW_KM"); return !(e && e[0] == '0'); }();
   return v;
@@ -1427,9 +1169,8 @@ void make_plan(const vilco_gemm_desc* d, Plan& p) {
   // 256-row tile do not fit the LDS)
   // (single-part products: measured in the step, the weight-gradient shapes run 5-15 % slower on it than on gemm_pp_kernel's K2
   // loop -- 1024 x 3072 x 9082: 103 -> 119 us -- their intervals hold a third of the MFMAs per byte and the late group's DMAs
-  // do not land inside one MFMA phase; VILCO_GEMM_GL_SINGLE=1 selects it anyway)
-  static const bool gl_single = [] { const char* e = getenv("VILCO_GEMM_GL_SINGLE"); return e && e[0] == '1'; }();
-  p.gl = gl_enabled() && (d->precision == 3 || (d->precision == 4 && p.k2 && gl_single));
+  // do not land inside one MFMA phase: they stay there)
+  p.gl = d->precision == 3;
   if (tiles128 <= 256 || d->M < 2048) {
     p.BM = 128;
   } else {
@@ -1459,8 +1200,8 @@ void make_plan(const vilco_gemm_desc* d, Plan& p) {
   }
   const long tiles = p.BM == 256 ? tiles256 : (p.BM == 192 ? tiles192 : tiles128);
   const int nk32p = p.Kp / BK;
-  // barrier intervals of the K loop: gemm_gl_kernel 64 k (two parts) / 128 k (single part), gemm_pp_kernel 32 k (K2: 64)
-  const int nk = p.gl ? (d->precision == 4 ? (nk32p + 3) / 4 : (nk32p + 1) / 2) : (p.k2 ? (nk32p + 1) / 2 : nk32p);
+  // barrier intervals of the K loop: gemm_gl_kernel 64 k, gemm_pp_kernel 32 k (K2: 64)
+  const int nk = (p.gl || p.k2) ? (nk32p + 1) / 2 : nk32p;
   int ks = 1;
   // Split-K, re-measured in round 2 with tools/lab/ks_try*.sh (kernel + finish, operands packed): what matters is the
   // number of rounds -- a grid of exactly <= 256 workgroups beats a slightly larger one by 15-20 % (1024 x 1024 x 4608:
@@ -1517,7 +1258,7 @@ void make_plan(const vilco_gemm_desc* d, Plan& p) {
   if (force_ks >= 1 && force_ks <= nk) ks = force_ks;
   // few-row NT products of the default precision: one launch of gemm_skinny_kernel instead of a split-K plan + its reduce launch
   p.skinny = false;
-  if (skinny_enabled() && force_bm == 0 && force_ks < 1 && d->precision == 3 && gl_enabled() && !p.a_tr && !p.b_tr && !p.a_km && !p.b_km &&
+  if (skinny_enabled() && force_bm == 0 && force_ks < 1 && d->precision == 3 && !p.a_tr && !p.b_tr && !p.a_km && !p.b_km &&
       d->tap_operand == VILCO_TAP_NONE && d->band == 0 && nbatch == 1 && d->M <= skinny_max_rows() && d->K >= 64 && d->K <= skinny_max_k() &&
       d->N <= 1024) {
     // (tools/lab/skinny_ab.py, hipGraph replays: 16..512 x 512 x 512 7.3-8.8 us against 10.7-12.2 tiled, 154 x 1024 x 768 9.8 against
@@ -1537,14 +1278,6 @@ void make_plan(const vilco_gemm_desc* d, Plan& p) {
   }
   p.split_stride = out_span;
   p.part_bytes = p.ksplit > 1 ? align_up(out_span * p.ksplit * 4, 256) : 0;
-  p.fixup = false;
-  if (p.ksplit > 1 && fixup_enabled() && !p.gl) {
-    const long ntiles = tn * ((d->M + p.BM - 1) / p.BM) * nbatch;
-    if (ntiles <= FIX_TILES) {      // slots [tile][split] of BM x 128 floats in the accumulators' register layout
-      p.fixup = true;
-      p.part_bytes = align_up(ntiles * p.ksplit * (long)p.BM * BN * 4, 256);
-    }
-  }
 }
 
 template <int BM, int NP, bool F16, bool AKM, bool BKM, bool K2 = false>
@@ -1562,23 +1295,23 @@ void launch_pp_km(const GArgs& g, dim3 grid, hipStream_t s) {
   hipLaunchKernelGGL((gemm_pp_kernel<BM, NP, F16, AKM, BKM, K2>), grid, dim3(512), lds, s, g);
 }
 
-template <int BM, bool AKM, bool BKM, bool SINGLE>
+template <int BM, bool AKM, bool BKM>
 void launch_gl_km(const GArgs& g, dim3 grid, hipStream_t s) {
   constexpr size_t lds = (size_t)4 * (BM + BN) * 128;          // two stages x two slots x (A + B) x 128 B
   static const bool once = [] {
-    hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_gl_kernel<BM, AKM, BKM, SINGLE>),
+    hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_gl_kernel<BM, AKM, BKM>),
                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     (void)hipGetLastError();
     return true;
   }();
   (void)once;
-  hipLaunchKernelGGL((gemm_gl_kernel<BM, AKM, BKM, SINGLE>), grid, dim3(512), lds, s, g);
+  hipLaunchKernelGGL((gemm_gl_kernel<BM, AKM, BKM>), grid, dim3(512), lds, s, g);
 }
-template <int BM, bool SINGLE>
+template <int BM>
 void launch_gl(const GArgs& g, dim3 grid, hipStream_t s, bool akm, bool bkm) {
-  if (akm && bkm) launch_gl_km<BM, true, true, SINGLE>(g, grid, s);
-  else if (bkm) launch_gl_km<BM, false, true, SINGLE>(g, grid, s);
-  else launch_gl_km<BM, false, false, SINGLE>(g, grid, s);
+  if (akm && bkm) launch_gl_km<BM, true, true>(g, grid, s);
+  else if (bkm) launch_gl_km<BM, false, true>(g, grid, s);
+  else launch_gl_km<BM, false, false>(g, grid, s);
 }
 
 // operand orientations in use: (kc,kc) forward / convs, (kc,km) dX = dY W, (km,km) dW = dY^T X
@@ -1625,7 +1358,7 @@ ProfState& prof() { static ProfState p; return p; }
 // number of max|C| partials a vilco_gemm call with this descriptor writes to desc->amax_out (0: too many -- do not ask)
 static long amax_out_parts(const vilco_gemm_desc* d, const Plan& p) {
   const long nz = (long)d->batch_outer * d->batch_inner;
-  if (p.ksplit > 1 && !p.fixup) {
+  if (p.ksplit > 1) {
     long blocks = ((long)d->M * d->N * nz + 255) / 256;
     return blocks > 2048 ? 2048 : blocks;
   }
@@ -1744,7 +1477,6 @@ extern "C" int vilco_pack_many(const vilco_pack_item* items, int32_t n, int32_t 
   if (precision == 3) {
     int todo = 0;
     for (int i = 0; i < n; ++i) todo += have_amax[i] ? 0 : 1;
-    if (todo == n && dispatch_pack_fused(NP, pk.a, am.op, n, nbatch, s, VILCO_SITE_PACK)) return vilco_launch_status();   // amax + pack: 1 launch
     if (todo) {
       AmaxArgs am2;
       int k = 0;
@@ -1860,27 +1592,23 @@ static int gemm_impl(const vilco_gemm_desc* d, void* stream, GArgs* gout, Plan* 
   if (p.tapkm) { pb.K = d->tapC; }                                                  // X rows: Cin wide
   pb.vec = vilco_aligned(d->B, 16) && (d->ldb % 4) == 0 && (d->sBo % 4) == 0 && (d->sBi % 4) == 0;
   pb.amax = f16 ? scales + AMAX_MAX_BLOCKS : nullptr; pb.namax = 0; pb.inv_scale = scales + 2 * AMAX_MAX_BLOCKS + 2;
-  bool doneA = !packA, doneB = !packB;
   if (f16 && (packA || packB)) {
-    // k-contiguous operands: amax + pack in one launch each (grid barrier, pack.h); transposing packs keep the amax launch
     AmaxOp ma = amax_view(pa, p.a_tr, p.a_nbo, scales), mb = amax_view(pb, p.b_tr, p.b_nbo, scales + AMAX_MAX_BLOCKS);
-    if (packA && !p.a_tr && !d->a_amax) doneA = dispatch_pack_fused(p.NP, &pa, &ma, 1, p.a_nbo * p.a_nbi, s, VILCO_SITE_GEMMPACK);
-    if (packB && !p.b_tr && !d->b_amax) doneB = dispatch_pack_fused(p.NP, &pb, &mb, 1, p.b_nbo * p.b_nbi, s, VILCO_SITE_GEMMPACK);
     AmaxArgs am;
     int nops = 0;
     // partials left by the producer of A / B (vilco_gemm_desc.a_amax / b_amax) replace the amax pass over that operand
-    if (!doneA) {
+    if (packA) {
       if (d->a_amax && d->a_namax > 0) { pa.amax = d->a_amax; pa.namax = d->a_namax; }
       else { am.op[nops++] = ma; pa.namax = ma.nblocks; }
     }
-    if (!doneB) {
+    if (packB) {
       if (d->b_amax && d->b_namax > 0) { pb.amax = d->b_amax; pb.namax = d->b_namax; }
       else { am.op[nops++] = mb; pb.namax = mb.nblocks; }
     }
     if (nops) launch_amax(am, nops, s);
   }
-  if (!doneA) dispatch_pack(p.NP, pa, p.a_tr, p.a_nbo * p.a_nbi, s);
-  if (!doneB) dispatch_pack(p.NP, pb, p.b_tr, p.b_nbo * p.b_nbi, s);
+  if (packA) dispatch_pack(p.NP, pa, p.a_tr, p.a_nbo * p.a_nbi, s);
+  if (packB) dispatch_pack(p.NP, pb, p.b_tr, p.b_nbo * p.b_nbi, s);
   const float* inv_a = pa.inv_scale;
   const float* inv_b = pb.inv_scale;
   if (!packA) {    // planes from vilco_pack: [part][rows32][cols32] behind the header
@@ -1922,7 +1650,6 @@ static int gemm_impl(const vilco_gemm_desc* d, void* stream, GArgs* gout, Plan* 
   g.batch_inner = d->batch_inner; g.sCo = d->sCo; g.sCi = d->sCi;
   g.tiles_n = (d->N + BN - 1) / BN;
   g.ntiles = g.tiles_n * ((d->M + p.BM - 1) / p.BM);
-  g.tm0 = 0;
   g.ksplit = p.ksplit; g.kchunk = p.kchunk; g.split_stride = p.split_stride;
   g.inv_a = inv_a; g.inv_b = inv_b;
   g.band = d->band; g.bandT = d->bandT;
@@ -1932,49 +1659,12 @@ static int gemm_impl(const vilco_gemm_desc* d, void* stream, GArgs* gout, Plan* 
               vilco_aligned(d->residual, 16);
   g.c = p.ksplit > 1 ? parts : d->C;
   g.cfinal = d->C;
-  g.tile_ctr = nullptr;
-  if (p.fixup) {
-    g.tile_ctr = tile_counters(s);
-    if (!g.tile_ctr) return VILCO_ERR_UNSUPPORTED;      // more than FIX_STREAMS streams in one process
-  }
   g.amax_out = d->band == 1 ? nullptr : d->amax_out;
   g.e = Epi{d->alpha, d->beta, d->bias, d->preact, d->act, d->row_len, d->rowT, d->colscale, d->residual,
             d->res_masked, d->row_mask};
   const int nz = d->batch_outer * d->batch_inner;
   if (gout) { *gout = g; *pout = p; return VILCO_OK; }
   dim3 grid(g.ntiles, p.ksplit, nz);
-  // Between one and two rounds of 192-row tiles (384 tiles on 256 CUs: the k = 3 head convs at 9082 rows, 4608 x 2048, 2304 x 4096 ...)
-  // the second round is half empty and costs a whole one.  Two launches instead: ONE full round of 192-row tiles over the first
-  // rows, the remaining rows as one round of 128-row tiles (a round of those costs 0.74 of a 192-row round, see make_plan):
-  // 1.74 instead of 2 round-units on paper.  Same tiles' arithmetic as either height alone (a tile's K order does not depend on
-  // its height), row ranges disjoint, bit-identical results (tests/test_ops_gpu.py).  MEASURED (tools/lab/tail128_ab.sh, operands
-  // packed): 9082 x 1024 x 3072 184.9 -> 178.4 us, 4608 x 2048 x 1024 / 2304 x 4096 x 1024 / 9216 x 1024 x 1024 unchanged (69 us), the
-  // P step 20.49 -> 20.63 ms: the second launch starts only when the first has drained, and a lone round of 128-row tiles costs
-  // more than the 0.74 it costs inside a multi-round launch.  OFF by default (VILCO_GEMM_TAIL128=1 / vilco_gemm_set_tail128(1)).
-  if (tail128_enabled() && p.gl && d->precision == 3 && p.BM == 192 && p.ksplit == 1 && nz == 1 && !g.amax_out && d->band == 0 &&
-      g.ntiles > 256 && g.ntiles <= 512 && g.tiles_n <= 128 && (256 % g.tiles_n) == 0) {
-    const int rows1 = (256 / g.tiles_n) * 192;                        // one full round of 192-row tiles (a multiple of 128 rows)
-    const long rem_tiles = (long)((d->M - rows1 + 127) / 128) * g.tiles_n;
-    if (rows1 < d->M && rem_tiles <= 256) {
-      const bool ak = p.a_km, bk = p.b_km;
-      GArgs g1 = g, g2 = g;
-      g1.ntiles = 256; g1.tm0 = 0;
-      g2.ntiles = (int)rem_tiles; g2.tm0 = rows1 / 128;
-      hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr, e3 = nullptr;      // (every profile pair owns its two events)
-      if (prof().on) { hipEventCreate(&e0); hipEventCreate(&e1); hipEventCreate(&e2); hipEventCreate(&e3); hipEventRecord(e0, s); }
-      launch_gl<192, false>(g1, dim3(g1.ntiles, 1, 1), s, ak, bk);
-      if (e0) { hipEventRecord(e1, s); hipEventRecord(e2, s); }
-      launch_gl<128, false>(g2, dim3(g2.ntiles, 1, 1), s, ak, bk);
-      if (e0) {
-        hipEventRecord(e3, s);
-        prof().ev.emplace_back(e0, e1);
-        prof().rec.push_back(ProfRec{{rows1, d->N, d->K, nz, 192, 1, d->precision, p.a_km, p.b_km, p.a_tap | (p.b_tap << 4)}});
-        prof().ev.emplace_back(e2, e3);
-        prof().rec.push_back(ProfRec{{d->M - rows1, d->N, d->K, nz, 128, 1, d->precision, p.a_km, p.b_km, p.a_tap | (p.b_tap << 4)}});
-      }
-      return vilco_launch_status();
-    }
-  }
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   if (prof().on) { hipEventCreate(&ev0); hipEventCreate(&ev1); hipEventRecord(ev0, s); }
   {
@@ -1982,9 +1672,8 @@ static int gemm_impl(const vilco_gemm_desc* d, void* stream, GArgs* gout, Plan* 
     if (p.skinny) {
       if (p.BM == 16) launch_skinny<16>(g, s); else launch_skinny<32>(g, s);
     } else if (p.gl) {
-      const bool single = d->precision == 4;
-      if (p.BM == 192) { if (single) launch_gl<192, true>(g, grid, s, ak, bk); else launch_gl<192, false>(g, grid, s, ak, bk); }
-      else { if (single) launch_gl<128, true>(g, grid, s, ak, bk); else launch_gl<128, false>(g, grid, s, ak, bk); }
+      if (p.BM == 192) launch_gl<192>(g, grid, s, ak, bk);
+      else launch_gl<128>(g, grid, s, ak, bk);
     } else if (d->precision == 4 && p.k2) {  // one MFMA per product on the leading fp16 parts, two K-steps per barrier interval
       if (p.BM == 256) launch_pp<256, 2, true, true>(g, grid, s, ak, bk);
       else if (p.BM == 192) launch_pp<192, 2, true, true>(g, grid, s, ak, bk);
@@ -1993,12 +1682,7 @@ static int gemm_impl(const vilco_gemm_desc* d, void* stream, GArgs* gout, Plan* 
       if (p.BM == 256) launch_pp<256, 1, true>(g, grid, s, ak, bk);
       else if (p.BM == 192) launch_pp<192, 1, true>(g, grid, s, ak, bk);
       else launch_pp<128, 1, true>(g, grid, s, ak, bk);
-    } else if (f16) {
-      if (p.BM == 256) launch_pp<256, 2, true>(g, grid, s, ak, bk);
-      else if (p.BM == 192) launch_pp<192, 2, true>(g, grid, s, ak, bk);
-      else launch_pp<128, 2, true>(g, grid, s, ak, bk);
-    }
-    else if (p.BM == 256) {
+    } else if (p.BM == 256) {
       if (p.NP == 1) launch_pp<256, 1>(g, grid, s, ak, bk);
       else if (p.NP == 2) launch_pp<256, 2>(g, grid, s, ak, bk);
       else launch_pp<256, 3>(g, grid, s, ak, bk);
@@ -2013,12 +1697,12 @@ static int gemm_impl(const vilco_gemm_desc* d, void* stream, GArgs* gout, Plan* 
     prof().ev.emplace_back(ev0, ev1);
     prof().rec.push_back(ProfRec{{d->M, d->N, d->K, nz, p.BM, p.ksplit, d->precision, p.a_km, p.b_km, p.a_tap | (p.b_tap << 4)}});
   }
-  if (p.ksplit > 1 && !p.fixup && vilco_defer_active() && nz == 1 && d->alpha == 1.f && d->beta == 0.f && !d->bias &&
+  if (p.ksplit > 1 && vilco_defer_active() && nz == 1 && d->alpha == 1.f && d->beta == 0.f && !d->bias &&
       !d->preact && d->act == VILCO_ACT_NONE && !d->row_len && !d->row_mask && !d->colscale && !d->residual && d->drop_p == 0.f &&
       !d->amax_out) {
     // a plain sum of the split slabs whose result nothing reads before the end of backward (a weight gradient): recorded
     vilco_defer_push_sk(g.c, g.cfinal, g.split_stride, g.ldc, d->M, d->N, p.ksplit);
-  } else if (p.ksplit > 1 && !p.fixup) {
+  } else if (p.ksplit > 1) {
     long blocks = ((long)d->M * d->N * nz + 255) / 256;       // == amax_out_parts(): one max|C| partial per block, either form
     if (blocks > 2048) blocks = 2048;
     if (g.vec_out) hipLaunchKernelGGL(splitk_reduce_kernel<true>, dim3((int)blocks), dim3(256), 0, s, g, nz);
@@ -2051,7 +1735,7 @@ static void launch_gl_group(const GArgsN& gg, int n, int ntiles, hipStream_t s, 
 }
 
 // n (2..4) independent products of ONE shape, orientation and format in one launch (gemm_gl_group_kernel): operands packed
-// beforehand, precision 3, unbatched, untapped, no band; whatever does not qualify -- a split-K plan, the old kernel, unequal
+// beforehand, precision 3, unbatched, untapped, no band; whatever does not qualify -- a split-K plan, unequal
 // shapes -- runs as n ordinary vilco_gemm calls, in order (same results either way: the kernel body is the same).
 extern "C" int vilco_gemm_group(const vilco_gemm_desc* descs, int32_t n, void* stream) {
   if (!descs || n < 1 || n > 4) return VILCO_ERR_BADARG;
@@ -2091,33 +1775,13 @@ extern "C" int vilco_gemm_group(const vilco_gemm_desc* descs, int32_t n, void* s
 // tuning override (tools/gemm_tune.py): force the tile height (128 | 192 | 256; 0 = cost model) and the split-K count
 // (0 = heuristic) of every following vilco_gemm of this process; the environment variables VILCO_GEMM_BM / VILCO_GEMM_KS
 // give the initial values.
-// split-K finish: 1 = inside the launch (tile counters), 0 = partial slabs + splitk_reduce_kernel (default; see
-// fixup_enabled()).  Both sum the splits in the same order: the results are bitwise equal (tests/test_ops_gpu.py).
 // every setter below bumps this generation: a captured hipGraph replays the plan it recorded, so vilco_amd/graph.py keys its
 // graphs on the value (a vilco_gemm_set_* call between replays used to replay the old kernels silently)
 static int64_t g_config_gen = 0;
 extern "C" int64_t vilco_gemm_config_gen(void) { return g_config_gen; }
 
-extern "C" int vilco_gemm_set_fixup(int32_t on) {
-  fixup_enabled() = on != 0;
-  ++g_config_gen;
-  return VILCO_OK;
-}
-
-extern "C" int vilco_gemm_set_gl(int32_t on) {
-  gl_enabled() = on != 0;
-  ++g_config_gen;
-  return VILCO_OK;
-}
-
 extern "C" int vilco_gemm_set_skinny(int32_t on) {
   skinny_enabled() = on != 0;
-  ++g_config_gen;
-  return VILCO_OK;
-}
-
-extern "C" int vilco_gemm_set_tail128(int32_t on) {
-  tail128_enabled() = on != 0;
   ++g_config_gen;
   return VILCO_OK;
 }

@@ -163,8 +163,7 @@ template <int NV, bool FULL, bool RELU>
 __global__ __launch_bounds__(LN_THREADS) void ln_bwd_kernel(
     const float* __restrict__ dy, const float* __restrict__ x, const float* __restrict__ y,
     const float* __restrict__ gamma, const float* __restrict__ mean, const float* __restrict__ rstd,
-    float* __restrict__ dx, float* __restrict__ ws, long rows, int C,
-    float* __restrict__ dgamma, float* __restrict__ dbeta, unsigned* sync, const float* __restrict__ dres,
+    float* __restrict__ dx, float* __restrict__ ws, long rows, int C, const float* __restrict__ dres,
     float* __restrict__ amax_parts) {          // amax_parts (round 6): max|dx| of this block, for the consumer's operand planes
   __shared__ float red[LN_WAVES][64 * 4];
   float amax = 0.f;
@@ -247,7 +246,7 @@ __global__ __launch_bounds__(LN_THREADS) void ln_bwd_kernel(
           const float4 t = *reinterpret_cast<const float4*>(&red[w][lane * 4]);
           a.x += t.x; a.y += t.y; a.z += t.z; a.w += t.w;
         }
-        float* o = wsb + which * C + c;         // crosses the in-launch barrier: write-through stores
+        float* o = wsb + which * C + c;
         vilco_st_agent(o, a.x); vilco_st_agent(o + 1, a.y); vilco_st_agent(o + 2, a.z); vilco_st_agent(o + 3, a.w);
       }
     }
@@ -264,9 +263,6 @@ __global__ __launch_bounds__(LN_THREADS) void ln_bwd_kernel(
       amax_parts[blockIdx.x] = m;
     }
   }
-  // ws rows are [dgamma | dbeta] per block: finish the column sums in this launch (grid barrier), when the host could
-  // give us a counter; otherwise a reduce_rows launch follows
-  if (sync) vilco_finish_colsum(ws, dgamma, dbeta, (int)gridDim.x, 2 * C, C, sync, blockIdx.x, gridDim.x);
 }
 
 // out[j] = sum_r ws[r][j]  (j < ncols); also used by every two-stage column reduction.
@@ -453,11 +449,10 @@ extern "C" int vilco_layernorm_bwd_res_amax(const float* dy, const float* x, con
   const int nb = ln_blocks(rows);
   dim3 grid(nb);
   float* ws = reinterpret_cast<float*>(workspace);
-  unsigned* sync = (dgamma && dbeta) ? vilco_sync_counter(s, VILCO_SITE_LN) : nullptr;   // nb <= 256 blocks: co-resident
   float* ap = (dx_amax_parts && n_parts) ? dx_amax_parts : nullptr;       // one partial per block (nb <= 2048: ln_blocks)
   if (ap) *n_parts = nb;
-  if (relu) { LN_DISPATCH_B(nv, ln_bwd_kernel, true, dy, x, y, gamma, mean, rstd, dx, ws, (long)rows, (int)C, dgamma, dbeta, sync, dres, ap) }
-  else { LN_DISPATCH_B(nv, ln_bwd_kernel, false, dy, x, y, gamma, mean, rstd, dx, ws, (long)rows, (int)C, dgamma, dbeta, sync, dres, ap) }
-  if (dgamma && dbeta && !sync) vilco_reduce_rows(ws, dgamma, dbeta, nb, 2 * C, C, s);  // ws rows: [dgamma | dbeta]
+  if (relu) { LN_DISPATCH_B(nv, ln_bwd_kernel, true, dy, x, y, gamma, mean, rstd, dx, ws, (long)rows, (int)C, dres, ap) }
+  else { LN_DISPATCH_B(nv, ln_bwd_kernel, false, dy, x, y, gamma, mean, rstd, dx, ws, (long)rows, (int)C, dres, ap) }
+  if (dgamma && dbeta) vilco_reduce_rows(ws, dgamma, dbeta, nb, 2 * C, C, s);  // ws rows: [dgamma | dbeta]
   return vilco_launch_status();
 }

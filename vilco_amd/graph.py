@@ -41,8 +41,7 @@ _OWN_STREAM = os.environ.get("VILCO_GRAPH_OWN_STREAM", "1") != "0"      # replay
 # identical) -- ON A STREAM OF ITS OWN: replayed on the default (null) stream with the buckets queued asynchronously between
 # the stage graphs, the small gradients (the ones gathered into their bucket by a copy) came back stale or as garbage once the
 # host ran ahead (not RCCL, not the multi-tensor copy, not Python's GC; exact on any created stream).  _replay therefore moves
-# every replay off the null stream.  VILCO_DP_STAGE_SYNC=1 adds a host wait before every bucket group (the first
-# workaround; not needed any more).
+# every replay off the null stream.
 _DP_SEGMENTS = os.environ.get("VILCO_DP_SEGMENTS", "1") != "0"
 
 
@@ -239,12 +238,9 @@ class GraphedStep:
             staged = bool(red is not None and self.segments and not comm)
             tape = ops.SegTape() if staged else None
             seg_graphs, seg_done = [], []
-            forks = ops._FORKS
             pins = ops._capture_pins = []    # persistent buffers the recorded kernels address: they live as long as the graph
             try:
                 ops.seg_tape = tape
-                if staged and os.environ.get("VILCO_DP_STAGE_FORKS", "1") == "0":
-                    ops._FORKS = set()           # (debugging aid: a staged capture without the forked text / regression-head chains)
                 with torch.cuda.graph(g, pool=self._pool, **_capture_kw()):
                     if red is not None:
                         red._capture_stream = torch.cuda.current_stream()
@@ -277,7 +273,6 @@ class GraphedStep:
             finally:
                 ops.seg_tape = None
                 ops._capture_pins = None
-                ops._FORKS = forks
                 if self.reducer is not None:
                     self.reducer._capture_stream = None
                     self.reducer.end_capture()
@@ -370,7 +365,7 @@ class GraphedStep:
             torch._foreach_zero_(ent['fill'])
         red.reduce_begin()
         graphs = [ent['graph']] + list(ent['seg_graphs'])
-        if (not red._avg and _DP_REPLAY_SYNC) or os.environ.get("VILCO_DP_STAGE_LATE") == "1":      # (_LATE: debugging aid)
+        if not red._avg and _DP_REPLAY_SYNC:
             # gloo (CPU-side collectives: tests, two replicas on one GPU): a gloo collective next to a running graph crawls
             # (seconds per step, see _replay) -- the stages are replayed back to back and the exchange follows, unoverlapped
             for gk in graphs:
@@ -378,22 +373,11 @@ class GraphedStep:
             torch.cuda.current_stream().synchronize()
             red.reduce_launch(len(red.buckets))
         else:
-            mode = os.environ.get("VILCO_DP_STAGE_SYNC", "0")      # see _DP_SEGMENTS: "1" a host wait before every bucket group,
-            hsync = mode == "1"                                    # "step" one per step (on the previous step's end), "0" none (default)
-            if mode == "step":
-                ev = getattr(self, "_step_done", None)
-                if ev is not None:
-                    ev.synchronize()
             for k, gk in enumerate(graphs):
                 gk.replay()
                 if ent['seg_upto'][k] > red._next:
-                    if hsync:
-                        torch.cuda.current_stream().synchronize()
                     red.reduce_launch(ent['seg_upto'][k])
         red.reduce_wait()
-        if os.environ.get("VILCO_DP_STAGE_SYNC", "0") == "step":
-            self._step_done = torch.cuda.Event()
-            self._step_done.record()
 
     def _replay(self, ent, inp):
         """Never on the default (null) stream: graph launches with asynchronous eager work queued between them -- bucket gathers
