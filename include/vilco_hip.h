@@ -644,6 +644,26 @@ int vilco_retrieval_hits(const double* pred_start, const double* pred_end, const
                          const int32_t* grp_gt_off, int32_t n_grp, const double* thresholds, int32_t n_thr,
                          const int32_t* ranks, int32_t n_rank, int64_t* hits, int64_t* total, void* workspace,
                          size_t workspace_bytes, void* stream);
+/* External classification scores fused into the detections (fuse.hip): the expansion of           */
+/* postprocess_results (MQ/libs/utils/postprocessing.py:97-155).  Predictions are grouped by video:   */
+/* pred_score / pred_start / pred_end[n_pred] (device, fp64), video v owns rows                       */
+/* pred_off[v] .. pred_off[v + 1]; cls_score[n_vid][n_cls] (device, fp64) is the external class-score */
+/* table.  Video v keeps its m = min(num_pred, rows) best rows by score and yields topk * m rows at    */
+/* out_off[v]: the topk best classes by rank, inside a class the kept rows by rank; out_vid = v,       */
+/* out_label = the class, out_start / out_end = the row's segment, out_score = sqrt(class score * row  */
+/* score): one fp64 product and one correctly rounded square root, NaN for a negative product.  Both   */
+/* rankings: descending value, equal values (and NaN, ranked first) with the larger index first.       */
+/* pred_off and out_off[n_vid + 1] are HOST arrays; they are checked here (monotone from 0,            */
+/* pred_off[n_vid] == n_pred, out_off[v + 1] - out_off[v] == topk * m, out_off[n_vid] == n_out) and     */
+/* copied into the workspace with hipMemcpyAsync on the stream, so the call cannot be captured into a   */
+/* graph.  1 <= topk <= n_cls and num_pred >= 1 (else BADARG), topk <= 64 (else UNSUPPORTED).  No       */
+/* atomics: repeated calls are bitwise equal.                                                          */
+size_t vilco_score_fuse_workspace(int64_t n_pred, int32_t n_vid);
+int vilco_score_fuse(const double* pred_score, const double* pred_start, const double* pred_end,
+                     const int32_t* pred_off, int64_t n_pred, int32_t n_vid, const double* cls_score, int32_t n_cls,
+                     int32_t num_pred, int32_t topk, const int32_t* out_off, int64_t n_out, int32_t* out_vid,
+                     int32_t* out_label, double* out_start, double* out_end, double* out_score, void* workspace,
+                     size_t workspace_bytes, void* stream);
 /* NLQ Recall@K over IoU and mIoU (ReferringRecall).  Query q has one ground-truth window           */
 /* gt[q] = (start, end), fp64, and pred_cnt[q] predictions pred[q][0 .. cnt) = (start, end) in        */
 /* result order, 0 <= cnt <= k_cap; rows past the count are never read.  pred is fp32 when            */

@@ -15,7 +15,14 @@ Run:  python tools/eval_bench.py --nlq [--queries 5000] [--rows 5] [--segments 1
 config P's level sizes (2304 .. 72 tokens x 1024 channels): device times of vilco_frob_scale, vilco_gram and
 vilco_herd_select, the level-0 Gram product alone with its fraction of the HBM peak in bytes of X read, and the same selection
 done as the literal greedy loop in torch ops on the device.
-Run:  python tools/eval_bench.py --herding [--clips 96] [--keep 10]"""
+Run:  python tools/eval_bench.py --herding [--clips 96] [--keep 10]
+
+--ext-scores times the fusion of external classification scores (csrc/fuse.hip): --videos videos of --rows-per-video rows
+(fp32, as the model emits them), --classes classes, num_pred 200, topk 2.  One JSON line: the device time of
+vilco_score_fuse alone (HIP events), `fuse_external_scores` end to end (host grouping, upload of the un-fused rows, kernel;
+ends in a synchronise), and the route without the kernel re-stated here -- the expansion in NumPy on the host followed by
+the upload of the five fused columns -- with a check that both give the same bytes.
+Run:  python tools/eval_bench.py --ext-scores [--videos 400] [--rows-per-video 1000] [--classes 110]"""
 import argparse
 import ctypes as C
 import json
@@ -46,7 +53,11 @@ def main():
     ap.add_argument("--herding", action="store_true")
     ap.add_argument("--clips", type=int, default=96)
     ap.add_argument("--keep", type=int, default=10)
+    ap.add_argument("--ext-scores", action="store_true")
+    ap.add_argument("--rows-per-video", type=int, default=1000)
     a = ap.parse_args()
+    if a.ext_scores:
+        return ext_scores(a)
     if a.nlq:
         return nlq(a)
     if a.herding:
@@ -255,6 +266,97 @@ def herding(a):
                       "herd_select_ms": round(t_sel, 3), "herding_device_ms": round(t_frob + t_gram + t_sel, 3),
                       "literal_torch_loop_ms": round(t_lit, 1), "same_selection": sel.tolist() == sel_lit.tolist(),
                       "selection": sel.tolist()}))
+
+
+def ext_scores(a):
+    from vilco_amd import _lib
+    from vilco_amd.utils import postprocessing as PP
+    n_vid = a.videos if a.videos != 4000 else 400           # 4000 is the detection benchmark's default
+    num_pred, topk = 200, 2
+    rng = np.random.default_rng(1)
+    cnt = rng.integers(max(a.rows_per_video // 2, 1), a.rows_per_video + 1, n_vid)
+    n = int(cnt.sum())
+    vids = np.repeat(np.array(["vid%05d" % v for v in range(n_vid)], dtype=object), cnt)
+    order = rng.permutation(n)
+    res = {'video-id': vids[order].tolist(), 't-start': rng.uniform(0, 300, n).astype(np.float32),
+           't-end': rng.uniform(300, 400, n).astype(np.float32), 'label': np.zeros(n, np.int64),
+           'score': rng.uniform(size=n).astype(np.float32)}
+    cls = {"vid%05d" % v: rng.uniform(size=a.classes).tolist() for v in range(n_vid)}
+
+    def numpy_route():
+        """the expansion on the host, then the fused columns go up (what the validation loop did before the kernel)"""
+        v = np.asarray(res['video-id'], dtype=object)
+        uniq, inv = np.unique(v.astype(str), return_inverse=True)
+        perm = np.argsort(inv, kind='stable')
+        off = np.r_[0, np.cumsum(np.bincount(inv))]
+        sc, ts, te = (res[k].astype(np.float64)[perm] for k in ('score', 't-start', 't-end'))
+        V, L, S, E, W = [], [], [], [], []
+        for i, u in enumerate(uniq):
+            lo, hi = off[i], off[i + 1]
+            keep = lo + np.argsort(sc[lo:hi], kind='stable')[::-1][:num_pred]
+            c = np.asarray(cls[u], np.float64)
+            top = np.argsort(c, kind='stable')[::-1][:topk]
+            W.append(np.sqrt(c[top][:, None] * sc[keep][None, :]).reshape(-1))
+            S.append(np.tile(ts[keep], topk)); E.append(np.tile(te[keep], topk))
+            L.append(np.repeat(top, len(keep))); V.append(np.full(topk * len(keep), i))
+        cols = [torch.as_tensor(np.concatenate(x).astype(dt)).cuda()
+                for x, dt in ((V, np.int32), (L, np.int32), (S, np.float64), (E, np.float64), (W, np.float64))]
+        torch.cuda.synchronize()
+        return cols
+
+    def device_route():
+        f = PP.fuse_external_scores(res, cls, num_pred=num_pred, topk=topk)
+        torch.cuda.synchronize()
+        return f
+
+    def timed(fn, reps):
+        fn()
+        t = []
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            out = fn()
+            t.append(time.perf_counter() - t0)
+        return t, out
+    # alternate the two routes so that drift of the box hits both
+    t_np, t_dev = [], []
+    for _ in range(3):
+        t, cols = timed(numpy_route, 3); t_np += t
+        t, f = timed(device_route, 3); t_dev += t
+    same = all(c.cpu().numpy().tobytes() == f[k].cpu().numpy().tobytes()
+               for c, k in zip(cols, ('video-index', 'label', 't-start', 't-end', 'score')))
+    # the kernel alone, on device-resident inputs
+    lib = _lib.load()
+    uniq, vidx, perm = PP._by_video(res)
+    c_ = np.bincount(vidx, minlength=n_vid)
+    pred_off = np.r_[0, np.cumsum(c_)].astype(np.int32)
+    out_off = np.r_[0, np.cumsum(topk * np.minimum(c_, num_pred))].astype(np.int32)
+    n_out = int(out_off[-1])
+    d = [torch.as_tensor(res[k].astype(np.float64)[perm]).cuda() for k in ('score', 't-start', 't-end')]
+    tab = torch.as_tensor(np.stack([np.asarray(cls[u], np.float64) for u in uniq])).cuda()
+    o = [torch.empty(n_out, dtype=dt, device='cuda') for dt in (torch.int32, torch.int32, torch.float64, torch.float64,
+                                                                 torch.float64)]
+    nws = lib.vilco_score_fuse_workspace(n, n_vid)
+    ws = torch.empty(nws, dtype=torch.uint8, device='cuda')
+    i32p = C.POINTER(C.c_int32)
+
+    def run():
+        _lib.check(lib.vilco_score_fuse(d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), pred_off.ctypes.data_as(i32p), n,
+                                        n_vid, tab.data_ptr(), a.classes, num_pred, topk, out_off.ctypes.data_as(i32p), n_out,
+                                        *[t.data_ptr() for t in o], ws.data_ptr(), nws,
+                                        torch.cuda.current_stream().cuda_stream))
+    for _ in range(3):
+        run()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(a.iters):
+        run()
+    e1.record()
+    torch.cuda.synchronize()
+    ms = lambda t: [round(x * 1e3, 2) for x in sorted(t)]          # noqa: E731
+    print(json.dumps({"videos": n_vid, "rows": n, "fused_rows": n_out, "classes": a.classes, "num_pred": num_pred, "topk": topk,
+                      "device_ms": round(e0.elapsed_time(e1) / a.iters, 4), "fuse_external_scores_ms": ms(t_dev),
+                      "numpy_expansion_and_upload_ms": ms(t_np), "runs_per_route": len(t_dev), "same_bytes": bool(same)}))
 
 
 def gt_vids(ev):

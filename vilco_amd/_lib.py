@@ -184,6 +184,9 @@ SIGNATURES = {
     "vilco_retrieval_hits_workspace": (sz, [i32, i32, i32]),
     "vilco_retrieval_hits": (C.c_int, [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, i32, C.POINTER(C.c_double), i32,
                                        C.POINTER(i32), i32, c_fp, c_fp, c_fp, sz, c_fp]),
+    "vilco_score_fuse_workspace": (sz, [i64, i32]),
+    "vilco_score_fuse": (C.c_int, [c_fp, c_fp, c_fp, C.POINTER(i32), i64, i32, c_fp, i32, i32, i32, C.POINTER(i32), i64,
+                                   c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, sz, c_fp]),
     "vilco_nlq_recall_workspace": (sz, [i64, i32]),
     "vilco_nlq_recall": (C.c_int, [c_fp, i32, c_fp, i32, c_fp, c_fp, i64, i32, C.POINTER(C.c_double), i32, C.POINTER(i32), i32,
                                    i32, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, sz, c_fp]),

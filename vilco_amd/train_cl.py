@@ -66,6 +66,24 @@ def _barrier(reducer):
         dist.barrier(group=reducer.group)
 
 
+def make_mq_validate(cfg, val_stream, evaluator, retrieval_eval=None, idx_classes=None, logger=None, print_freq=100):
+    """The `validate(model, epoch, task)` callback of `run_episodes` as the reference's driver validates
+    (train_cl.py:210, :291): `valid_one_epoch_cl_single_gpu` over the tasks learnt so far, its mAP as the metric.
+    cfg['test_cfg']['ext_score_file'] (external classification scores, utils/postprocessing.py) is passed through."""
+    from .utils import train_utils as tu
+    ext_score_file = cfg.get('test_cfg', {}).get('ext_score_file')
+
+    def validate(model, epoch, task):
+        ret = tu.valid_one_epoch_cl_single_gpu(val_stream, model, epoch, task, ext_score_file=ext_score_file,
+                                               evaluator=evaluator, logger=logger, print_freq=print_freq,
+                                               dataset_name=cfg.get('dataset_name', 'ego4d_cl'),
+                                               retrieval_eval=retrieval_eval, idx_classes=idx_classes)
+        model.train()
+        return ret[4]
+
+    return validate
+
+
 def run_episodes(cfg, model, train_stream, validate=None, ckpt_folder=None, gpu_id=0, start_task=0, start_epoch=0,
                  combine_train=False, reducer=None, logger=None, print_freq=20, on_step_history=None, use_graph=False,
                  keep_history=True):

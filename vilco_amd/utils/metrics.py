@@ -193,13 +193,37 @@ class _DetGT:
         self.cls_npos = _nonempty(_dev(self.npos, torch.int32))
 
 
+def _is_device_columns(preds):
+    """the output of postprocessing.fuse_external_scores: fused rows that are already on the device"""
+    return isinstance(preds, dict) and 'video-index' in preds and 'offsets' in preds
+
+
+def _remap_device(labels, index):
+    """`_remap` on a device column"""
+    if labels.numel() == 0 or not index:
+        return labels
+    keys = torch.tensor(sorted(index), dtype=torch.int64, device=labels.device)
+    vals = torch.tensor([index[int(k)] for k in sorted(index)], dtype=torch.int64, device=labels.device)
+    lab = labels.to(torch.int64)
+    pos = torch.searchsorted(keys, lab).clamp_(0, len(keys) - 1)
+    return torch.where(keys[pos] == lab, vals[pos], lab).to(torch.int32)
+
+
+def _dev_col(a, dtype):
+    """a prediction column for vilco_det_ap: host arrays are uploaded, device tensors are passed as they are"""
+    if isinstance(a, torch.Tensor) and a.is_cuda:
+        return _nonempty(a.to(dtype).contiguous())           # no copy when the dtype and layout already fit
+    return _nonempty(_dev(a, dtype))
+
+
 def det_ap_device(gt, vidx, cls, ts, te, score, tiou_thresholds, want_flags=False):
-    """AP[n_thr, n_cls] (and the TP flags [n_thr, n_pred] in input order) of host prediction columns against a _DetGT"""
+    """AP[n_thr, n_cls] (and the TP flags [n_thr, n_pred] in input order) of prediction columns against a _DetGT.  The
+    columns are host arrays or device tensors; class indices outside [0, n_cls) are ignored by the kernel."""
     lib = _lib.load()
     thr = np.asarray(tiou_thresholds, dtype=np.float64).reshape(-1)
     n, n_thr = len(cls), len(thr)
-    cols = [_nonempty(_dev(vidx, torch.int32)), _nonempty(_dev(cls, torch.int32)), _nonempty(_dev(ts, torch.float64)),
-            _nonempty(_dev(te, torch.float64)), _nonempty(_dev(score, torch.float64))]
+    cols = [_dev_col(vidx, torch.int32), _dev_col(cls, torch.int32), _dev_col(ts, torch.float64),
+            _dev_col(te, torch.float64), _dev_col(score, torch.float64)]
     ap = torch.empty((n_thr, max(gt.n_cls, 1)), dtype=torch.float64, device='cuda')
     flags = torch.empty((n_thr, max(n, 1)), dtype=torch.uint8, device='cuda') if want_flags else None
     nws = lib.vilco_det_ap_workspace(n, gt.n_gt, n_thr)
@@ -241,8 +265,16 @@ class ANETdetection(object):
         return self._dev_gt[key]
 
     def prepare(self, preds, current_task_id=None):
-        """host part of evaluate(): the packed prediction columns (video index, class index, start, end, score)"""
+        """host part of evaluate(): the packed prediction columns (video index, class index, start, end, score); device
+        tensors when preds is the output of postprocessing.fuse_external_scores"""
         gt = self._task(current_task_id)
+        if _is_device_columns(preds):
+            # fused rows stay where they are: the video id -> GT index lookup runs once per video on the host and is
+            # expanded by the video-index column; labels are range-checked by the kernel
+            lut = _dev(_video_index(np.asarray(preds['video-id'], dtype=object), gt.video_index), torch.int32)
+            vidx = lut[preds['video-index'].long()] if len(preds['video-id']) else preds['video-index']
+            cls = preds['label'] if self.use_cl else _remap_device(preds['label'], self.activity_index)
+            return gt, (vidx, cls, preds['t-start'], preds['t-end'], preds['score'])
         vids, ts, te, labels, score = _pred_columns(preds)
         # with use_cl the reference's preds['label'].replace(list_of_dicts) is a no-op: labels are class indices as given
         cls = labels if self.use_cl else _remap(labels, self.activity_index)

@@ -443,6 +443,8 @@ def _validate_tasks(val_qilDatasetList, model, current_task_id, evaluator, retri
     learnt so far is validated on its own loader; per task the records go (a) as the ANet JSON object to the retrieval
     metric and (b) as the flat result dict to the evaluator.  Yields (n_task, num_queries, recall table [5 tIoU, 2 ranks]
     or None, avg_mAP)."""
+    from .postprocessing import fuse_external_scores, load_cls_scores
+    ext_scores = None         # the score file is read once per validation
     model.eval()
     for b in getattr(model, 'list_bias_layers', ()):
         b.eval()
@@ -457,7 +459,11 @@ def _validate_tasks(val_qilDatasetList, model, current_task_id, evaluator, retri
                         logger.info(f'Task {n_task} Rank {r}x @ tIoU {t} is {eval_result[i, j]}')
         assert evaluator is not None
         if ext_score_file is not None and isinstance(ext_score_file, str):
-            raise NotImplementedError("external classification scores (postprocess_results) are outside the hot path")
+            # train_utils.py:1153-1154, after the retrieval metric (which saw the rows as the model gave them); the fused
+            # rows are made on the device and stay there for the evaluator
+            if ext_scores is None:
+                ext_scores = load_cls_scores(ext_score_file)
+            results = fuse_external_scores(results, ext_scores)
         mAP, avg_mAP, tious = evaluator.evaluate(results, current_task_id=current_task_id, verbose=False)
         if logger is not None:
             for tiou, m in zip(tious, mAP):
