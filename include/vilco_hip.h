@@ -615,7 +615,7 @@ int vilco_nms_last_kernels(void);
 /* ------------------------------------------------------------------------------------------ */
 /* MQ evaluation on the device (evaluate.hip): ANETdetection's AP over tIoU thresholds           */
 /* (MQ/libs/utils/metrics.py:274-393) and evaluation_retrieval's Recall@K                        */
-/* (MQ/libs/utils/get_retrieval_performance.py:116-183).  All arithmetic fp64, match decisions    */
+/* (MQ/libs/utils/get_retrieval_performance.py:116-184).  All arithmetic fp64, match decisions    */
 /* bit-identical; no float atomics (repeated calls are bitwise equal).  Threshold and rank lists   */
 /* are HOST arrays (copied into kernel arguments); every other pointer is device memory.           */
 /* ------------------------------------------------------------------------------------------ */
@@ -626,6 +626,8 @@ int vilco_nms_last_kernels(void);
 /* count per class.  Outputs ap[n_thr][n_cls] and, when tp_flags is not null, the TP flag of every */
 /* prediction [n_thr][n_pred] in input order.  Score ties rank the later row first; tIoU ties      */
 /* match the later GT first.  n_thr <= 16, n_cls < 65536, n_vid < 2^24 - 1 (else UNSUPPORTED).     */
+/* A class with cls_npos == 0 has AP 0 whatever its predictions: the reference builds its class    */
+/* index from the ground truth's labels, so it never scores such a class (no 0/0 recall here).     */
 size_t vilco_det_ap_workspace(int64_t n_pred, int32_t n_gt, int32_t n_thr);
 int vilco_det_ap(const int32_t* pred_vid, const int32_t* pred_cls, const double* pred_start, const double* pred_end,
                  const double* pred_score, int64_t n_pred, const double* gt_start, const double* gt_end,
@@ -636,8 +638,10 @@ int vilco_det_ap(const int32_t* pred_vid, const int32_t* pred_cls, const double*
 /* gt_*[grp_gt_off[g] .. grp_gt_off[g + 1]) and its predictions, in result order,                 */
 /* pred_*[grp_pred_off[g] .. + grp_pred_cnt[g]).  A GT is retrieved at (threshold t, rank r) when  */
 /* one of the group's first r * n_gt predictions overlaps it by more than t (intersection over     */
-/* the hull).  Outputs hits[n_thr][n_rank] (int64 counts) and *total = number of GT;               */
-/* recall = hits / total.  n_thr <= 16, n_rank <= 8.                                               */
+/* the hull: iou(), get_retrieval_performance.py:166-184).  A NaN boundary on either side gives a  */
+/* NaN overlap, which is no hit; so does the 0/0 of a zero-width hull.  A rank of 0 retrieves        */
+/* nothing; a negative rank is BADARG.  Outputs hits[n_thr][n_rank] (int64 counts) and *total =     */
+/* number of GT; recall = hits / total.  n_thr <= 16, n_rank <= 8.                                  */
 size_t vilco_retrieval_hits_workspace(int32_t n_grp, int32_t n_thr, int32_t n_rank);
 int vilco_retrieval_hits(const double* pred_start, const double* pred_end, const int32_t* grp_pred_off,
                          const int32_t* grp_pred_cnt, const double* gt_start, const double* gt_end,

@@ -11,7 +11,8 @@ retrieval metric the prediction object rjson{e} (JSON text) and recall{e}[5, 2];
 Cases: empty predictions, a class without predictions, predictions in videos without GT, the label-remap quirks (simultaneous
 map; a label missing from the GT stays raw), the 0/0 tIoU, a (class, video) group of more than 64 GT, a class of ~20 000
 predictions, three CL tasks (current_task_id 0/1/2), and the recorded result dicts of eval_formats.pt against a synthetic
-annotation set for those clips."""
+annotation set for those clips.  metrics_edges.npz: the edge set of `case_edges` (NaN / reversed / zero-length boundaries, special
+score values, equal scores, tied tIoU, the Recall@K cut-off at r * n_gt - 1 / r * n_gt / r * n_gt + 1 predictions)."""
 import importlib.util
 import json
 import os
@@ -19,7 +20,12 @@ import pickle
 import sys
 import tempfile
 
-import numpy as np
+# The reference ranks with NumPy's default argsort()[::-1].  NumPy's AVX-512 / AVX2 sort kernels order equal keys their own
+# way at every size; its portable introsort is an insertion sort, hence stable, up to 16 elements.  The tied cases of
+# case_edges are recorded with the portable sort (and assert that it was stable); the tie-free cases do not depend on this.
+os.environ.setdefault("NPY_DISABLE_CPU_FEATURES", "AVX512F AVX512CD AVX512_SKX AVX512_CLX AVX512_CNL AVX512_ICL AVX2")
+
+import numpy as np  # noqa: E402
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 REF = "/root/reference/MQ/libs/utils"
@@ -244,9 +250,89 @@ def case_formats(rng):
     write_case("formats", ann, True, "val", evals, extra={'valid_ret': acc / wsum})
 
 
+def assert_order_defined(ann, p):
+    """The reference ranks with argsort()[::-1] (metrics.py:305, 329), whose order of equal keys is whatever NumPy's default
+    sort does.  The edge set keeps every class at 16 predictions or fewer and every (class, video) group at 16 GT or fewer,
+    where the portable sort is an insertion sort, i.e. stable; this asserts it on the very arrays the reference will sort."""
+    lab = np.asarray(p['label'])
+    for c in np.unique(lab):
+        rows = np.flatnonzero(lab == c)
+        assert len(rows) <= 16
+        sc = np.asarray(p['score'])[rows]
+        assert np.array_equal(sc.argsort(), sc.argsort(kind='stable')), c
+        for r in rows:
+            cand = np.array([a["segment"] for a in ann[p['video-id'][r]]["annotations"] if a["label_id"] == c], np.float64)
+            if len(cand) == 0:
+                continue
+            assert len(cand) <= 16
+            with np.errstate(invalid='ignore', divide='ignore'):
+                t = ref_metrics.segment_iou(np.array([p['t-start'][r], p['t-end'][r]]), cand)
+            assert np.array_equal(t.argsort(), t.argsort(kind='stable')), (c, r)
+
+
+def case_edges():
+    """Left out: NaN in a GROUND-TRUTH boundary (remove_duplicate_annotations and the JSON annotation file are not meant to
+    carry it; the device tests cover it against the restatement), groups of more than 16 GT or classes of more than 16
+    predictions with tied keys (the reference's order of ties is NumPy's introsort there, not a rule), and a class of the
+    activity index without GT (the reference builds the index from the GT labels and cannot reach it)."""
+    nan, inf = float('nan'), float('inf')
+
+    def ants(lab, segs):
+        return [{"segment": [float(a), float(b)], "label_id": lab, "label": "c%d" % lab} for a, b in segs]
+
+    gt = {"e0": ants(0, [(0, 10), (20, 30), (40, 50)]),
+          "e1": ants(1, [(50, 50), (10, 20), (60, 70)]),                       # a zero-length GT
+          "e2": ants(2, [(0, 10), (20, 30), (40, 50), (60, 70)]),
+          "e3": ants(3, [(0, 10), (20, 30)]),
+          "e4": ants(4, [(20 * k, 20 * k + 10) for k in range(8)])}           # integer grid: tied tIoU
+    rows = [
+        # class 0: NaN start / end / both, more of them than GT (NaN tIoU is the best overlap until every GT is locked)
+        ("e0", nan, 10, 0, .9), ("e0", 5, nan, 0, .8), ("e0", nan, nan, 0, .7), ("e0", 60, 70, 0, .95), ("e0", 21, 29, 0, .6),
+        ("e0", nan, 50, 0, .5), ("e0", 41, nan, 0, .4), ("e0", 40, 50, 0, .3),
+        # class 1: zero length on the zero-length GT (0/0), end < start (union 0 or negative), again zero length
+        ("e1", 50, 50, 1, .9), ("e1", 20, 10, 1, .8), ("e1", 18, 12, 1, .7), ("e1", 65, 61, 1, .6), ("e1", 12, 18, 1, .5),
+        ("e1", 50, 50, 1, .45), ("e1", 70, 60, 1, .4),
+        # class 2: scores NaN, +inf, -inf, 0.0, -0.0; the 0.0 / -0.0 rows are one tie group whose order decides the flags
+        ("e2", 0, 10, 2, nan), ("e2", 1, 10, 2, inf), ("e2", 0, 9, 2, -inf), ("e2", 20, 30, 2, 0.0), ("e2", 26, 30, 2, -0.0),
+        ("e2", 20, 29, 2, 0.0), ("e2", 27, 30, 2, -0.0), ("e2", 40, 50, 2, .5), ("e2", 41, 50, 2, nan), ("e2", 60, 70, 2, -inf),
+        ("e2", 61, 70, 2, inf), ("e2", 62, 70, 2, .5), ("e2", 2, 10, 2, nan),
+        # class 3: equal scores, the weaker overlap sometimes ranked first
+        ("e3", 0, 4, 3, .5), ("e3", 0, 10, 3, .5), ("e3", 0, 3, 3, .5), ("e3", 20, 30, 3, .7), ("e3", 20, 23, 3, .7),
+        ("e3", 20, 24, 3, .5), ("e3", 1, 10, 3, .5), ("e3", 20, 29, 3, .5),
+        # class 4: predictions that overlap two or all GT equally
+        ("e4", 5, 25, 4, .9), ("e4", 10, 20, 4, .8), ("e4", 25, 45, 4, .7), ("e4", 5, 25, 4, .6), ("e4", 45, 65, 4, .5),
+        ("e4", 0, 150, 4, .4), ("e4", 65, 85, 4, .3), ("e4", 5, 25, 4, .2), ("e4", 0, 150, 4, .1), ("e4", 30, 40, 4, .05)]
+    # Recall@K cut-off: groups of 2 GT with r * 2 - 1, r * 2, r * 2 + 1 predictions for r = 1 and r = 5; the only prediction
+    # that overlaps GT 0 is the last one, the first overlaps GT 1
+    cut = {}
+    for k, n in enumerate((1, 2, 3, 9, 10, 11)):
+        vid = "q%d" % k
+        gt[vid] = ants(5, [(10, 20), (40, 50)])
+        segs = [[100.0 + i, 101.0 + i] for i in range(n)]
+        segs[0] = [40.0, 49.0]
+        segs[-1] = [10.0, 19.0]
+        cut[vid] = [{"segment": s, "score": 1.0 - 0.01 * i, "label": "c5"} for i, s in enumerate(segs)]
+    ann = {v: {"subset": "val", "clip_id": v, "annotations": a} for v, a in gt.items()}
+
+    def preds(rs):
+        return {'video-id': [r[0] for r in rs], 't-start': np.array([r[1] for r in rs], np.float64),
+                't-end': np.array([r[2] for r in rs], np.float64), 'label': np.array([r[3] for r in rs], np.int64),
+                'score': np.array([r[4] for r in rs], np.float64)}
+
+    evals = []
+    for rs in (rows, rows[::-1]):                      # reversed input: "the later row first" names other rows
+        p = preds(rs)
+        assert_order_defined(ann, p)
+        obj = anet_obj(p)
+        obj["results"].update(cut)
+        evals.append((p, None, obj))
+    write_case("edges", ann, False, "val", evals)
+
+
 if __name__ == "__main__":
     rng = np.random.default_rng(20261016)
     case_json(rng)
     case_large(rng)
     case_cl(rng)
     case_formats(rng)
+    case_edges()

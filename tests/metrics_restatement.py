@@ -1,4 +1,4 @@
-"""NumPy restatement of the MQ evaluators (MQ/libs/utils/metrics.py:274-393, get_retrieval_performance.py:116-195), written
+"""NumPy restatement of the MQ evaluators (MQ/libs/utils/metrics.py:274-393, get_retrieval_performance.py:116-184), written
 from the definitions, with the project's tie rule (the later row first on equal scores / equal tIoU) and the TP flags of every
 prediction.  Test infrastructure only: the product scores on the device (vilco_amd.utils.metrics)."""
 import numpy as np
@@ -11,7 +11,9 @@ def _desc(x):
 
 def det_ap(vidx, cls, ts, te, score, gt_vidx, gt_cls, gt_s, gt_e, n_cls, thresholds):
     """ap[n_thr, n_cls], tp flags [n_thr, n_pred] (input order).  Predictions with cls outside [0, n_cls) are ignored,
-    those of a video without GT of their class are FPs.  GT rows in the reference's order."""
+    those of a video without GT of their class are FPs.  GT rows in the reference's order.  A class without GT rows has AP 0
+    whatever its predictions: the reference builds its class index from the GT labels and cannot reach that state (its
+    recall would be 0/0), so 0 is the value this library documents (include/vilco_hip.h, vilco_det_ap)."""
     thr = np.asarray(thresholds, dtype=np.float64)
     n_thr, n = len(thr), len(cls)
     ap = np.zeros((n_thr, n_cls))
@@ -20,7 +22,7 @@ def det_ap(vidx, cls, ts, te, score, gt_vidx, gt_cls, gt_s, gt_e, n_cls, thresho
         gsel = np.flatnonzero(gt_cls == c)
         npos = float(len(gsel))
         rows = np.flatnonzero(cls == c)
-        if len(rows) == 0:
+        if len(rows) == 0 or len(gsel) == 0:
             continue
         rows = rows[_desc(score[rows])]
         by_video = {}
@@ -61,7 +63,8 @@ def det_ap(vidx, cls, ts, te, score, gt_vidx, gt_cls, gt_s, gt_e, n_cls, thresho
 
 
 def overlap(ps, pe, gs, ge):
-    """get_retrieval_performance.py:186-195: intersection over the hull, [n_pred, n_gt]"""
+    """iou(), get_retrieval_performance.py:166-184: intersection over the hull, [n_pred, n_gt]; np.maximum / np.minimum
+    propagate NaN, so a NaN boundary on either side gives a NaN overlap, which is no hit"""
     inter = np.maximum(0.0, np.minimum(pe[:, None], ge[None, :]) - np.maximum(ps[:, None], gs[None, :]))
     union = np.maximum(0.0, np.maximum(pe[:, None], ge[None, :]) - np.minimum(ps[:, None], gs[None, :]))
     with np.errstate(invalid='ignore', divide='ignore'):
@@ -86,7 +89,7 @@ def retrieval_hits(groups, tious=(0.1, 0.2, 0.3, 0.4, 0.5), ranks=(1, 5)):
 
 
 # ----------------------------------------------------------------------------------------------- golden-case plumbing
-GOLDENS = ("json", "large", "cl", "formats")
+GOLDENS = ("json", "large", "cl", "formats", "edges")
 
 
 def golden(name):
@@ -146,3 +149,27 @@ def restated_recall(path, g, e):
     groups = [(np.stack([ps[o:o + c], pe[o:o + c]], 1), np.stack([gs[goff[k]:goff[k + 1]], ge[goff[k]:goff[k + 1]]], 1))
               for k, (o, c) in enumerate(zip(poff, pcnt))]
     return retrieval_hits(groups)
+
+
+# ------------------------------------------------------------------------------------------------- seeded random cases
+def random_case(rng, n_pred, n_cls, n_vid, ties):
+    n_gt = n_vid * 5
+    gvid = rng.integers(0, n_vid, n_gt)
+    gcls = rng.integers(0, n_cls, n_gt)
+    gs = np.round(rng.uniform(0, 100, n_gt), 0 if ties else 6)
+    ge = gs + np.round(rng.uniform(0, 20, n_gt), 0 if ties else 6)
+    src = rng.integers(0, n_gt, n_pred)
+    vidx = np.where(rng.uniform(size=n_pred) < 0.97, gvid[src], n_vid + 1).astype(np.int64)
+    cls = np.where(rng.uniform(size=n_pred) < 0.9, gcls[src], rng.integers(-1, n_cls + 2, n_pred))
+    jit = 0 if ties else 3.0
+    ts = np.round(gs[src] + rng.normal(0, 3, n_pred), 0) if ties else gs[src] + rng.normal(0, jit, n_pred)
+    te = np.maximum(ts, np.round(ge[src] + rng.normal(0, 3, n_pred), 0) if ties else ge[src] + rng.normal(0, jit, n_pred))
+    score = np.round(rng.uniform(size=n_pred), 1) if ties else rng.uniform(size=n_pred)
+    return (vidx, cls, ts, te, score), (gvid, gcls, gs, ge)
+
+
+def device_gt(gvid, gcls, gs, ge, n_cls, n_vid):
+    from vilco_amd.utils import metrics as M
+    gt = M._DetGT({'video-id': ["%d" % v for v in gvid], 't-start': gs, 't-end': ge, 'label': gcls},
+                  {i: i for i in range(n_cls)})
+    return gt

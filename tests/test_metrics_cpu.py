@@ -95,6 +95,8 @@ def test_evaluator_abi_rejects_bad_arguments():
     assert lib.vilco_det_ap(*args, 17, dummy, None, dummy, 1 << 30, None) == -2          # > 16 thresholds
     a2 = list(args); a2[14] = 1 << 16
     assert lib.vilco_det_ap(*a2, 1, dummy, None, dummy, 1 << 30, None) == -2             # class count beyond the key
+    a3 = list(args); a3[15] = (1 << 24) - 1
+    assert lib.vilco_det_ap(*a3, 1, dummy, None, dummy, 1 << 30, None) == -2             # video count beyond the key
     need = lib.vilco_det_ap_workspace(10, 1, 1)
     assert need > 0
     assert lib.vilco_det_ap(*args, 1, dummy, None, dummy, need - 1, None) == -4
@@ -103,3 +105,5 @@ def test_evaluator_abi_rejects_bad_arguments():
     r = [dummy] * 7 + [1, thr]
     assert lib.vilco_retrieval_hits(*r, 17, rk, 1, dummy, dummy, None, 0, None) == -2
     assert lib.vilco_retrieval_hits(*r, 1, rk, 9, dummy, dummy, None, 0, None) == -2
+    neg = (ctypes.c_int32 * 2)(1, -1)
+    assert lib.vilco_retrieval_hits(*r, 1, neg, 2, dummy, dummy, None, 0, None) == -1    # a negative rank

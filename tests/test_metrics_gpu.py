@@ -33,27 +33,7 @@ def test_device_matches_reference_goldens(name, tmp_path):
             np.testing.assert_array_equal(r, g['recall%d' % e])
 
 
-def _random_case(rng, n_pred, n_cls, n_vid, ties):
-    n_gt = n_vid * 5
-    gvid = rng.integers(0, n_vid, n_gt)
-    gcls = rng.integers(0, n_cls, n_gt)
-    gs = np.round(rng.uniform(0, 100, n_gt), 0 if ties else 6)
-    ge = gs + np.round(rng.uniform(0, 20, n_gt), 0 if ties else 6)
-    src = rng.integers(0, n_gt, n_pred)
-    vidx = np.where(rng.uniform(size=n_pred) < 0.97, gvid[src], n_vid + 1).astype(np.int64)
-    cls = np.where(rng.uniform(size=n_pred) < 0.9, gcls[src], rng.integers(-1, n_cls + 2, n_pred))
-    jit = 0 if ties else 3.0
-    ts = np.round(gs[src] + rng.normal(0, 3, n_pred), 0) if ties else gs[src] + rng.normal(0, jit, n_pred)
-    te = np.maximum(ts, np.round(ge[src] + rng.normal(0, 3, n_pred), 0) if ties else ge[src] + rng.normal(0, jit, n_pred))
-    score = np.round(rng.uniform(size=n_pred), 1) if ties else rng.uniform(size=n_pred)
-    return (vidx, cls, ts, te, score), (gvid, gcls, gs, ge)
-
-
-def _device_gt(gvid, gcls, gs, ge, n_cls, n_vid):
-    from vilco_amd.utils import metrics as M
-    gt = M._DetGT({'video-id': ["%d" % v for v in gvid], 't-start': gs, 't-end': ge, 'label': gcls},
-                  {i: i for i in range(n_cls)})
-    return gt
+_random_case, _device_gt = R.random_case, R.device_gt
 
 
 @pytest.mark.parametrize("ties", [False, True])

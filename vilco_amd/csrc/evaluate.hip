@@ -1,5 +1,5 @@
 // MQ and NLQ evaluation on the device: detection AP over tIoU thresholds (MQ/libs/utils/metrics.py:274-393) and Recall@K over tIoU
-// (MQ/libs/utils/get_retrieval_performance.py:116-183).  Every tIoU, precision and recall value is fp64 in the reference's
+// (MQ/libs/utils/get_retrieval_performance.py:116-184).  Every tIoU, precision and recall value is fp64 in the reference's
 // expression order and this file is compiled with -ffp-contract=off, so match decisions are bit-identical.
 //
 // Detection AP, per call:
@@ -11,7 +11,9 @@
 //            threshold the first unlocked GT in the reference's order (NaN tIoU first, then tIoU descending, later GT
 //            first on ties) among those that do not fail `tiou < thr` is locked and the prediction is a TP.
 //   ap       one workgroup per (class, threshold): integer prefix counts of the TP flags in rank order, fp64 precision /
-//            recall, the reverse running maximum and the sum of interpolated_prec_rec, in fixed order.
+//            recall, the reverse running maximum and the sum of interpolated_prec_rec, in fixed order.  A class without
+//            ground truth (cls_npos == 0) has no group, hence no TP and no term: AP 0.  The reference cannot reach that
+//            state (its class index is built from the GT labels), so 0 is this library's documented value.
 // No float atomics, no allocation, no host synchronisation; workgroups meet only at launch boundaries.
 // NLQ Recall@K over IoU and mIoU (NLQ/libs/utils/metrics.py:47-68, 107-177): see the section further down.
 #include "common.h"
@@ -179,7 +181,9 @@ __device__ __forceinline__ int lower_bound_dev(const T* a, int n, T key) {
   return lo;
 }
 
-// tIoU of one prediction against one GT, segment_iou's expression order (metrics.py:396-422)
+// tIoU of one prediction against one GT, segment_iou's expression order (metrics.py:357-381).  The ternaries drop a NaN
+// prediction boundary where np.maximum / np.minimum keep it, but `pe - ps` carries it into the union: the tIoU is NaN either
+// way (tests/test_metrics_edges_gpu.py holds that).
 __device__ __forceinline__ double seg_tiou(double ps, double pe, double gs, double ge) {
   const double tt1 = ps > gs ? ps : gs;                  // np.maximum(target[0], candidates[:, 0])
   const double tt2 = pe < ge ? pe : ge;
@@ -321,6 +325,12 @@ __global__ __launch_bounds__(RT) void ev_ap_kernel(const int* __restrict__ cls1,
 }
 
 // ------------------------------------------------------------------------------------------------------------ Recall@K
+// np.maximum / np.minimum and torch.max / torch.min: NaN propagates
+__device__ __forceinline__ double nmax(double a, double b) { return (a >= b || a != a) ? a : b; }
+__device__ __forceinline__ double nmin(double a, double b) { return (a <= b || a != a) ? a : b; }
+__device__ __forceinline__ float nmaxf(float a, float b) { return (a >= b || a != a) ? a : b; }
+__device__ __forceinline__ float nminf(float a, float b) { return (a <= b || a != a) ? a : b; }
+
 __global__ __launch_bounds__(64) void ev_hits_zero_kernel(long long* hits, int ncell, long long* total, const int* grp_gt_off,
                                                           int n_grp) {
   for (int i = threadIdx.x; i < ncell; i += 64) hits[i] = 0;
@@ -351,12 +361,9 @@ __global__ __launch_bounds__(64) void ev_hits_kernel(const double* __restrict__ 
     if (valid) {
       for (int i = 0; i < m; ++i) {
         const double ps = ps_[p0 + i], pe = pe_[p0 + i];
-        const double il = ps > gs ? ps : gs, ir = pe < ge ? pe : ge;         // get_retrieval_performance.py:186-195
-        const double di = ir - il;
-        const double inter = 0.0 > di ? 0.0 : di;
-        const double ul = ps < gs ? ps : gs, ur = pe > ge ? pe : ge;
-        const double du = ur - ul;
-        const double uni = 0.0 > du ? 0.0 : du;
+        // iou() (get_retrieval_performance.py:166-184): a NaN boundary on either side gives a NaN overlap, no hit
+        const double inter = nmax(0.0, nmin(pe, ge) - nmax(ps, gs));
+        const double uni = nmax(0.0, nmax(pe, ge) - nmin(ps, gs));
         const double ov = 1.0 * inter / uni;
         unsigned bits = 0u;
         for (int t = 0; t < n_thr; ++t) bits |= (ov > thr.t[t]) ? (1u << t) : 0u;
@@ -383,12 +390,6 @@ __global__ __launch_bounds__(64) void ev_hits_kernel(const double* __restrict__ 
 //                 thread over its queries in index order, then a fixed tree -- no atomics, repeated calls are bit-equal.
 //                 It reads n_seg * n_query segment ids; n_seg is the number of query templates (13 in the benchmark).
 enum { NLQ_NUMPY64 = 0, NLQ_TORCH32 = 1 };
-
-// np.maximum / np.minimum and torch.max / torch.min: NaN propagates
-__device__ __forceinline__ double nmax(double a, double b) { return (a >= b || a != a) ? a : b; }
-__device__ __forceinline__ double nmin(double a, double b) { return (a <= b || a != a) ? a : b; }
-__device__ __forceinline__ float nmaxf(float a, float b) { return (a >= b || a != a) ? a : b; }
-__device__ __forceinline__ float nminf(float a, float b) { return (a <= b || a != a) ? a : b; }
 
 __device__ __forceinline__ double nlq_iou64(double ps, double pe, double gs, double ge) {
   const double inter = nmax(0.0, nmin(pe, ge) - nmax(ps, gs));
