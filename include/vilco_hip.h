@@ -686,6 +686,33 @@ int vilco_nlq_recall(const void* pred, int32_t pred_fp32, const int32_t* pred_cn
                      const int32_t* seg_id, int64_t n_query, int32_t n_seg, const double* thresholds, int32_t n_thr,
                      const int32_t* ranks, int32_t n_rank, int32_t mode, int64_t* hits, int64_t* n, double* top1,
                      double* top1_sum, uint8_t* flags, void* workspace, size_t workspace_bytes, void* stream);
+/* NLQ model ensembling (ensemble.hip): the per-query recipe of NLQ/ensemble.py:7-101, 123-143 with  */
+/* NLQ/temporal_nms.py:6-74, all queries in one launch.  pred[n_model][n_query][k_cap][3] holds rows  */
+/* (start, end, score) in result order, fp32 when pred_fp32 != 0, else fp64; cnt[n_model][n_query]    */
+/* the rows present (clamped to [0, k_cap]; rows past the count are never read).  Per query:          */
+/* the first top1_max_input rows of every model, in model order, go through top1_generator: keyed by  */
+/* centre (end + start) / 2, of equal centres the last row stays; centres ascending; a centre joins   */
+/* the cluster while centre - previous centre < distance; per cluster total = the scores summed left   */
+/* to right, "max" = the first row of maximal score, "middle" = row (c - 1) / 2 for an odd count c,    */
+/* for an even one row c / 2 if its score is greater than that of row c / 2 - 1, else that row; the    */
+/* proposal is (middle + max) / 2 in start, end and score; proposals by total descending, ties in      */
+/* centre order.  The fusion list = the first max_input rows of model 0, 1, ..., then the proposals    */
+/* (scored by their averaged score).  NMS: stable order by score descending; greedily keep the head   */
+/* and drop every later row with overlap > nms_thd, overlap = max(0, min(e) - max(s)) / (max(e) -      */
+/* min(s)), 0 when that span is 0; at most max_after_nms rows.  out[n_query][max_after_nms][3] (fp64)  */
+/* = the kept rows (start, end, score); rows past the kept ones repeat the last one when pad != 0,     */
+/* else are 0; out_cnt[n_query] = rows kept before padding.  Optional (both or neither):               */
+/* prop[n_query][n_model * top1_max_input][4] = the proposals (start, end, score, total) in their      */
+/* order, rows past prop_cnt[n_query] untouched.  top1_max_input = 0 switches the generator off: with  */
+/* n_model = 1 the call is a batched temporal_nms.  All arithmetic is fp64 in the reference's order:   */
+/* bit-equal to CPython for finite inputs (NaN has no defined order there).  Limits (else BADARG, as   */
+/* for null pointers with n_query > 0): 1 <= n_model <= 8, 1 <= max_input <= 10, k_cap >=              */
+/* max_input, n_model * top1_max_input <= 64, n_model * (max_input + min(top1_max_input, k_cap)) <=    */
+/* 128, 1 <= max_after_nms <= 128.  No workspace, no atomics, no host synchronisation.                 */
+int vilco_nlq_ensemble(const void* pred, int32_t pred_fp32, const int32_t* cnt, int32_t n_model, int64_t n_query,
+                       int32_t k_cap, int32_t max_input, int32_t top1_max_input, double distance, double nms_thd,
+                       int32_t max_after_nms, int32_t pad, double* out, int32_t* out_cnt, double* prop,
+                       int32_t* prop_cnt, void* stream);
 
 /* ------------------------------------------------------------------------------------------ */
 /* Herding exemplar selection for the replay memory (herding.hip).  Replaces the reference's      */

@@ -22,7 +22,14 @@ Run:  python tools/eval_bench.py --herding [--clips 96] [--keep 10]
 vilco_score_fuse alone (HIP events), `fuse_external_scores` end to end (host grouping, upload of the un-fused rows, kernel;
 ends in a synchronise), and the route without the kernel re-stated here -- the expansion in NumPy on the host followed by
 the upload of the five fused columns -- with a check that both give the same bytes.
-Run:  python tools/eval_bench.py --ext-scores [--videos 400] [--rows-per-video 1000] [--classes 110]"""
+Run:  python tools/eval_bench.py --ext-scores [--videos 400] [--rows-per-video 1000] [--classes 110]
+
+--nlq-ensemble times the NLQ ensemble (csrc/ensemble.hip): --queries queries x --models models x 5 rows (fp32, as a record
+stream holds them), the reference's parameters.  One JSON line: the device time of vilco_nlq_ensemble alone (HIP events,
+after warm-up, median and spread over --repeats groups of --iters launches), `ensemble_streams` end to end (pairing by key,
+packing the streams' buffers, the launch; ends in a synchronise), and the fixture's `ref_seconds` (the reference's Python loop
+on the same job size, recorded on the host that made tests/golden/nlq_ensemble.npz) for scale.
+Run:  python tools/eval_bench.py --nlq-ensemble [--queries 5000] [--models 3]"""
 import argparse
 import ctypes as C
 import json
@@ -55,9 +62,14 @@ def main():
     ap.add_argument("--keep", type=int, default=10)
     ap.add_argument("--ext-scores", action="store_true")
     ap.add_argument("--rows-per-video", type=int, default=1000)
+    ap.add_argument("--nlq-ensemble", action="store_true")
+    ap.add_argument("--models", type=int, default=3)
+    ap.add_argument("--repeats", type=int, default=7)
     a = ap.parse_args()
     if a.ext_scores:
         return ext_scores(a)
+    if a.nlq_ensemble:
+        return nlq_ensemble(a)
     if a.nlq:
         return nlq(a)
     if a.herding:
@@ -357,6 +369,63 @@ def ext_scores(a):
     print(json.dumps({"videos": n_vid, "rows": n, "fused_rows": n_out, "classes": a.classes, "num_pred": num_pred, "topk": topk,
                       "device_ms": round(e0.elapsed_time(e1) / a.iters, 4), "fuse_external_scores_ms": ms(t_dev),
                       "numpy_expansion_and_upload_ms": ms(t_np), "runs_per_route": len(t_dev), "same_bytes": bool(same)}))
+
+
+def nlq_ensemble(a):
+    import nlq_ensemble_restatement as R
+    from vilco_amd.utils import ensemble_nlq as E
+    from vilco_amd.utils.metrics_nlq import NLQRecordStream
+    rng = np.random.default_rng(5)
+    n, M, rows = a.queries, a.models, 5
+    base = rng.uniform(0, 400, (1, n, 1))
+    start = base + rng.normal(0, 3.0, (M, n, rows)) * (1 + np.arange(rows))
+    far = rng.uniform(size=start.shape) < 0.08
+    start[far] = rng.uniform(0, 400, int(far.sum()))
+    end = start + rng.uniform(2, 30, (1, n, 1)) * rng.uniform(0.5, 1.5, (M, n, rows))
+    score = -np.sort(-rng.uniform(0.05, 1.0, (M, n, rows)), axis=2)
+    pred = torch.as_tensor(np.stack([start, end, score], axis=3).astype(np.float32)).cuda().contiguous()
+    cnt = torch.full((M, n), rows, dtype=torch.int32, device='cuda')
+    run = lambda: E.nlq_ensemble_device(pred, cnt)                                   # noqa: E731
+    for _ in range(5):
+        out, kept = run()
+    torch.cuda.synchronize()
+    times = []
+    for _ in range(a.repeats):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(a.iters):
+            run()
+        e1.record()
+        torch.cuda.synchronize()
+        times.append(e0.elapsed_time(e1) / a.iters)
+    # the same rows as record streams, scored end to end
+    streams = []
+    host = pred.cpu()
+    for m in range(M):
+        st = NLQRecordStream(lambda key: 0, k_cap=10, capacity=n)
+        for q in range(n):
+            st.append(("c", "a", q), host[m, q, :, :2], host[m, q, :, 2])
+        streams.append(st)
+    t_e2e = []
+    for _ in range(4):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        ens = E.ensemble_streams(streams)
+        torch.cuda.synchronize()
+        t_e2e.append(time.perf_counter() - t0)
+    assert torch.equal(ens.table, out)
+    # a sample against the plain-Python restatement
+    hp = host.double().numpy()
+    for q in range(0, n, max(n // 50, 1)):
+        want, k, _ = R.ensemble_query([hp[m, q].tolist() for m in range(M)])
+        assert out[q].cpu().tolist() == want and int(kept[q]) == k
+    times.sort()
+    print(json.dumps({"queries": n, "models": M, "rows": rows, "launches_per_group": a.iters, "groups": a.repeats,
+                      "device_ms_median": round(times[len(times) // 2], 4), "device_ms_min": round(times[0], 4),
+                      "device_ms_max": round(times[-1], 4),
+                      "ensemble_streams_ms": [round(x * 1e3, 2) for x in sorted(t_e2e[1:])],
+                      "padded_fraction": round(float((kept < 5).float().mean()), 3),
+                      "fixture_ref_seconds": round(float(R.golden()["ref_seconds"]), 3)}))
 
 
 def gt_vids(ev):

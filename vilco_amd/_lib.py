@@ -190,6 +190,8 @@ SIGNATURES = {
     "vilco_nlq_recall_workspace": (sz, [i64, i32]),
     "vilco_nlq_recall": (C.c_int, [c_fp, i32, c_fp, i32, c_fp, c_fp, i64, i32, C.POINTER(C.c_double), i32, C.POINTER(i32), i32,
                                    i32, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, sz, c_fp]),
+    "vilco_nlq_ensemble": (C.c_int, [c_fp, i32, c_fp, i32, i64, i32, i32, i32, C.c_double, C.c_double, i32, i32, c_fp, c_fp,
+                                     c_fp, c_fp, c_fp]),
     "vilco_frob_scale_workspace": (sz, [i64, i64]),
     "vilco_frob_scale": (C.c_int, [c_fp, i64, i64, i64, c_fp, c_fp, sz, c_fp]),
     "vilco_gram_workspace": (sz, [i64, i64]),
