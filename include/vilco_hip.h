@@ -749,6 +749,40 @@ size_t vilco_herd_select_workspace(int32_t n_cls, int32_t L, int32_t N);
 int vilco_herd_select(const double* grams, int32_t n_cls, int32_t L, int32_t N, int32_t m, int32_t* sel,
                       void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------ */
+/* BiC stage 2 (bic.hip): fit (alpha, beta) of the newest BiasLayer on held-out clips with the     */
+/* network frozen.  Replaces the reference's second phase, MQ/train_bic.py:602-649 with            */
+/* train_bic_one_epoch's per-step model forward, PtTransformer.losses                              */
+/* (MQ/libs/modeling/meta_archs.py:1374-1447, the focal term) and backward to the two scalars --   */
+/* whose optimizer (train_bic.py:622) the reference never steps.  The cache (built once, the       */
+/* network is frozen) holds all points of all held-out clips, clip after clip:                     */
+/*   logits[N][C] fp32 raw classification logits (before the bias correction), C <= 128;           */
+/*   label_bits[N][2] uint64, bit c = (gt_cls[n][c] == 1);  weight[N] fp32 = valid * w_cls (w_cls  */
+/*   is 1 on negatives; 0 on padded points);  pos[N] uint8 = pos_mask;  clip_ptr[n_clips + 1]      */
+/*   int32 row offsets (empty clips allowed).  For a set S of clips and the columns [lo, hi):      */
+/*   L = (1 / max(P, 1)) sum_{n in S} weight[n] sum_{c in [lo,hi)} focal(alpha x[n][c] + beta, t), */
+/*   P = sum_{n in S} pos[n],  t = bit (1 - smoothing) + smoothing / (C + 1),  focal =             */
+/*   sigmoid_focal_loss with alpha 0.25, gamma 2 (losses.py:5-52).                                 */
+/* Per-element arithmetic is fp32; the sums are fp64 from the thread upward in a fixed order: two  */
+/* calls give bit-equal results.  No atomics, no grid barrier, no host synchronisation.            */
+/* BADARG: C > 128, lo >= hi, hi > C, batch_clips <= 0, null pointers.  N < 2^24.                  */
+/* ------------------------------------------------------------------------------------------ */
+/* n_steps plain-SGD steps, step k over the clips order[k * batch_clips .. (k + 1) * batch_clips)  */
+/* (device int32; indices outside [0, n_clips) are skipped).  ab_inout[2] = (alpha, beta) fp32 on  */
+/* the device, read once and rewritten after every step; the trajectory itself is kept in fp64.    */
+/* loss_out[n_steps] fp64 = L of every step before its update.  Two launches per step, ordered by  */
+/* the stream.                                                                                     */
+size_t vilco_bic_fit_ws_bytes(int64_t N, int32_t n_clips, int32_t batch_clips, int32_t lo, int32_t hi);
+int vilco_bic_fit(const float* logits, const uint64_t* label_bits, const float* weight, const uint8_t* pos,
+                  const int32_t* clip_ptr, int64_t N, int32_t n_clips, const int32_t* order, int32_t n_steps,
+                  int32_t batch_clips, int32_t C, int32_t lo, int32_t hi, float smoothing, double lr, float* ab_inout,
+                  double* loss_out, void* ws, size_t ws_size, void* stream);
+/* One pass over all clips: out3 = (L, dL/dalpha, dL/dbeta) fp64 at ab[2] = (alpha, beta) fp32.    */
+size_t vilco_bic_eval_ws_bytes(int64_t N, int32_t n_clips, int32_t lo, int32_t hi);
+int vilco_bic_eval(const float* logits, const uint64_t* label_bits, const float* weight, const uint8_t* pos,
+                   const int32_t* clip_ptr, int64_t N, int32_t n_clips, int32_t C, int32_t lo, int32_t hi, float smoothing,
+                   const float* ab, double* out3, void* ws, size_t ws_size, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -198,6 +198,11 @@ SIGNATURES = {
     "vilco_gram": (C.c_int, [c_fp, i64, i64, i64, c_fp, c_fp, i32, c_fp, sz, c_fp]),
     "vilco_herd_select_workspace": (sz, [i32, i32, i32]),
     "vilco_herd_select": (C.c_int, [c_fp, i32, i32, i32, i32, c_fp, c_fp, sz, c_fp]),
+    "vilco_bic_fit_ws_bytes": (sz, [i64, i32, i32, i32, i32]),
+    "vilco_bic_fit": (C.c_int, [c_fp, c_fp, c_fp, c_fp, c_fp, i64, i32, c_fp, i32, i32, i32, i32, i32, f32, C.c_double, c_fp,
+                                c_fp, c_fp, sz, c_fp]),
+    "vilco_bic_eval_ws_bytes": (sz, [i64, i32, i32, i32]),
+    "vilco_bic_eval": (C.c_int, [c_fp, c_fp, c_fp, c_fp, c_fp, i64, i32, i32, i32, i32, f32, c_fp, c_fp, c_fp, sz, c_fp]),
 }
 
 _lib = None

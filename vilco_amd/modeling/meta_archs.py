@@ -385,6 +385,7 @@ class PtTransformer(nn.Module):
         self.n_known = 0
         self.dist_loss = nn.BCEWithLogitsLoss()
         self.list_bias_layers, self.list_splits = [], []
+        self.bic_raw_logits = False          # True while cl_methods/bic.py caches the logits BEFORE the bias correction
         self.cl_name = cl_cfg['name']
 
         self.prompt_pool = cl_cfg['prompt_pool']
@@ -634,7 +635,7 @@ class PtTransformer(nn.Module):
         level_T = [f.shape[1] for f in fpn_feats]
         points = self.point_generator(fpn_feats, lengths=level_T)
 
-        if self.n_known > 0 and self.cl_name == 'bic':
+        if self.n_known > 0 and self.cl_name == 'bic' and not self.bic_raw_logits:
             out_cls_logits = [self._bic_correct(x) for x in out_cls_logits]
 
         # [B, T_l] bool per level -- not needed by the fused training losses (they read the prefix lengths): 12 launches less on the

@@ -2001,6 +2001,56 @@ def herd_select(grams, m):
     return sel
 
 
+# ---------------------------------------------------------------------------------------- BiC stage 2 over cached logits
+def _bic_cache_args(logits, label_bits, weight, pos, clip_ptr):
+    for t, dt, name in ((logits, torch.float32, 'logits'), (label_bits, torch.int64, 'label_bits'),
+                        (weight, torch.float32, 'weight'), (pos, torch.uint8, 'pos'), (clip_ptr, torch.int32, 'clip_ptr')):
+        if not t.is_cuda:
+            raise RuntimeError("vilco_amd ops run on the HIP device only (got a %s tensor); there is no CPU fallback" % t.device)
+        if t.dtype != dt or not t.is_contiguous():
+            raise RuntimeError("%s must be a contiguous %s tensor" % (name, dt))
+    N, Cn = logits.shape
+    if tuple(label_bits.shape) != (N, 2) or tuple(weight.shape) != (N,) or tuple(pos.shape) != (N,) or clip_ptr.dim() != 1 \
+            or clip_ptr.numel() < 1:
+        raise RuntimeError("BiC cache arrays do not agree: logits [N, C], label_bits [N, 2], weight [N], pos [N], clip_ptr [n + 1]")
+    return int(N), int(Cn), int(clip_ptr.numel()) - 1
+
+
+def bic_eval(logits, label_bits, weight, pos, clip_ptr, lo, hi, smoothing, ab):
+    """vilco_bic_eval: (L, dL/dalpha, dL/dbeta) of the stage-2 objective over ALL clips of the cache at ab = (alpha, beta)
+    (fp32 [2] on the device) -> fp64 [3] on the device.  label_bits: int64 [N, 2] holding the uint64 bit patterns."""
+    N, Cn, n_clips = _bic_cache_args(logits, label_bits, weight, pos, clip_ptr)
+    _chk(ab)
+    lib = _lib.load()
+    out = torch.empty(3, dtype=torch.float64, device=logits.device)
+    nws = lib.vilco_bic_eval_ws_bytes(N, n_clips, int(lo), int(hi))
+    ws = _ws(nws, logits.device)
+    _lib.check(lib.vilco_bic_eval(logits.data_ptr(), label_bits.data_ptr(), weight.data_ptr(), pos.data_ptr(), clip_ptr.data_ptr(),
+                                  N, n_clips, Cn, int(lo), int(hi), float(smoothing), ab.data_ptr(), out.data_ptr(), ws.data_ptr(),
+                                  nws, _stream()))
+    return out
+
+
+def bic_fit(logits, label_bits, weight, pos, clip_ptr, order, batch_clips, lo, hi, smoothing, lr, ab):
+    """vilco_bic_fit: order.numel() // batch_clips plain-SGD steps on ab = (alpha, beta) (fp32 [2] on the device, updated in
+    place), step k over the clips order[k * batch_clips : (k + 1) * batch_clips] (int32 on the device).  Returns the steps'
+    losses, fp64 [n_steps] on the device.  Nothing waits for the host."""
+    N, Cn, n_clips = _bic_cache_args(logits, label_bits, weight, pos, clip_ptr)
+    _chk(ab)
+    if not order.is_cuda or order.dtype != torch.int32 or not order.is_contiguous():
+        raise RuntimeError("order must be a contiguous int32 tensor on the device")
+    lib = _lib.load()
+    batch_clips = int(batch_clips)
+    n_steps = int(order.numel()) // batch_clips if batch_clips > 0 else 0
+    losses = torch.empty(n_steps, dtype=torch.float64, device=logits.device)
+    nws = lib.vilco_bic_fit_ws_bytes(N, n_clips, batch_clips, int(lo), int(hi))
+    ws = _ws(nws, logits.device)
+    _lib.check(lib.vilco_bic_fit(logits.data_ptr(), label_bits.data_ptr(), weight.data_ptr(), pos.data_ptr(), clip_ptr.data_ptr(),
+                                 N, n_clips, order.data_ptr(), n_steps, batch_clips, Cn, int(lo), int(hi), float(smoothing),
+                                 float(lr), ab.data_ptr(), losses.data_ptr(), ws.data_ptr(), nws, _stream()))
+    return losses
+
+
 # ---------------------------------------------------------------------------------------- fused ln1 -> q/k/v pre-projection
 def qkv_pre_supported(Cn):
     return bool(_lib.load().vilco_qkv_pre_supported(int(Cn)))

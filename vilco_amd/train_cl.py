@@ -37,7 +37,22 @@ def load_best_checkpoint(model, file_folder, file_name, current_task, gpu_id):
         model.load_state_dict(ck['state_dict'])
         model.reg_params = ck['reg_params']
         model = model.cuda(gpu_id)
+        if 'list_splits' in ck and 'list_bias_layers' in ck:      # BiC checkpoints (train_bic.py:317-326)
+            model.list_splits = list(ck['list_splits'])
+            model.list_bias_layers = [_bias_layer(model.device, sd) for sd in ck['list_bias_layers']]
     return model
+
+
+def _bias_layer(device, state=None):
+    """a frozen BiasLayer on `device` (train_bic.py:244-248), optionally with a checkpoint's alpha / beta"""
+    from .modeling.meta_archs import BiasLayer
+    layer = BiasLayer()
+    if state is not None:
+        layer.load_state_dict(state)
+    layer.to(device)
+    for p in layer.parameters():
+        p.requires_grad = False
+    return layer
 
 
 def memory_quota(memory_size, n_classes):
@@ -46,16 +61,22 @@ def memory_quota(memory_size, n_classes):
 
 
 @torch.no_grad()
-def cache_prev_logits(model, loader, task_id, as_numpy=False):
+def cache_prev_logits(model, loader, task_id, as_numpy=False, kind='sigmoid'):
     """{video_id: [sigmoid(cls logits) per pyramid level]} of the incoming model (train_cl.py:226-235): the distillation
-    targets of iCaRL / BiC.  They stay ON THE DEVICE (one small tensor per level and clip; the reference round-trips them
+    targets of iCaRL.  They stay ON THE DEVICE (one small tensor per level and clip; the reference round-trips them
     through numpy and uploads them again in every iteration, meta_archs.py:1492,1508); as_numpy=True gives the
-    reference's format."""
+    reference's format.  kind='softmax_T2': softmax(logits[:, :n_known] / 2) instead, the targets of BiC's distillation
+    term (train_bic.py:241), which multiplies them with a log-softmax."""
+    if kind not in ('sigmoid', 'softmax_T2'):
+        raise ValueError("kind must be 'sigmoid' or 'softmax_T2', not %r" % (kind,))
     out = {}
     for video_list in loader:
         cls_logits, _, _ = model(video_list, task_id=task_id, get_emb=True)
         for i, v in enumerate(video_list):
-            probs = [torch.sigmoid(lvl[i]).clone() for lvl in cls_logits]
+            if kind == 'softmax_T2':
+                probs = [torch.softmax(lvl[i][:, :model.n_known] / 2, dim=1) for lvl in cls_logits]
+            else:
+                probs = [torch.sigmoid(lvl[i]).clone() for lvl in cls_logits]
             out[v['video_id']] = [np.array(t.cpu().numpy()) for t in probs] if as_numpy else probs
     return out
 
@@ -179,6 +200,117 @@ def run_episodes(cfg, model, train_stream, validate=None, ckpt_folder=None, gpu_
             if reducer is not None:
                 reducer.rebuild()          # the class head and the gaussian parameters are new tensors
             graph = make_graph(optimizer)  # new parameters, new optimizer: the old task's graphs are dropped
+    return model, optimizer, scheduler, log
+
+
+def run_episodes_bic(cfg, model, train_stream, validate=None, ckpt_folder=None, gpu_id=0, combine_train=False,
+                     stage2_epochs=None, stage2_lr=0.001, logger=None, print_freq=20, keep_history=True):
+    """The episode loop of BiC (cl_cfg.name = 'bic'; MQ/train_bic.py:210-760) in its order of events, through the pieces
+    of `run_episodes`.  train_stream: `utils.cl_stream.InMemoryBiCStream`'s contract, next() -> (data, stage-1 loader,
+    held-out loader or None, num_next_classes).  Per task j:
+
+      a frozen BiasLayer is appended and list_splits grows by num_classes                     (:244-249, :414-419)
+      n_known > 0: the distillation targets softmax(logits[:, :n_known] / 2) are cached       (:231-242, :423-435)
+      stage 1: train_one_epoch over the stage-1 loader, validation after the first third of the epochs, best
+          checkpoint -- with list_splits and every bias layer's alpha / beta                   (:441-549)
+      replay memory, n_known, reload of the best checkpoint, final validation                  (:551-576)
+      j >= 1, stage 2: the newest layer's alpha, beta are fitted on the held-out clips with everything else frozen --
+          `cl_methods.bic.BiCCache.build` once, then `fit_bias_layer` (one device call for all epochs; the reference
+          runs a model forward and backward per step and never steps its bias optimizer, :602-649, DESIGN.md 7);
+          the parameters are printed as `printParam` does (:624-625), the model is validated with the corrected head
+          and the checkpoint is written again so that it carries the fitted layer
+      if another task follows: augment_classification, a NEW optimizer and scheduler           (:578-599)
+
+    stage2_epochs: epochs of stage 2 (default: as many as stage 1, as in the reference); stage2_lr: its SGD learning rate
+    (:622).  Single process (the reference's stage 2 is not data parallel either).  Returns (model, optimizer, scheduler,
+    log); a task's log entry has 'bic' = {'alpha', 'beta', 'before', 'after', 'losses'} after a stage 2."""
+    from .cl_methods.bic import BiCCache, fit_bias_layer, newest_split
+    from .utils.cl_stream import DistributedBatchLoader
+    optimizer = make_optimizer(model, cfg['opt'])
+    it = iter(train_stream)
+    num_tasks = train_stream.num_tasks
+    max_epochs = cfg['opt'].get('early_stop_epochs', cfg['opt']['epochs'] + cfg['opt']['warmup_epochs'])
+    memory_size = cfg['cl_cfg']['memory_size']
+    scheduler, log = None, []
+
+    def checkpoint(j, epoch, name):
+        save_checkpoint({'task': j, 'epoch': epoch, 'state_dict': model.state_dict(), 'scheduler': scheduler.state_dict(),
+                         'optimizer': optimizer.state_dict(), 'reg_params': model.reg_params,
+                         'list_splits': list(model.list_splits),
+                         'list_bias_layers': [{k: v.detach().cpu() for k, v in b.state_dict().items()}
+                                              for b in model.list_bias_layers]}, file_folder=ckpt_folder, file_name=name)
+
+    def every_clip(ld):
+        """every clip of a loader once, in dataset order (a training loader shuffles and drops a short last batch)"""
+        items = getattr(ld, 'items', None)
+        return ld if items is None else DistributedBatchLoader(items, ld.batch_size, shuffle=False, drop_last=False)
+
+    for j in range(num_tasks):
+        data, loader, held, num_next = next(it)
+        if scheduler is None:
+            scheduler = make_scheduler(optimizer, cfg['opt'], len(loader))
+        entry = {'task': j, 'init_metric': None, 'best_metric': None, 'best_epoch': -1, 'history': []}
+        if validate is not None:
+            entry['init_metric'] = validate(model, 0, j)
+        model.list_bias_layers.append(_bias_layer(model.device))
+        model.list_splits.append(model.num_classes)
+        prev_logits = cache_prev_logits(model, every_clip(loader), j, kind='softmax_T2') if model.n_known > 0 else {}
+        best, best_epoch = -10000.0, -1
+        ck_name = 'best_task_{:03d}_performance.pth.tar'.format(j)
+        for epoch in range(max_epochs):
+            loader.sampler.set_epoch(epoch)
+            hist = train_one_epoch(loader, model, optimizer, scheduler, epoch, 1, model_ema=None,
+                                   clip_grad_l2norm=cfg['train_cfg']['clip_grad_l2norm'], print_freq=print_freq,
+                                   logger=logger, cl_name=cfg['cl_cfg']['name'], reg_lambda=cfg['cl_cfg']['reg_lambda'],
+                                   prev_out_cls_logits_dict=prev_logits, current_task_id=j, keep_history=keep_history)
+            if keep_history:
+                entry['history'].append(hist)
+            if combine_train or epoch < max_epochs // 3:
+                continue
+            metric = validate(model, epoch, j) if validate is not None else float(epoch)
+            if metric > best:
+                best, best_epoch = metric, epoch
+                if ckpt_folder is not None:
+                    checkpoint(j, epoch, ck_name)
+        entry['best_metric'], entry['best_epoch'] = best, best_epoch
+
+        n_cls = model.cls_head.cls_head.conv.out_channels
+        if memory_size != 0:
+            model.add_samples_to_mem(train_stream, data, memory_quota(memory_size, n_cls))
+        train_stream.memory = model.memory
+        model.n_known = len(model.memory)
+        if ckpt_folder is not None:
+            os.makedirs(ckpt_folder, exist_ok=True)
+            with open(os.path.join(ckpt_folder, cfg['cl_cfg']['path_memory']), 'wb') as h:
+                pickle.dump(model.memory, h)
+            model = load_best_checkpoint(model, ckpt_folder, ck_name, j, gpu_id)
+        if validate is not None:
+            entry['final_metric'] = validate(model, max_epochs - 1, j)
+
+        if held is not None:
+            cache = BiCCache.build(model, every_clip(held), j)
+            lo, hi = newest_split(model)
+            layer = model.list_bias_layers[-1]
+            before = cache.eval(lo, hi, float(layer.alpha), float(layer.beta))
+            losses = fit_bias_layer(model, cache, max_epochs if stage2_epochs is None else stage2_epochs,
+                                    getattr(held, 'batch_size', 1), lr=stage2_lr, seed=getattr(held, 'seed', 0))
+            after = cache.eval(lo, hi, float(layer.alpha), float(layer.beta))
+            for i, b in enumerate(model.list_bias_layers):
+                b.printParam(i)
+            entry['bic'] = {'alpha': float(layer.alpha), 'beta': float(layer.beta), 'before': before.tolist(),
+                            'after': after.tolist(), 'losses': losses, 'n_clips': cache.n_clips}
+            print('BiC stage 2, task %d: held-out focal loss %.6f -> %.6f over %d clips, %d steps'
+                  % (j, entry['bic']['before'][0], entry['bic']['after'][0], cache.n_clips, losses.numel()))
+            if validate is not None:
+                entry['bic_metric'] = validate(model, max_epochs - 1, j)
+            if ckpt_folder is not None:
+                checkpoint(j, best_epoch, ck_name)
+        log.append(entry)
+
+        if num_next is not None:
+            model.augment_classification(num_next, torch.device('cuda', gpu_id))
+            optimizer = make_optimizer(model, cfg['opt'])
+            scheduler = make_scheduler(optimizer, cfg['opt'], len(loader))
     return model, optimizer, scheduler, log
 
 

@@ -108,3 +108,40 @@ class InMemoryQILStream:
         if memory is not None:
             comp = {**self._tag(memory, True), **comp}
         return DistributedBatchLoader(self.flatten(comp), batch_size, shuffle=False, drop_last=False)
+
+
+class InMemoryBiCStream(InMemoryQILStream):
+    """The stream of the BiC driver (`BiCQILSetTask.__next__`, cl_benchmark.py:198-235): next(stream) ->
+    (data, stage-1 loader, held-out loader, num_next_classes).  Task 0 trains on everything and has no held-out loader
+    (None).  From task 1 on the lists of {**memory, **data} -- replayed classes first -- are cut class by class at
+    int(len * perc): the front goes to the stage-1 loader, the rest to the held-out loader that stage 2 fits the bias
+    layer on.  A class with a single clip therefore has it held out (int(0.9) = 0) and is absent from stage 1.
+    The reference never advances its task counter after task 0 (:209-213 return without `current_task += 1`) and
+    reports the size of the task itself as the next task's; here the counter advances and num_next_classes is what
+    QILSetTask gives."""
+
+    def __init__(self, set_tasks, batch_size=2, shuffle=True, seed=0, train_enable=True, rank=0, world=1, perc=0.9):
+        super().__init__(set_tasks, batch_size, shuffle, seed, train_enable, rank, world)
+        self.perc = perc
+
+    def split(self, comp):
+        train, held = {}, {}
+        for key, values in comp.items():
+            cut = int(len(values) * self.perc)
+            train[key], held[key] = values[:cut], values[cut:]
+        return train, held
+
+    def __next__(self):
+        if self.current_task >= self.num_tasks:
+            raise StopIteration
+        first = self.current_task == 0
+        data = self.set_tasks[self.current_task]
+        new = self._tag(data, False)
+        comp = {**self._tag(self.memory, True), **new} if self.train_enable else new
+        train, held = (comp, None) if first else self.split(comp)
+
+        def loader(d):
+            return DistributedBatchLoader(self.flatten(d), self.batch_size, self.shuffle, self.seed, self.rank, self.world)
+        self.current_task += 1
+        nxt = len(self.set_tasks[self.current_task]) if self.current_task < self.num_tasks else None
+        return data, loader(train), None if first else loader(held), nxt

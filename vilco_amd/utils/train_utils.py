@@ -369,6 +369,8 @@ def train_one_epoch(train_loader, model, optimizer, scheduler, curr_epoch, n_gpu
         for v in video_list:
             if prev_out_cls_logits_dict is not None and v['video_id'] in prev_out_cls_logits_dict:
                 prev.append(prev_out_cls_logits_dict[v['video_id']])
+        if prev and model.cl_name == 'bic':
+            prev = prev[-1]        # train_bic_one_epoch (train_utils.py:493): BiC's term walks ONE clip's per-level list
         if graph is not None:
             graph.between = penalty
             losses = graph(video_list, task_id=current_task_id, prev_out_cls_logits=prev)
