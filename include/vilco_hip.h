@@ -571,6 +571,17 @@ int vilco_mq_loss_bwd(const vilco_loss_desc* d, const float* g_cls, const float*
 int vilco_cl_penalty(const int64_t* ptrs, const int64_t* numel, const int32_t* chunk_tensor,
                      const int64_t* chunk_off, int32_t n, int32_t nchunks, int32_t chunk, float lambda,
                      int32_t shared_params, float* partial, float* out, void* stream);
+/* Importance accumulation of the consolidation passes MQ/libs/cl_methods/EWC.py:24-56 (on_task_update) and MAS.py:23-57        */
+/* (on_task_mas_update), which keep the last batch's squared / absolute gradient; summing over the batches, and merging the   */
+/* tasks (the commented-out consolidate_reg_params of MAS.py), is ONE multi-tensor launch over the same chunk table:           */
+/*   acc_t[i] = beta * acc_t[i] + alpha * f(src_t[i])   for i < numel[t];   op 0: f(x) = x, 1: x * x, 2: |x|                  */
+/* ptrs = device int64 [2][n]: src, acc.  numel[t] may be shorter than either allocation: elements past it are not touched.    */
+/* beta == 0: acc is not read (fresh memory needs no memset, NaNs in it do not propagate); alpha == 0: src is not read.        */
+/* Every element has one owner thread: no atomics, no workspace, the same bits on every call.  16-byte accesses wherever src  */
+/* and acc are misaligned by the same amount, 4-byte accesses otherwise.  nchunks == 0 launches nothing.                       */
+int vilco_cl_accumulate(const int64_t* ptrs, const int64_t* numel, const int32_t* chunk_tensor,
+                        const int64_t* chunk_off, int32_t n, int32_t nchunks, int32_t chunk, int32_t op, float alpha,
+                        float beta, void* stream);
 
 /* Deferred finishing (csrc/defer.hip).  The second stage of every two-stage column reduction (LayerNorm d-gamma / d-beta,  */
 /* bias and scale gradients, depthwise-tap gradients: reference autograd sums under blocks.py:152-166, 106-130, 628-641)  */

@@ -8,10 +8,15 @@ The penalty  lambda * sum_tasks sum_names sum_elems F (theta* - theta[:len(theta
 multi-tensor launch (vilco_cl_penalty, csrc/optim.hip) over a chunk table of every (task, name) pair, instead of
 one autograd graph node per pair per step: the value comes back as a device scalar, the gradient
 -2 lambda F (theta* - theta) is accumulated straight into p.grad (after backward, before clipping, which is where the
-reference's autograd puts it too)."""
+reference's autograd puts it too).
+
+The consolidation pass (`on_task_update`) reproduces the reference by default: the LAST batch's gradient, one more
+dictionary per task.  `importance='mean'` estimates the importance over the whole task and `merge='online'` keeps one
+dictionary for the whole stream; both do their arithmetic in vilco_cl_accumulate (csrc/optim.hip), one multi-tensor
+launch per batch / per merge."""
 import torch
 
-from .. import _lib
+from .. import _lib, ops
 
 CHUNK = 16384
 
@@ -74,27 +79,114 @@ def get_regularized_loss(loss, model, reg_lambda, kind='ewc'):
     return loss
 
 
-def on_task_update(loader_task, device, optimizer, model, kind='ewc', group=None, data_parallel=False):
+IMPORTANCE_MODES = ('last', 'mean')
+MERGE_MODES = ('per_task', 'online')
+
+
+def check_modes(importance, merge):
+    if importance not in IMPORTANCE_MODES:
+        raise ValueError("cl_cfg.importance must be one of %s, got %r" % (', '.join(map(repr, IMPORTANCE_MODES)), importance))
+    if merge not in MERGE_MODES:
+        raise ValueError("cl_cfg.importance_merge must be one of %s, got %r" % (', '.join(map(repr, MERGE_MODES)), merge))
+
+
+def importance_options(cl_cfg):
+    """the keyword arguments of `on_task_update` that a cl_cfg asks for: cl_cfg['importance'] ('last' | 'mean'),
+    ['importance_merge'] ('per_task' | 'online'), ['importance_gamma'].  The keys are optional (the reference's config has
+    none of them); an unknown value raises ValueError."""
+    out = dict(importance=cl_cfg.get('importance', 'last'), merge=cl_cfg.get('importance_merge', 'per_task'),
+               gamma=float(cl_cfg.get('importance_gamma', 1.0)))
+    check_modes(out['importance'], out['merge'])
+    return out
+
+
+def _mean_importance(loader_task, optimizer, model, kind):
+    """{name: mean over the batches of f(batch gradient)}, f = square (EWC) / abs (MAS): after every backward ONE
+    cl_accumulate launch adds f(p.grad) of every gradient-bearing parameter to its accumulator, one more launch scales by
+    1 / n_batches.  An accumulator is allocated when its parameter first shows a gradient (beta = 0: written, not read)."""
+    op = ops.CL_OP_SQUARE if kind == 'ewc' else ops.CL_OP_ABS
+    acc, n_batches = {}, 0
+    for video_list in loader_task:
+        optimizer.zero_grad(set_to_none=True)
+        model(video_list)['final_loss'].backward()
+        n_batches += 1
+        first, later = ([], []), ([], [])
+        for name, p in model.named_parameters():
+            if p.grad is None:
+                continue
+            g = p.grad.detach()
+            srcs, accs = later if name in acc else first
+            if name not in acc:
+                acc[name] = torch.empty(p.shape, dtype=p.dtype, device=p.device)
+            srcs.append(g if g.is_contiguous() else g.contiguous())
+            accs.append(acc[name])
+        ops.cl_accumulate(first[0], first[1], op, 1.0, 0.0)
+        ops.cl_accumulate(later[0], later[1], op, 1.0, 1.0)
+    if n_batches:
+        ops.cl_accumulate(list(acc.values()), list(acc.values()), op, 0.0, 1.0 / n_batches)
+    return {name: acc[name] for name, _ in model.named_parameters() if name in acc}
+
+
+def _merge_online(model, old_imp, imp_d, gamma):
+    """imp_d[name] += gamma * old_imp[name] on the old tensor's flat prefix (a class head that grew in dim 0 keeps the new
+    importance alone on its new rows); a name without a gradient this task is carried as gamma * old in the parameter's
+    current shape; a name that left the model is dropped."""
+    params = dict(model.named_parameters())
+    both, carried = ([], []), ([], [])
+    for name, old in old_imp.items():
+        if name not in params:
+            continue
+        if name in imp_d:
+            srcs, accs = both
+        else:
+            srcs, accs = carried
+            imp_d[name] = torch.zeros_like(params[name].data, memory_format=torch.contiguous_format)
+        new = imp_d[name]
+        assert old.numel() <= new.numel() and old.shape[1:] == new.shape[1:], name
+        srcs.append(old)
+        accs.append(new)
+    ops.cl_accumulate(both[0], both[1], ops.CL_OP_COPY, gamma, 1.0, numels=[o.numel() for o in both[0]])
+    ops.cl_accumulate(carried[0], carried[1], ops.CL_OP_COPY, gamma, 0.0, numels=[o.numel() for o in carried[0]])
+
+
+def on_task_update(loader_task, device, optimizer, model, kind='ewc', group=None, data_parallel=False, importance='last',
+                   merge='per_task', gamma=1.0):
     """importance of the weights after a task (EWC.py:24-56 / MAS.py:23-57): one pass over the task's loader with
-    zero_grad before every batch -- so, as in the reference, what is kept is the LAST batch's gradient (squared for
-    EWC, absolute for MAS) -- plus a copy of the parameters.
+    zero_grad before every batch, plus a copy of the parameters.
+    importance='last' (the reference): what is kept is the LAST batch's gradient (squared for EWC, absolute for MAS).
+    importance='mean': the mean over ALL batches of the squared / absolute BATCH gradient, accumulated on the device by
+      vilco_cl_accumulate (one launch per batch).  The granularity is the reference's -- the gradient of a batch's loss --
+      so a loader with batch size 1 gives the per-sample empirical Fisher; larger batches give the Fisher of the batch mean.
+    merge='per_task' (the reference): every task appends one dictionary, the penalty walks tasks x tensors entries.
+    merge='online': reg[key] and reg['optpar'] hold ONE dictionary: importance = new + gamma * old (the merge the
+      commented-out consolidate_reg_params of MAS.py sketches), anchored at the current parameters, so the penalty's cost
+      and the importance memory do not grow with the number of tasks.  Dictionaries that are already there (a checkpoint
+      of a per-task run) are folded in, each weighted by gamma.
     data_parallel / group: the run is data parallel over `group` (None = the default group).  Every rank sees the last batch of ITS shard, so the importances
     are averaged over the ranks (the reference wraps this pass in no DDP hook and lets them differ; the penalty is
     applied after the gradient exchange, so different importances would pull the replicas apart)."""
+    check_modes(importance, merge)
     model.train()
     reg = model.reg_params
     key = 'fisher' if kind == 'ewc' else 'importance'
     if not (key in reg and 'optpar' in reg):
         reg[key], reg['optpar'] = [], []
-    for video_list in loader_task:
-        optimizer.zero_grad(set_to_none=True)
-        model(video_list)['final_loss'].backward()
-    imp_d, opt_d = {}, {}
-    for name, p in model.named_parameters():
-        if p.grad is not None:
-            opt_d[name] = p.data.clone()
-            g = p.grad.data.clone()
-            imp_d[name] = g.pow(2) if kind == 'ewc' else g.abs()
+    if importance == 'mean':
+        imp_d = _mean_importance(loader_task, optimizer, model, kind)
+    else:
+        for video_list in loader_task:
+            optimizer.zero_grad(set_to_none=True)
+            model(video_list)['final_loss'].backward()
+        imp_d = {}
+        for name, p in model.named_parameters():
+            if p.grad is not None:
+                g = p.grad.data.clone()
+                imp_d[name] = g.pow(2) if kind == 'ewc' else g.abs()
+    if merge == 'online':
+        for old_imp in reg[key]:
+            _merge_online(model, old_imp, imp_d, float(gamma))
+        del reg[key][:], reg['optpar'][:]
+    opt_d = {name: p.data.clone() for name, p in model.named_parameters() if name in imp_d}
     if data_parallel and torch.distributed.is_initialized() and torch.distributed.get_world_size(group) > 1:
         ws = float(torch.distributed.get_world_size(group))
         for name in sorted(imp_d):                      # the same order on every rank

@@ -187,6 +187,62 @@ __global__ __launch_bounds__(OPT_THREADS) void cl_penalty_atomic_kernel(MultiArg
   if (threadIdx.x == 0) partial[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
+// Importance accumulation of the consolidation pass (MQ/libs/cl_methods/EWC.py:24-56, MAS.py:23-57, summed over the task's
+// batches instead of keeping the last one): acc = beta * acc + alpha * f(src), f = x | x^2 | |x|, over a chunk table of
+// (src, acc) pairs.  ptrs = [2][n]: src, acc; numel[t] = elements to touch (a prefix of acc when the class head has grown).
+// Pure streaming, one owner thread per element.  beta == 0: acc is not read; alpha == 0: src is not read.
+template <int OP>
+__device__ __forceinline__ float cl_acc_value(float a, float x, float alpha, float beta, bool rd_src, bool rd_acc) {
+  const float f = OP == 1 ? x * x : OP == 2 ? fabsf(x) : x;
+  if (!rd_acc) return alpha * f;
+  return rd_src ? __fmaf_rn(beta, a, alpha * f) : beta * a;
+}
+
+template <int OP>
+__device__ __forceinline__ void cl_acc_scalar(const float* src, float* acc, long lo, long hi, float alpha, float beta,
+                                              bool rd_src, bool rd_acc) {
+  for (long i = lo + threadIdx.x; i < hi; i += OPT_THREADS) {
+    const float x = rd_src ? src[i] : 0.f;
+    const float a = rd_acc ? acc[i] : 0.f;
+    acc[i] = cl_acc_value<OP>(a, x, alpha, beta, rd_src, rd_acc);
+  }
+}
+
+template <int OP>
+__global__ __launch_bounds__(OPT_THREADS) void cl_accumulate_kernel(MultiArgs a, float alpha, float beta) {
+  const int t = a.chunk_tensor[blockIdx.x];
+  const long off = a.chunk_off[blockIdx.x];
+  const float* src = reinterpret_cast<const float*>(a.ptrs[t]) + off;
+  float* acc = reinterpret_cast<float*>(a.ptrs[(long)a.n + t]) + off;
+  long cnt = a.numel[t] - off;
+  if (cnt > a.chunk) cnt = a.chunk;
+  if (off < 0 || cnt <= 0) return;
+  const bool rd_src = alpha != 0.f, rd_acc = beta != 0.f;
+  // 16-byte accesses over the part where BOTH streams are 16-byte aligned: that needs the same misalignment on both (tensor
+  // base pointers are arbitrary); then a scalar head of up to 3 elements, the wide body, a scalar tail.  Otherwise all scalar.
+  const unsigned ma = (unsigned)(reinterpret_cast<uintptr_t>(acc) & 15), ms = (unsigned)(reinterpret_cast<uintptr_t>(src) & 15);
+  long head = cnt, nvec = 0;
+  if (ma == ms && (ma & 3) == 0) {
+    head = ((16 - ma) & 15) >> 2;
+    if (head > cnt) head = cnt;
+    nvec = (cnt - head) >> 2;
+  }
+  cl_acc_scalar<OP>(src, acc, 0, head, alpha, beta, rd_src, rd_acc);
+  const float4* s4 = reinterpret_cast<const float4*>(src + head);
+  float4* a4 = reinterpret_cast<float4*>(acc + head);
+  for (long i = threadIdx.x; i < nvec; i += OPT_THREADS) {
+    const float4 x = rd_src ? s4[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+    const float4 v = rd_acc ? a4[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+    float4 r;
+    r.x = cl_acc_value<OP>(v.x, x.x, alpha, beta, rd_src, rd_acc);
+    r.y = cl_acc_value<OP>(v.y, x.y, alpha, beta, rd_src, rd_acc);
+    r.z = cl_acc_value<OP>(v.z, x.z, alpha, beta, rd_src, rd_acc);
+    r.w = cl_acc_value<OP>(v.w, x.w, alpha, beta, rd_src, rd_acc);
+    a4[i] = r;
+  }
+  cl_acc_scalar<OP>(src, acc, head + 4 * nvec, cnt, alpha, beta, rd_src, rd_acc);
+}
+
 __global__ __launch_bounds__(OPT_THREADS) void scaled_sum_kernel(const float* __restrict__ partial, int n, float scale,
                                                                  float* __restrict__ out) {
   __shared__ double red[OPT_THREADS];
@@ -234,6 +290,21 @@ extern "C" int vilco_cl_penalty(const int64_t* ptrs, const int64_t* numel, const
       hipLaunchKernelGGL(cl_penalty_kernel, dim3(nchunks), dim3(OPT_THREADS), 0, s, a, lambda, partial);
   }
   hipLaunchKernelGGL(scaled_sum_kernel, dim3(1), dim3(OPT_THREADS), 0, s, partial, nchunks, lambda, out);
+  return vilco_launch_status();
+}
+
+extern "C" int vilco_cl_accumulate(const int64_t* ptrs, const int64_t* numel, const int32_t* chunk_tensor,
+                                   const int64_t* chunk_off, int32_t n, int32_t nchunks, int32_t chunk, int32_t op,
+                                   float alpha, float beta, void* stream) {
+  if (!ptrs || !numel || !chunk_tensor || !chunk_off || n < 0 || nchunks < 0 || chunk <= 0 || op < 0 || op > 2)
+    return VILCO_ERR_BADARG;
+  if (nchunks == 0) return VILCO_OK;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  MultiArgs a{reinterpret_cast<const long*>(ptrs), reinterpret_cast<const long*>(numel), chunk_tensor,
+              reinterpret_cast<const long*>(chunk_off), nullptr, n, chunk};
+  if (op == 0) hipLaunchKernelGGL(cl_accumulate_kernel<0>, dim3(nchunks), dim3(OPT_THREADS), 0, s, a, alpha, beta);
+  else if (op == 1) hipLaunchKernelGGL(cl_accumulate_kernel<1>, dim3(nchunks), dim3(OPT_THREADS), 0, s, a, alpha, beta);
+  else hipLaunchKernelGGL(cl_accumulate_kernel<2>, dim3(nchunks), dim3(OPT_THREADS), 0, s, a, alpha, beta);
   return vilco_launch_status();
 }
 

@@ -2001,6 +2001,67 @@ def herd_select(grams, m):
     return sel
 
 
+# ---------------------------------------------------------------------------------------- EWC / MAS importance accumulation
+CL_CHUNK = 16384
+CL_OP_COPY, CL_OP_SQUARE, CL_OP_ABS = 0, 1, 2
+_cl_table = {}          # the last chunk table, by (numels, device): a consolidation pass asks for the same one every batch
+
+
+def _cl_chunks(numels, device):
+    key = (tuple(numels), device)
+    if key not in _cl_table:
+        ct, co = [], []
+        for i, n in enumerate(numels):
+            for off in range(0, n, CL_CHUNK):
+                ct.append(i)
+                co.append(off)
+        _cl_table.clear()
+        _cl_table[key] = (torch.tensor(numels, dtype=torch.int64).to(device), torch.tensor(ct, dtype=torch.int32).to(device),
+                          torch.tensor(co, dtype=torch.int64).to(device))
+    return _cl_table[key]
+
+
+def cl_accumulate(srcs, accs, op, alpha, beta, numels=None):
+    """vilco_cl_accumulate: accs[t][:n_t] = beta * accs[t][:n_t] + alpha * f(srcs[t][:n_t]) over the flat elements of every
+    pair, in place, as ONE multi-tensor launch.  op: 0 f(x) = x, 1 x * x, 2 |x|.  numels: n_t per pair (default: all of
+    accs[t]); elements past it are not touched.  beta == 0: accs is not read; alpha == 0: srcs is not read.
+    Pairs that live in HOST memory get the same expression, in the same order, as tensor ops (the consolidation pass of a
+    model that lives on the host); device tensors always go through the kernel."""
+    if op not in (CL_OP_COPY, CL_OP_SQUARE, CL_OP_ABS):
+        raise ValueError("cl_accumulate: op must be 0 (x), 1 (x * x) or 2 (|x|), got %r" % (op,))
+    srcs, accs = list(srcs), list(accs)
+    if len(srcs) != len(accs):
+        raise RuntimeError("cl_accumulate: %d sources for %d accumulators" % (len(srcs), len(accs)))
+    numels = [a.numel() for a in accs] if numels is None else [int(n) for n in numels]
+    if len(numels) != len(accs) or any(n < 0 or n > a.numel() or n > s.numel() for n, s, a in zip(numels, srcs, accs)):
+        raise RuntimeError("cl_accumulate: numels must give a prefix of every source and accumulator")
+    if not accs:
+        return
+    alpha, beta = float(alpha), float(beta)
+    if not any(t.is_cuda for t in srcs + accs):
+        for s, a, n in zip(srcs, accs, numels):
+            if s.dtype != torch.float32 or a.dtype != torch.float32 or not (s.is_contiguous() and a.is_contiguous()):
+                raise RuntimeError("cl_accumulate needs contiguous fp32 tensors")
+            av = a.detach().view(-1)[:n]
+            if alpha == 0.0:
+                av.mul_(beta) if beta != 0.0 else av.zero_()
+                continue
+            x = s.detach().view(-1)[:n]
+            f = x * x if op == CL_OP_SQUARE else x.abs() if op == CL_OP_ABS else x
+            if beta == 0.0:
+                av.copy_(f * alpha)
+            else:
+                av.mul_(beta).add_(f * alpha)
+        return
+    _chk(*srcs)
+    _chk(*accs)
+    dev = accs[0].device
+    t_numel, t_ct, t_co = _cl_chunks(numels, dev)
+    ptrs = torch.tensor([[s.data_ptr() for s in srcs], [a.data_ptr() for a in accs]], dtype=torch.int64).to(dev, non_blocking=True)
+    _lib.check(_lib.load().vilco_cl_accumulate(ptrs.data_ptr(), t_numel.data_ptr(), t_ct.data_ptr(), t_co.data_ptr(), len(accs),
+                                               int(t_ct.numel()), CL_CHUNK, int(op), alpha, beta, _stream()))
+
+
 # ---------------------------------------------------------------------------------------- BiC stage 2 over cached logits
 def _bic_cache_args(logits, label_bits, weight, pos, clip_ptr):
     for t, dt, name in ((logits, torch.float32, 'logits'), (label_bits, torch.int64, 'label_bits'),

@@ -116,6 +116,7 @@ def run_episodes(cfg, model, train_stream, validate=None, ckpt_folder=None, gpu_
     keep_history: keep every iteration's loss dict (device scalars) in the log; off for long runs.
     Returns (model, optimizer, scheduler, log) with log = list of per-task dicts."""
     is_main = int(os.environ.get("LOCAL_RANK", "0")) == 0
+    imp_opts = regularizers.importance_options(cfg['cl_cfg'])      # a bad value fails here, not after the first task
     optimizer = make_optimizer(model, cfg['opt'])
 
     def make_graph(opt):
@@ -192,9 +193,11 @@ def run_episodes(cfg, model, train_stream, validate=None, ckpt_folder=None, gpu_
         if num_next is not None:
             model.augment_classification(num_next, torch.device('cuda', gpu_id))
             if cfg['cl_cfg']['name'] == 'ewc':
-                model.reg_params = regularizers.on_task_update(loader, gpu_id, optimizer, model, kind='ewc', group=getattr(reducer, 'group', None), data_parallel=reducer is not None)
+                model.reg_params = regularizers.on_task_update(loader, gpu_id, optimizer, model, kind='ewc', group=getattr(reducer, 'group', None), data_parallel=reducer is not None,
+                                                               **imp_opts)
             elif cfg['cl_cfg']['name'] == 'mas':
-                model.reg_params = regularizers.on_task_update(loader, gpu_id, optimizer, model, kind='mas', group=getattr(reducer, 'group', None), data_parallel=reducer is not None)
+                model.reg_params = regularizers.on_task_update(loader, gpu_id, optimizer, model, kind='mas', group=getattr(reducer, 'group', None), data_parallel=reducer is not None,
+                                                               **imp_opts)
             optimizer = make_optimizer(model, cfg['opt'])
             scheduler = make_scheduler(optimizer, cfg['opt'], iters_per_epoch)
             if reducer is not None:
@@ -361,6 +364,7 @@ def run_episodes_nlq(cfg, model, train_stream, val_stream, evaluator, ckpt_folde
     Returns (model, optimizer, scheduler, log)."""
     from .utils import train_utils_nlq as tu
     is_main = int(os.environ.get("LOCAL_RANK", "0")) == 0
+    imp_opts = regularizers.importance_options(cfg['cl_cfg'])
     hb = cfg['opt']["backbone_lr_weight"] != 1
 
     def new_optimizer():
@@ -448,7 +452,8 @@ def run_episodes_nlq(cfg, model, train_stream, val_stream, evaluator, ckpt_folde
         if num_next is not None:
             if cfg['cl_cfg']['name'] in ('ewc', 'mas'):
                 model.reg_params = regularizers.on_task_update(loader, gpu_id, optimizer, model, kind=cfg['cl_cfg']['name'],
-                                                               group=getattr(reducer, 'group', None), data_parallel=reducer is not None)
+                                                               group=getattr(reducer, 'group', None), data_parallel=reducer is not None,
+                                                               **imp_opts)
             optimizer = new_optimizer()
             scheduler = tu.make_scheduler(optimizer, cfg['opt'], iters_per_epoch)
             graph = make_graph(optimizer)
