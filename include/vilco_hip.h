@@ -794,6 +794,52 @@ int vilco_bic_eval(const float* logits, const uint64_t* label_bits, const float*
                    const int32_t* clip_ptr, int64_t N, int32_t n_clips, int32_t C, int32_t lo, int32_t hi, float smoothing,
                    const float* ab, double* out3, void* ws, size_t ws_size, void* stream);
 
+/* ------------------------------------------------------------------------------------------ */
+/* Narration SSL of the ViLCo recipe (ssl.hip).  Replaces, in MQ/libs/modeling/meta_archs.py,      */
+/* the masked mean poolings of forward (:794-811), MemoryBank.update (:38-60), the branch          */
+/* :939-945 and masked_contrastive_loss (:1351-1372) -- without their host reads (the mask sum,    */
+/* the boolean indexing, the Python ring pointer), so the step can be captured and replayed.       */
+/* fp32, wave64, fixed-order two-stage sums, no atomics: repeated calls are bit-equal.             */
+/* ------------------------------------------------------------------------------------------ */
+/* out[B][C] = (1/L) sum_l (1/max(len[b][l], 1)) sum_{t < len[b][l]} feats[l][b][t][:].            */
+/* feats: HOST array of L device pointers to token-major fp32 [B][T[l]][C]; T: host int32[L];      */
+/* lens: device int32 [B][L] prefix lengths (clamped to [0, T[l]]; 0 contributes zero, as the      */
+/* reference's denom[denom == 0] = 1).  Elements at or above the length are never read.  L = 1     */
+/* pools the narration encoder's output over the token lengths.  BADARG: L < 1, L > 16, B < 1,     */
+/* C < 1, T[l] < 1, null pointers.  The workspace holds the per-slab partials.                     */
+size_t vilco_ssl_pool_workspace(const int32_t* T, int32_t L, int32_t B, int32_t C);
+int vilco_ssl_pool_fwd(const float* const* feats, const int32_t* T, int32_t L, const int32_t* lens, int32_t B,
+                       int32_t C, float* out, void* workspace, size_t workspace_bytes, void* stream);
+/* dfeats[l][b][t][:] = dout[b][:] / (L max(len, 1)) for t < len, 0 for len <= t < T[l].            */
+int vilco_ssl_pool_bwd(const float* dout, float* const* dfeats, const int32_t* T, int32_t L, const int32_t* lens,
+                       int32_t B, int32_t C, void* stream);
+/* InfoNCE against the memory bank.  text, video: raw pooled rows [B][D]; mask: float [B], a row   */
+/* takes part when mask[b] != 0; bank [M][D]; ring: device int32[1], the bank's write position.    */
+/* In the reference's order: (1) both inputs are L2-normalised (x / max(||x||, 1e-12)) into        */
+/* xn[2][B][D]; (2) the masked normalised text rows, compacted in batch order, are written to      */
+/* bank rows (ring + rank) mod M and ring advances by their count n modulo M -- a launch of its    */
+/* own, so the loss sees the rows just written among its negatives; (3) per masked row and         */
+/* modality, logits [pos, x . bank_j ...] / temperature and their log-sum-exp;                     */
+/*   loss[0] = sum_masked ((lse_t - pos/temp) + (lse_v - pos/temp)) / (2 n).                       */
+/* n == 0: loss = 0, bank and ring untouched.  Saved for the backward: xn, stats[7 B] = (norms     */
+/* [2][B], pos [B], lse as shift [2][B] + log of the shifted sum [2][B]), logits [2 B][M] in fp64   */
+/* (accumulated in fp64: at temperature 0.07 fp32 rounding of a logit is 4e-6 of its probability). */
+/* BADARG: D % 4 != 0, D > 4096, B < 1, B > 64, B > M (the reference's assert), temperature <= 0,  */
+/* null or misaligned pointers.                                                                    */
+size_t vilco_ssl_nce_workspace(int32_t B, int32_t D, int32_t M);
+int vilco_ssl_nce_fwd(const float* text, const float* video, const float* mask, int32_t B, int32_t D, float* bank,
+                      int32_t M, int32_t* ring, float temperature, float* xn, float* stats, double* logits,
+                      float* loss, void* workspace, size_t workspace_bytes, void* stream);
+/* dtext, dvideo [B][D]: gradients of gloss[0] * loss with respect to the RAW text and video rows  */
+/* (through the normalisation, the positive pair's cross term in both); the bank must be what the  */
+/* forward left.  Unmasked rows and n == 0 give exact zeros.  The bank gets no gradient.           */
+int vilco_ssl_nce_bwd(const float* gloss, const float* mask, const float* xn, const float* stats, const double* logits,
+                      const float* bank, int32_t B, int32_t D, int32_t M, float temperature, float* dtext,
+                      float* dvideo, void* workspace, size_t workspace_bytes, void* stream);
+/* Step (2) alone, for rows that are normalised already (MemoryBank.update_masked).                */
+int vilco_ssl_ring_update(const float* rows, const float* mask, int32_t B, int32_t D, float* bank, int32_t M,
+                          int32_t* ring, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

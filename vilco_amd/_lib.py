@@ -204,6 +204,13 @@ SIGNATURES = {
                                 c_fp, c_fp, sz, c_fp]),
     "vilco_bic_eval_ws_bytes": (sz, [i64, i32, i32, i32]),
     "vilco_bic_eval": (C.c_int, [c_fp, c_fp, c_fp, c_fp, c_fp, i64, i32, i32, i32, i32, f32, c_fp, c_fp, c_fp, sz, c_fp]),
+    "vilco_ssl_pool_workspace": (sz, [C.POINTER(i32), i32, i32, i32]),
+    "vilco_ssl_pool_fwd": (C.c_int, [C.POINTER(c_fp), C.POINTER(i32), i32, c_fp, i32, i32, c_fp, c_fp, sz, c_fp]),
+    "vilco_ssl_pool_bwd": (C.c_int, [c_fp, C.POINTER(c_fp), C.POINTER(i32), i32, c_fp, i32, i32, c_fp]),
+    "vilco_ssl_nce_workspace": (sz, [i32, i32, i32]),
+    "vilco_ssl_nce_fwd": (C.c_int, [c_fp, c_fp, c_fp, i32, i32, c_fp, i32, c_fp, f32, c_fp, c_fp, c_fp, c_fp, c_fp, sz, c_fp]),
+    "vilco_ssl_nce_bwd": (C.c_int, [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, i32, i32, i32, f32, c_fp, c_fp, c_fp, sz, c_fp]),
+    "vilco_ssl_ring_update": (C.c_int, [c_fp, c_fp, i32, i32, c_fp, i32, c_fp, c_fp]),
 }
 
 _lib = None

@@ -7,19 +7,22 @@ no counterpart of this file (eager PyTorch); this is the MI355X answer to its st
 
 `GraphedStep(model, optimizer)` runs the first iterations of every input signature eagerly, then captures
 
-  graph 1: [bump the dropout step word] -> layout change -> backbone -> heads -> fused labels + losses -> backward
+  graph 1: [bump the dropout step word] -> layout change -> backbone -> heads -> fused labels + losses
+           [-> narration SSL: encoder, poolings, memory-bank ring update, InfoNCE] -> backward
   graph 2: global-norm clip coefficient -> fused AdamW / SGD update (+ max|w| partials for the next weight packs)
 
 and from then on an iteration is: copy the batch into the static input buffers, replay 1, (eager work the caller wants
 between backward and update: a gradient all-reduce, an EWC / MAS penalty), hand the learning rates over, replay 2.
 What must differ between replays lives in device memory: the inputs, the dropout step word (common.h: vilco_step_seed),
 the stochastic-depth factors (torch's graph-safe Philox draw, captured), the loss-normaliser EMA, the optimizer's step
-counts and learning rates (vilco_optim_step_dev).
+counts and learning rates (vilco_optim_step_dev), the narration memory bank and its ring word (csrc/ssl.hip: the update
+advances the word on the device by the number of narrated clips, which differs from batch to batch).
 
 What is captured is what ran: graphs are keyed by the input shapes, task id and the identity / requires_grad of every
 parameter, and dropped when parameters were written from outside (load_state_dict, an eager optimizer step) -- cached
 operand planes and max|w| partials would be stale otherwise.  Steps the device half cannot run alone (distillation
-against host-side logits, narration SSL, BiC) fall back to the eager path.
+against host-side logits, BiC, narration SSL with its fused path switched off by VILCO_FUSED_SSL=0) fall back to the eager
+path.
 """
 import ctypes as C
 import gc
@@ -75,12 +78,14 @@ def _capture_kw():
 
 class GraphedStep:
     def __init__(self, model, optimizer=None, clip_grad_l2norm=-1.0, eager_steps=2, between=None, enabled=True,
-                 gt_pad=8, max_graphs=16, reducer=None, comm_in_graph=None, segments=None):
+                 gt_pad=8, max_graphs=16, reducer=None, comm_in_graph=None, segments=None, narr_pad=8):
         """optimizer: a FusedOptimizer (None: forward + backward only, gradients left in p.grad);
         eager_steps: iterations of a new signature run eagerly before its capture (>= 1 with an optimizer: the capture
         must follow an eager update, whose max|w| partials scale the captured weight packs);
         between: callable run eagerly between backward and the update of every iteration;
         gt_pad: ground-truth rows are padded to this many segments per clip so that their count does not key the graph;
+        narr_pad: the narration token block is zero-padded to a multiple of this many tokens, for the same reason (the token
+        counts travel as lengths and are unchanged);
         reducer: a dist.GradReducer -- eager iterations exchange gradients from its autograd hooks (overlapped with
         backward), replayed ones stage by stage (`segments`, below) or right after graph 1 (`reduce_now`, averaged in place);
         comm_in_graph (default: env VILCO_DP_GRAPH_COMM, off): capture the bucketed RCCL all-reduces INSIDE graph 1 -- the
@@ -96,6 +101,7 @@ class GraphedStep:
         self.model, self.optimizer, self.clip = model, optimizer, float(clip_grad_l2norm)
         self.eager_steps = max(int(eager_steps), 1 if optimizer is not None else 0)
         self.between, self.enabled, self.gt_pad, self.max_graphs = between, bool(enabled), gt_pad, int(max_graphs)
+        self.narr_pad = int(narr_pad)
         self.reducer = reducer
         self.comm_in_graph = (os.environ.get("VILCO_DP_GRAPH_COMM", "0") == "1") if comm_in_graph is None else bool(comm_in_graph)
         self.segments = _DP_SEGMENTS if segments is None else bool(segments)
@@ -125,7 +131,7 @@ class GraphedStep:
     # ------------------------------------------------------------------ one iteration
     def __call__(self, video_list, task_id=0, prev_out_cls_logits=None):
         model = self.model
-        inp = model.prepare(video_list, True, gt_pad=self.gt_pad)
+        inp = model.prepare(video_list, True, gt_pad=self.gt_pad, narr_pad=self.narr_pad)
         if not (self.enabled and model.training and model.capturable(inp, task_id, prev_out_cls_logits)):
             return self._eager(inp, video_list, task_id, prev_out_cls_logits)
         key = (inp.signature(), int(task_id), self._param_sig(), int(model.n_known > 0), ops.arithmetic_key())
@@ -154,7 +160,7 @@ class GraphedStep:
         eager before the first replayed step (bench.py, N > 1): a capture that fails on one rank only would leave the ranks
         issuing different collectives.  False also when the step is not capturable; the signature then stays eager."""
         model = self.model
-        inp = model.prepare(video_list, True, gt_pad=self.gt_pad)
+        inp = model.prepare(video_list, True, gt_pad=self.gt_pad, narr_pad=self.narr_pad)
         if not (self.enabled and model.training and model.capturable(inp, task_id, None)):
             return False
         if self.reducer is not None and self.reducer.enabled and self.reducer.planned() is None:

@@ -53,29 +53,45 @@ class BiasLayer(nn.Module):
 
 
 class MemoryBank:
-    """ring buffer of narration embeddings for the SSL loss (meta_archs.py:38-60)."""
+    """ring buffer of narration embeddings for the SSL loss (meta_archs.py:38-60).  The write position lives on the device
+    (`ring`, int32[1]): the fused SSL path advances it by a data-dependent count inside a launch, so a replayed step carries
+    it; `ptr` reads it back (and waits for the device, like PtTransformer.loss_normalizer)."""
 
     def __init__(self, size, feature_dim, device=None):
         self.size, self.feature_dim = size, feature_dim
         self.memory = torch.randn(size, feature_dim, device=device if device is not None else "cuda")
-        self.ptr = 0
+        self.ring = torch.zeros(1, dtype=torch.int32, device=self.memory.device)
+
+    @property
+    def ptr(self):
+        return int(self.ring.item())
+
+    @ptr.setter
+    def ptr(self, v):
+        self.ring.fill_(int(v))
 
     @torch.no_grad()
     def update(self, features):
         n = features.size(0)
         assert n <= self.size, "Batch size must be less than or equal to memory bank size"
-        end = self.ptr + n
+        ptr = self.ptr                       # one read of the device word per update
+        end = ptr + n
         if end <= self.size:
-            self.memory[self.ptr:end] = features
+            self.memory[ptr:end] = features
             self.ptr = end
         else:
-            head = self.size - self.ptr
-            self.memory[self.ptr:] = features[:head]
+            head = self.size - ptr
+            self.memory[ptr:] = features[:head]
             self.memory[:end - self.size] = features[head:]
             self.ptr = end - self.size
 
     def get_all(self):
         return self.memory
+
+    @torch.no_grad()
+    def update_masked(self, features, mask):
+        """rows of `features` [B, D] whose mask [B] is non-zero, in batch order, without a host read (ops.ssl_ring_update)"""
+        ops.ssl_ring_update(features.detach(), mask.to(torch.float32), self.memory, self.ring)
 
 
 class Adapter(nn.Module):
@@ -276,12 +292,15 @@ class PtTransformerRegHead(_ConvHead):
 
 class StepInputs:
     """device-resident inputs of one step (PtTransformer.prepare): feats_cf [B,Cin,T], lens int32 [B], text_cf
-    [B,Ctxt,L], text_lens int32 [B], gt float [B, 3*Nmax+1] (training), narr = narration tuple or None"""
-    __slots__ = ("feats_cf", "lens", "T", "text_cf", "text_lens", "narr", "gt")
+    [B,Ctxt,L], text_lens int32 [B], gt float [B, 3*Nmax+1] (training); the narration inputs of the fused SSL path:
+    narr_cf [B,Cn,n_pad] tokens, narr_lens int32 [B] token counts, narr_mask float [B] (the clip has a narration); narr =
+    the unfused path's narration tuple or None"""
+    __slots__ = ("feats_cf", "lens", "T", "text_cf", "text_lens", "narr", "gt", "narr_cf", "narr_lens", "narr_mask")
 
     def tensors(self):
         """(name, tensor) of every device buffer a replayed step reads"""
-        return [(k, getattr(self, k)) for k in ("feats_cf", "lens", "text_cf", "text_lens", "gt") if getattr(self, k) is not None]
+        return [(k, getattr(self, k)) for k in ("feats_cf", "lens", "text_cf", "text_lens", "gt", "narr_cf", "narr_lens",
+                                                "narr_mask") if getattr(self, k, None) is not None]
 
     def signature(self):
         return tuple((k, tuple(t.shape)) for k, t in self.tensors()) + (("narr", self.narr is not None),)
@@ -376,6 +395,7 @@ class PtTransformer(nn.Module):
         self.loss_normalizer = t['init_loss_norm']     # EMA, not checkpointed (:611); a device scalar in the sync-free path
         self.sync_free_loss = os.environ.get("VILCO_SYNC_FREE_LOSS", "1") != "0"
         self.fused_loss = os.environ.get("VILCO_FUSED_LOSS", "1") != "0"      # ops.mq_loss (0: tensor expressions)
+        self.fused_ssl = os.environ.get("VILCO_FUSED_SSL", "1") != "0"        # ops.ssl_pool / ssl_nce (0: tensor expressions)
         self.loss_normalizer_momentum = 0.9
         self.reg_params = {}
 
@@ -494,9 +514,21 @@ class PtTransformer(nn.Module):
         batched, lens, narr = self._query_batch_cf(video_list, padding_val)
         return ops.transpose(batched), lens, narr
 
+    def _ssl_fused(self, batch=1):
+        """narration SSL through ops.ssl_pool / ops.ssl_nce: no host read, no boolean indexing, the ring pointer on the device.
+        A batch outside the kernels' limits (include/vilco_hip.h: 1 <= B <= 64, B <= the bank's rows, D % 4 == 0, D <= 4096)
+        takes the tensor-expression branch, as with VILCO_FUSED_SSL=0."""
+        if not (self.narration_ssl and self.fused_ssl and self.sync_free_loss):
+            return False
+        M, D = self._memory_bank_cfg
+        return 1 <= batch <= min(64, M) and D % 4 == 0 and D <= 4096
+
     @torch.no_grad()
-    def _query_batch_cf(self, video_list, padding_val=0.0):
-        """-> (batched [B,768,Lmax] channel-first on device, lens int32 [B], narration tuple or None)"""
+    def _query_batch_cf(self, video_list, padding_val=0.0, narr_pad=8):
+        """-> (batched [B,768,Lmax] channel-first on device, lens int32 [B], narration or None).  Narration: the tuple
+        (tokens [B,Cn,n], m0 [B], m1 [B,1,n]) of the reference, or on the fused path the dict cf = tokens [B,Cn,n_pad]
+        (zero-filled, n padded to a multiple of narr_pad so that the token count does not key a graph per batch), lens =
+        int32 [B] token counts, mask = float [B]."""
         feats = [x['prompt_feature'] for x in video_list]
         lens_h = [f.shape[-1] for f in feats]
         dev = self.device
@@ -505,7 +537,16 @@ class PtTransformer(nn.Module):
             dst[..., :f.shape[-1]].copy_(f, non_blocking=True)
         lens = self._h2d(torch.as_tensor(lens_h, dtype=torch.int32))
         narr = None
-        if self.training and self.narration_ssl:
+        if self.training and self._ssl_fused(len(video_list)):
+            nf = [x['narration_feats'] for x in video_list]
+            nl = [f.shape[-1] for f in nf]
+            pad = max(int(narr_pad or 1), 1)
+            nb = torch.zeros((len(nf), nf[0].shape[0], (max(nl) + pad - 1) // pad * pad), dtype=torch.float32, device=dev)
+            for f, dst in zip(nf, nb):
+                dst[..., :f.shape[-1]].copy_(f, non_blocking=True)
+            narr = {'cf': nb, 'lens': self._h2d(torch.as_tensor(nl, dtype=torch.int32)),
+                    'mask': self._h2d(torch.tensor([float(x['narration_mask']) for x in video_list], dtype=torch.float32))}
+        elif self.training and self.narration_ssl:
             nf = [x['narration_feats'] for x in video_list]
             nl = [f.shape[-1] for f in nf]
             nb = torch.full((len(nf), nf[0].shape[0], max(nl)), padding_val, dtype=torch.float32, device=dev)
@@ -540,16 +581,22 @@ class PtTransformer(nn.Module):
             host = host.pin_memory()
         return host.to(dev, non_blocking=True)
 
-    def prepare(self, video_list, is_training=True, gt_pad=None):
+    def prepare(self, video_list, is_training=True, gt_pad=None, narr_pad=8):
         """Everything `forward` takes from the clip dictionaries, as device tensors: the host half of the step (padding,
         H2D copies, the ground-truth table).  `forward_prepared` is the device half -- no host reads, no H2D copies, so a
         training step over a `StepInputs` can be captured as a hipGraph and replayed over refreshed buffers
         (vilco_amd/graph.py).  The channel-first -> token-major layout change is part of the device half."""
         inp = StepInputs()
         inp.feats_cf, inp.lens, inp.T = self._batch_cf(video_list, is_training)
-        inp.text_cf = inp.text_lens = inp.narr = None
+        inp.text_cf = inp.text_lens = inp.narr = inp.narr_cf = inp.narr_lens = inp.narr_mask = None
         if self.use_cross_modal:
-            inp.text_cf, inp.text_lens, inp.narr = self._query_batch_cf(video_list)
+            inp.text_cf, inp.text_lens, narr = self._query_batch_cf(video_list, narr_pad=narr_pad)
+            if isinstance(narr, dict):
+                inp.narr_cf, inp.narr_lens, inp.narr_mask = narr['cf'], narr['lens'], narr['mask']
+                if self.memory_bank is None:       # before any capture: the bank is state, not a buffer of one step
+                    self.memory_bank = MemoryBank(*self._memory_bank_cfg, device=self.device)
+            else:
+                inp.narr = narr
             assert inp.text_cf.shape[0] == inp.feats_cf.shape[0], \
                 "every clip of the batch needs labels (the reference drops unlabelled clips from the video batch only)"
         inp.gt = None
@@ -586,11 +633,13 @@ class PtTransformer(nn.Module):
 
     def capturable(self, inp, task_id=-1, prev_out_cls_logits=None):
         """can forward_prepared(inp, None, task_id) + backward run without touching the host?  (the fused label / loss
-        kernels, a fixed prompt window, no narration SSL -- whose memory-bank update reads a device flag --, no
-        distillation against host-side logits)"""
+        kernels, a fixed prompt window, narration SSL only on its fused path -- the unfused one reads the mask sum and
+        keeps the ring pointer on the host --, no distillation against host-side logits)"""
         if not (self.fused_loss and self.sync_free_loss and self.train_loss_weight > 0 and self.num_classes <= 128):
             return False
-        if inp.gt is None or (self.training and self.narration_ssl) or prev_out_cls_logits:
+        if inp.gt is None or prev_out_cls_logits:
+            return False
+        if self.training and self.narration_ssl and inp.narr_cf is None:
             return False
         if self.n_known > 0 and self.cl_name in ('bic', 'icarl'):
             return False
@@ -629,7 +678,12 @@ class PtTransformer(nn.Module):
         fpn_feats, fpn_lens, out_cls_logits, out_offsets = self._run_network(x_tm, lens, text_tm, text_lens,
                                                                             raw_offsets=fused)
 
-        if self.training and self.narration_ssl:
+        # the fused loss writes the memory bank and advances its ring word: only where the loss is consumed (the reference
+        # touches the bank inside the training-loss branch, :939-945 -- not in a get_emb pass such as cache_prev_logits')
+        ssl_fused = bool(self.training and inp.narr_cf is not None and is_training and not get_emb)
+        if ssl_fused:
+            ssl_loss = self._fused_ssl_loss(fpn_feats, fpn_lens, inp)
+        elif self.training and self.narration_ssl and inp.narr_cf is None:
             narration_feats, video_feats = self._ssl_embeddings(fpn_feats, fpn_lens, narr)
 
         level_T = [f.shape[1] for f in fpn_feats]
@@ -668,11 +722,18 @@ class PtTransformer(nn.Module):
                 losses = self.losses(fpn_masks, out_cls_logits, out_offsets, gt_cls, gt_off, label_list=gt_labels,
                                      normal_probs_cls=np_cls, normal_probs_reg=np_reg,
                                      prev_out_cls_logits=prev_out_cls_logits, reduce_sim=reduce_sim)
-            if self.narration_ssl and narr[1].sum() > 0:
+            if ssl_fused:
+                # always present on this path, an exact 0 when no clip of the batch has a narration (the reference leaves
+                # the key out there: the sum is the same)
+                losses["final_loss"] = losses["final_loss"] + self.ssl_factor * ssl_loss
+                losses["ssl_loss"] = self.ssl_factor * ssl_loss
+            elif self.narration_ssl and narr is not None and narr[1].sum() > 0:
                 m0 = narr[1].to(torch.bool)
                 self.memory_bank.update(narration_feats[m0])
                 ssl_loss = self.masked_contrastive_loss(narration_feats, video_feats, m0)
-                losses["final_loss"] += self.ssl_factor * ssl_loss
+                # (not in place: with the fused loss kernel final_loss is one of several views of its output, which autograd
+                # refuses to modify -- the reference's `+=` raised on this path)
+                losses["final_loss"] = losses["final_loss"] + self.ssl_factor * ssl_loss
                 losses["ssl_loss"] = self.ssl_factor * ssl_loss
             return losses
 
@@ -688,6 +749,19 @@ class PtTransformer(nn.Module):
             parts.append(self.list_bias_layers[i](logits[..., lo:hi]))
             lo = hi
         return torch.cat(parts, dim=-1)
+
+    def _fused_ssl_loss(self, fpn_feats, fpn_lens, inp):
+        """meta_archs.py:794-811 + 939-945 + 1351-1372 on the device: the narration encoder over the token-major tokens,
+        both masked mean poolings (ops.ssl_pool), then normalisation, the bank's ring update and InfoNCE (ops.ssl_nce)"""
+        if self.memory_bank is None:
+            self.memory_bank = MemoryBank(*self._memory_bank_cfg, device=self.device)
+        enc = self.narration_encoder
+        tokens = ops.linear(ops.transpose(inp.narr_cf), enc.weight, enc.bias)                  # [B, n_pad, D]
+        text = ops.ssl_pool([tokens], inp.narr_lens.reshape(-1, 1))
+        level_len = torch.stack([l.to(torch.int32) for l in fpn_lens], dim=1).contiguous()     # as _fused_losses' table
+        video = ops.ssl_pool(list(fpn_feats), level_len)
+        bank = self.memory_bank
+        return ops.ssl_nce(text, video, inp.narr_mask, bank.memory, bank.ring)[0]
 
     def _ssl_embeddings(self, fpn_feats, fpn_lens, narr):
         """masked mean pooling of narration / pyramid features (meta_archs.py:794-811)."""

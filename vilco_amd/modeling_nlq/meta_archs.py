@@ -101,6 +101,7 @@ class PtTransformer(mq.PtTransformer):
         self.loss_normalizer = t['init_loss_norm']
         self.sync_free_loss = os.environ.get("VILCO_SYNC_FREE_LOSS", "1") != "0"
         self.fused_loss = os.environ.get("VILCO_FUSED_LOSS", "1") != "0"
+        self.fused_ssl = os.environ.get("VILCO_FUSED_SSL", "1") != "0"
         self.loss_normalizer_momentum = 0.9
         self.reg_params = {}
 
@@ -154,16 +155,16 @@ class PtTransformer(mq.PtTransformer):
         vl = [x if 'labels' in x else dict(x, labels=[0]) for x in video_list]      # NLQ batches every clip (:923)
         return super()._batch_cf(vl, is_training, padding_val)
 
-    def _query_batch_cf(self, video_list, padding_val=0.0):
+    def _query_batch_cf(self, video_list, padding_val=0.0, narr_pad=8):
         vl = [x if 'prompt_feature' in x else dict(x, prompt_feature=x['query_feats']) for x in video_list]
-        return super()._query_batch_cf(vl, padding_val)
+        return super()._query_batch_cf(vl, padding_val, narr_pad)
 
-    def prepare(self, video_list, is_training=True, gt_pad=None):
+    def prepare(self, video_list, is_training=True, gt_pad=None, narr_pad=8):
         """the host half of the step (PtTransformer.prepare) over NLQ's batch dictionaries: class indices come from the
         one-hot rows, the text from `query_feats` -- also what vilco_amd.graph.GraphedStep calls"""
         if self.training and is_training and video_list and 'labels' not in video_list[0]:
             video_list = self._with_labels(video_list)
-        return super().prepare(video_list, is_training, gt_pad)
+        return super().prepare(video_list, is_training, gt_pad, narr_pad)
 
     def add_samples_to_mem(self, cilsettask, data, m):
         if self.type_sampling == 'herding':       # the pyramid descriptor path is only held to a contract on the MQ model

@@ -2216,3 +2216,126 @@ def qkv_pre(x, ln1, convs, norms, lens, stride, want_h, skip=False):
         for j in range(3):
             _tag_amax(outs[j], parts[j], n)
     return outs
+
+
+# ---------------------------------------------------------------------------------------- narration SSL (csrc/ssl.hip)
+def _ptr_table(ts):
+    return (_lib.c_fp * len(ts))(*[t.data_ptr() for t in ts])
+
+
+class _SslPool(torch.autograd.Function):
+    """masked mean over time of every level, averaged over the levels (vilco_ssl_pool_fwd / _bwd)"""
+
+    @staticmethod
+    def forward(ctx, lens, *feats):
+        _chk(*feats)
+        lib = _lib.load()
+        B, _, Cn = feats[0].shape
+        L = len(feats)
+        T = (_lib.i32 * L)(*[int(f.shape[1]) for f in feats])
+        out = torch.empty(B, Cn, dtype=torch.float32, device=feats[0].device)
+        nws = lib.vilco_ssl_pool_workspace(T, L, B, Cn)
+        ws = _ws(nws, out.device)
+        _lib.check(lib.vilco_ssl_pool_fwd(_ptr_table(feats), T, L, lens.data_ptr(), B, Cn, out.data_ptr(), ws.data_ptr(), nws,
+                                          _stream()))
+        ctx.T, ctx.shapes, ctx.lens = T, [f.shape for f in feats], lens
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        dout = dout.contiguous()
+        grads = [torch.empty(s, dtype=torch.float32, device=dout.device) for s in ctx.shapes]
+        B, _, Cn = ctx.shapes[0]
+        _lib.check(_lib.load().vilco_ssl_pool_bwd(dout.data_ptr(), _ptr_table(grads), ctx.T, len(grads), ctx.lens.data_ptr(),
+                                                  B, Cn, _stream()))
+        return (None,) + tuple(grads)
+
+
+def ssl_pool(feats, lens):
+    """feats: list of L <= 16 token-major fp32 [B, T_l, C]; lens: int32 [B, L] prefix lengths on the device ->
+    [B, C] = mean over levels of the mean over the rows below the length (0 for an empty level).  meta_archs.py:794-811."""
+    if not 1 <= len(feats) <= 16:
+        raise RuntimeError("ssl_pool takes 1 to 16 levels, got %d" % len(feats))
+    B, Cn = feats[0].shape[0], feats[0].shape[2]
+    if any(f.dim() != 3 or f.shape[0] != B or f.shape[2] != Cn for f in feats):
+        raise RuntimeError("ssl_pool: every level must be [B, T_l, C] with the same B and C")
+    if lens.dtype != torch.int32 or tuple(lens.shape) != (B, len(feats)) or not lens.is_cuda or not lens.is_contiguous():
+        raise RuntimeError("ssl_pool: lens must be a contiguous int32 [B, L] device tensor")
+    return _SslPool.apply(lens, *[f.contiguous() for f in feats])
+
+
+class _SslNce(torch.autograd.Function):
+    """normalise -> ring update of the memory bank -> InfoNCE (vilco_ssl_nce_fwd / _bwd)"""
+
+    @staticmethod
+    def forward(ctx, text, video, mask, bank, ring, temperature):
+        _chk(text, video, mask, bank)
+        lib = _lib.load()
+        B, D = text.shape
+        M = bank.shape[0]
+        dev = text.device
+        xn = torch.empty(2, B, D, dtype=torch.float32, device=dev)
+        stats = torch.empty(7 * B, dtype=torch.float32, device=dev)
+        logits = torch.empty(2 * B, M, dtype=torch.float64, device=dev)
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        nws = lib.vilco_ssl_nce_workspace(B, D, M)
+        ws = _ws(nws, dev)
+        _lib.check(lib.vilco_ssl_nce_fwd(text.data_ptr(), video.data_ptr(), mask.data_ptr(), B, D, bank.data_ptr(), M,
+                                         ring.data_ptr(), temperature, xn.data_ptr(), stats.data_ptr(), logits.data_ptr(),
+                                         loss.data_ptr(), ws.data_ptr(), nws, _stream()))
+        ctx.temperature, ctx.bank = temperature, bank           # (the bank is not an autograd input's value: no version check)
+        ctx.save_for_backward(mask, xn, stats, logits)
+        ctx.mark_non_differentiable(xn)
+        return loss[0], xn
+
+    @staticmethod
+    def backward(ctx, gloss, _gxn):
+        mask, xn, stats, logits = ctx.saved_tensors
+        lib = _lib.load()
+        _, B, D = xn.shape
+        bank = ctx.bank
+        M = bank.shape[0]
+        gloss = gloss.contiguous().float().reshape(1)
+        dt = torch.empty(B, D, dtype=torch.float32, device=xn.device)
+        dv = torch.empty(B, D, dtype=torch.float32, device=xn.device)
+        nws = lib.vilco_ssl_nce_workspace(B, D, M)
+        ws = _ws(nws, xn.device)
+        _lib.check(lib.vilco_ssl_nce_bwd(gloss.data_ptr(), mask.data_ptr(), xn.data_ptr(), stats.data_ptr(), logits.data_ptr(),
+                                         bank.data_ptr(), B, D, M, ctx.temperature, dt.data_ptr(), dv.data_ptr(), ws.data_ptr(),
+                                         nws, _stream()))
+        return dt, dv, None, None, None, None
+
+
+def _ssl_bank_args(rows, mask, bank, ring):
+    B, D = rows.shape
+    if tuple(mask.shape) != (B,) or bank.dim() != 2 or bank.shape[1] != D:
+        raise RuntimeError("narration SSL: rows [B, D], mask [B] and bank [M, D] do not fit together")
+    if D % 4 or D > 4096 or not 1 <= B <= 64 or B > bank.shape[0]:
+        raise RuntimeError("narration SSL: need D %% 4 == 0, D <= 4096, 1 <= B <= 64 and B <= the bank's size "
+                           "(B = %d, D = %d, M = %d)" % (B, D, bank.shape[0]))
+    if ring.dtype != torch.int32 or ring.numel() != 1 or not ring.is_cuda:
+        raise RuntimeError("narration SSL: the ring word is a device int32[1]")
+
+
+def ssl_nce(text, video, mask, bank, ring, temperature=0.07):
+    """raw pooled text / video [B, D], mask float [B], bank [M, D] and ring word int32[1] (both updated in place) ->
+    (loss, normalised rows [2, B, D]).  meta_archs.py:38-60, 939-945, 1351-1372; include/vilco_hip.h has the definition.
+    The backward reads the bank as the forward left it (its rows are constants of the loss and are not saved a second time):
+    run each call's backward before the next call that writes the same bank, as a training step does.  The bank is not an
+    autograd input, so autograd does not police this -- two forwards followed by two backwards give the first one the
+    second one's negatives."""
+    text, video, mask = text.contiguous(), video.contiguous(), mask.contiguous()
+    if text.shape != video.shape or text.dim() != 2:
+        raise RuntimeError("ssl_nce: text and video must both be [B, D]")
+    _chk(text, mask, bank)
+    _ssl_bank_args(text, mask, bank, ring)
+    return _SslNce.apply(text, video, mask, bank, ring, float(temperature))
+
+
+def ssl_ring_update(rows, mask, bank, ring):
+    """the bank's masked ring update alone: rows [B, D] (already normalised) with mask != 0 go to (ring + rank) mod M"""
+    rows, mask = rows.contiguous(), mask.contiguous()
+    _chk(rows, mask, bank)
+    _ssl_bank_args(rows, mask, bank, ring)
+    _lib.check(_lib.load().vilco_ssl_ring_update(rows.data_ptr(), mask.data_ptr(), rows.shape[0], rows.shape[1],
+                                                 bank.data_ptr(), bank.shape[0], ring.data_ptr(), _stream()))
