@@ -36,6 +36,8 @@ enum vilco_status {
 const char* vilco_status_str(int status);
 /* library / target identification: "vilco_hip <ver> gfx950" */
 const char* vilco_version(void);
+/* sizeof of a struct of this header by its name ("vilco_gemm_desc", ...), 0 for an unknown name: lets a binding check its mirror */
+size_t vilco_abi_sizeof(const char* struct_name);
 
 /* ------------------------------------------------------------------------------------------ */
 /* GEMM family: every 1x1 conv, k=3 conv, nn.Linear, einsum projection and (round 1) the        */
@@ -174,7 +176,7 @@ typedef struct vilco_pack_item {
   /* src[i][p - rows + i] or 0): the adjoint of rel_shift_bnij, so dS feeds the position-term gradients directly  */
   int32_t relshift;
   /* optional (precision 3): `namax` partial maxima of |src| already on the device -- left by the kernel that produced  */
-  /* src (vilco_layernorm_fwd_amax, vilco_act_bwd_amax, vilco_qkv_pre_fwd) -- so the pack needs no amax launch          */
+  /* src (vilco_layernorm_fwd, vilco_act_bwd, vilco_qkv_pre_fwd: their amax_parts) -- so the pack needs no amax launch  */
   const float* amax;
   int32_t namax;
   /* seq_len = T > 0: src is rows / T token sequences of T rows (cols % 8 == 0) and the planes are the image the k=3 convs   */
@@ -192,47 +194,66 @@ int vilco_pack_many(const vilco_pack_item* items, int32_t n, int32_t precision, 
 /* inside sqrt) and the stock nn.LayerNorm calls (blocks.py:446-451, modeling_xlnet_x.py:236,473). */
 /* relu=1 fuses the ReLU that follows every embed/head LN (backbones.py:219, meta_archs.py:270).  */
 /* ------------------------------------------------------------------------------------------ */
-int vilco_layernorm_fwd(const float* x, const float* gamma, const float* beta, float* y,
-                        float* mean, float* rstd, int64_t rows, int32_t C, float eps,
-                        int32_t relu, void* stream);
-/* the same, and the kernel also leaves *n_parts per-block partial maxima of |y| in amax_parts (device, >= 2048 floats): */
-/* the operand pack of y (vilco_pack_item.amax) then needs no separate pass over it                                     */
-int vilco_layernorm_fwd_amax(const float* x, const float* gamma, const float* beta, float* y,
-                             float* mean, float* rstd, int64_t rows, int32_t C, float eps,
-                             int32_t relu, float* amax_parts, int32_t* n_parts, void* stream);
-/* the same, and y also written by the kernel as the fp16 x2 operand planes (precision 3) of the product that consumes it: */
-/* seq_len = 0: vilco_pack's layout for [rows][C] (C % 32 == 0); seq_len = T > 0: the k=3 convs' zero-padded per-sequence    */
-/* image (vilco_pack_item.seq_len; C % 8 == 0, rows % T == 0).  `planes`: device, 256-byte aligned,                           */
-/* vilco_layernorm_planes_bytes() long (= vilco_pack_bytes / vilco_pack_item_bytes of the same tensor).  The planes' scale    */
-/* comes from the bound max|gamma| sqrt(C) + max|beta| >= max|y| instead of the exact maximum: no pass over y, no pack launch. */
-/* row_mask (optional, with or without planes): y[row][:] *= row_mask[row % mask_rows] -- the zero separator rows of the heads' */
-/* concatenated pyramid levels (meta_archs.py:216-235 runs the shared head per level); with relu = 1 and a 0 / 1 mask          */
-/* vilco_layernorm_bwd needs no mask of its own: it already drops the gradient wherever the saved y is 0.                        */
+/* Forward.  Zero-initialise, set what the call uses; a null / 0 field = that part off. */
+typedef struct vilco_ln_fwd_desc {
+  const float* x;        /* [rows][C] */
+  const float* gamma;    /* [C] or NULL */
+  const float* beta;     /* [C] or NULL */
+  float* y;              /* [rows][C] */
+  float* mean;           /* [rows], kept for backward; NULL: not wanted */
+  float* rstd;           /* [rows], likewise */
+  int64_t rows;
+  int32_t C;
+  float eps;
+  int32_t relu;
+  /* optional: the kernel also leaves *n_parts per-block partial maxima of |y| in amax_parts (device, >= 2048 floats): the operand */
+  /* pack of y (vilco_pack_item.amax) then needs no separate pass over it.  n_parts: HOST int32, written by the call.              */
+  float* amax_parts;
+  int32_t* n_parts;
+  /* optional: y also written by the kernel as the fp16 x2 operand planes (precision 3) of the product that consumes it:           */
+  /* seq_len = 0: vilco_pack's layout for [rows][C] (C % 32 == 0); seq_len = T > 0: the k=3 convs' zero-padded per-sequence image   */
+  /* (vilco_pack_item.seq_len; C % 8 == 0, rows % T == 0).  `planes`: device, 256-byte aligned, vilco_layernorm_planes_bytes() long */
+  /* (= vilco_pack_bytes / vilco_pack_item_bytes of the same tensor).  The planes' scale comes from the bound                       */
+  /* max|gamma| sqrt(C) + max|beta| >= max|y| instead of the exact maximum: no pass over y, no pack launch.                         */
+  void* planes;
+  size_t planes_bytes;
+  int32_t seq_len;
+  /* optional (with or without planes): y[row][:] *= row_mask[row % mask_rows] -- the zero separator rows of the heads' concatenated */
+  /* pyramid levels (meta_archs.py:216-235 runs the shared head per level); with relu = 1 and a 0 / 1 mask vilco_layernorm_bwd needs  */
+  /* no mask of its own: it already drops the gradient wherever the saved y is 0.                                                     */
+  const float* row_mask;
+  int64_t mask_rows;
+} vilco_ln_fwd_desc;
 size_t vilco_layernorm_planes_bytes(int64_t rows, int32_t C, int32_t seq_len);
-int vilco_layernorm_fwd_planes(const float* x, const float* gamma, const float* beta, float* y,
-                               float* mean, float* rstd, int64_t rows, int32_t C, float eps,
-                               int32_t relu, float* amax_parts, int32_t* n_parts, void* planes, size_t planes_bytes,
-                               int32_t seq_len, const float* row_mask, int64_t mask_rows, void* stream);
+int vilco_layernorm_fwd(const vilco_ln_fwd_desc* d, void* stream);
+
+typedef struct vilco_ln_bwd_desc {
+  const float* dy;       /* [rows][C] */
+  const float* x;
+  const float* y;        /* forward output: only read when relu = 1 */
+  const float* gamma;
+  const float* mean;
+  const float* rstd;
+  /* optional ([rows][C]): dx = LayerNorm backward + dres -- the gradient that reaches x over the residual connection around the   */
+  /* branch this LayerNorm opens (blocks.py:571-590: x + drop_path(attn(ln1(x))), out + drop_path(mlp(ln2(out)))): the sum         */
+  /* autograd would form with a kernel of its own.                                                                                 */
+  const float* dres;
+  float* dx;
+  float* dgamma;         /* [C], overwritten; dgamma and dbeta both set or both NULL */
+  float* dbeta;
+  int64_t rows;
+  int32_t C;
+  int32_t relu;
+  void* workspace;       /* vilco_layernorm_bwd_workspace() bytes */
+  size_t workspace_bytes;
+  /* optional (round 6): partial maxima of |dx| (device, >= 2048 floats; *n_parts, HOST int32 = how many were written): dx is the  */
+  /* output gradient of the layer in front of the LayerNorm, whose mask / activation-backward kernel turns it into operand planes   */
+  /* (vilco_act_bwd_desc.planes) from that bound.                                                                                   */
+  float* dx_amax_parts;
+  int32_t* n_parts;
+} vilco_ln_bwd_desc;
 size_t vilco_layernorm_bwd_workspace(int64_t rows, int32_t C);
-/* y (forward output) is only read when relu=1.  dgamma/dbeta are overwritten. */
-int vilco_layernorm_bwd(const float* dy, const float* x, const float* y, const float* gamma,
-                        const float* mean, const float* rstd, float* dx, float* dgamma,
-                        float* dbeta, int64_t rows, int32_t C, int32_t relu, void* workspace,
-                        size_t workspace_bytes, void* stream);
-/* dres (optional, [rows][C]): dx = LayerNorm backward + dres -- the gradient that reaches x over the residual connection  */
-/* around the branch this LayerNorm opens (blocks.py:571-590: x + drop_path(attn(ln1(x))), out + drop_path(mlp(ln2(out)))): */
-/* the sum autograd would form with a kernel of its own.  NULL: exactly vilco_layernorm_bwd.                               */
-int vilco_layernorm_bwd_res(const float* dy, const float* x, const float* y, const float* gamma,
-                            const float* mean, const float* rstd, const float* dres, float* dx, float* dgamma,
-                            float* dbeta, int64_t rows, int32_t C, int32_t relu, void* workspace,
-                            size_t workspace_bytes, void* stream);
-/* Round 6: the same + partial maxima of |dx| (dx_amax_parts: device, >= 2048 floats; *n_parts = how many were written): dx is the
- * output gradient of the layer in front of the LayerNorm, whose mask / activation-backward kernel turns it into operand planes
- * (vilco_act_bwd_planes / _seq) from that bound. */
-int vilco_layernorm_bwd_res_amax(const float* dy, const float* x, const float* y, const float* gamma,
-                                 const float* mean, const float* rstd, const float* dres, float* dx, float* dgamma,
-                                 float* dbeta, int64_t rows, int32_t C, int32_t relu, void* workspace,
-                                 size_t workspace_bytes, float* dx_amax_parts, int32_t* n_parts, void* stream);
+int vilco_layernorm_bwd(const vilco_ln_bwd_desc* d, void* stream);
 
 /* ------------------------------------------------------------------------------------------ */
 /* Depthwise k=3 conv, stride 1|2, zero pad 1, no bias, output masked: MaskedMHCA's query/key/   */
@@ -300,40 +321,60 @@ typedef struct vilco_attn_amax_in {
   const float* v; int32_t nv;
   const float* dout; int32_t ndo;       /* backward only */
 } vilco_attn_amax_in;
-/* workspace = 16-bit operand planes (q, k natural; v transposed, or natural on the hd = 64 fast path), built inside
- * the call by the pack kernels; amax_in (may be null): see above; o_amax / d*_amax: see vilco_attn_amax_parts (null = not wanted) */
+/* One descriptor for both directions (zero-initialise; forward ignores the backward-only fields). */
+typedef struct vilco_attn_desc {
+  const float* q;        /* [B,Tq,H*hd] */
+  const float* k;        /* [B,Tk,H*hd] */
+  const float* v;
+  const float* bias;     /* [B,H,Tq,Tk] or NULL */
+  const int32_t* kv_len; /* [B]; may be NULL in mask mode 2 */
+  float* o;              /* forward: output; backward: the forward's output (read) */
+  float* lse;            /* [B,H,Tq]: written by forward, read by backward */
+  int32_t B, H, Tq, Tk, hd;
+  float scale;
+  int32_t mode, window, precision;
+  float drop_p;
+  uint32_t drop_seed;
+  const vilco_attn_amax_in* amax_in;   /* may be NULL: see above */
+  /* workspace = 16-bit operand planes (q, k natural; v transposed, or natural on the hd = 64 fast path), built inside the call by  */
+  /* the pack kernels; vilco_attn_fwd_workspace() / vilco_attn_bwd_workspace() bytes                                                */
+  void* workspace;
+  size_t workspace_bytes;
+  /* forward only */
+  float* o_amax;         /* see vilco_attn_amax_parts (NULL = not wanted) */
+  /* optional: o also written as the fp16 x2 operand planes (vilco_pack's layout for [B * Tq][H * hd], precision 3, vilco_pack_bytes */
+  /* long, 256-byte aligned) of the output projection -- the hd = 64 kernels only (vilco_attn_planes_supported: when                 */
+  /* vilco_attn_amax_parts(...) > 0, or XLNet's relative attention at hd = 64).  Scale from the bound max|o| <= max|v| / keep.       */
+  void* o_planes;
+  size_t o_planes_bytes;
+  /* backward only: dq / dk / dv are overwritten; dbias (optional, [B,H,Tq,Tk]) receives dS.  Deterministic (no atomics). */
+  const float* dout;
+  float* dq;
+  float* dk;
+  float* dv;
+  float* dbias;
+  float* dq_amax;        /* see vilco_attn_amax_parts (NULL = not wanted) */
+  float* dk_amax;
+  float* dv_amax;
+  float* dbias_amax;
+  /* optional (round 5), XLNet's relative attention (mask mode 3, hd = 64, precision 3, Tq = Tk): the backward writes dS -- the      */
+  /* gradient of the position scores, modeling_xlnet_x.py:256-288 -- directly as the fp16 x2 operand planes of the UNSHIFTED          */
+  /* [Tq][Tq + Tk] view (the layout vilco_pack_many gives an item with relshift = 1, nbatch = B*H), ready for the two band-limited    */
+  /* products d(qr) = d(bd) kr and d(kr) = d(bd)^T qr (vilco_gemm_desc.a_planes, band 2 / 3), instead of fp32 dS + a pack pass        */
+  /* (0.68 GB written, 0.68 GB read and 1.36 GB written again at config P).  `ds_planes`: at least vilco_attn_dsplanes_bytes(B, H,    */
+  /* Tq) bytes, 256-byte aligned, whose out-of-band columns (p < Tq - i, p >= Tq + Tk - i of row i) and padding are ZERO: the kernel  */
+  /* writes the band only, so a buffer zeroed once can be reused call after call.  `dbias` and `dbias_amax` must be NULL with it and  */
+  /* Tk a multiple of 64.                                                                                                             */
+  void* ds_planes;
+  size_t ds_planes_bytes;
+} vilco_attn_desc;
 size_t vilco_attn_fwd_workspace(int32_t B, int32_t H, int32_t Tq, int32_t Tk, int32_t hd, int32_t precision);
-int vilco_attn_fwd(const float* q, const float* k, const float* v, const float* bias,
-                   const int32_t* kv_len, float* o, float* lse, int32_t B, int32_t H, int32_t Tq,
-                   int32_t Tk, int32_t hd, float scale, int32_t mode, int32_t window, int32_t precision, float drop_p,
-                   uint32_t drop_seed, const vilco_attn_amax_in* amax_in, float* o_amax, void* workspace,
-                   size_t workspace_bytes, void* stream);
-/* the same, and o also written as the fp16 x2 operand planes (vilco_pack's layout for [B * Tq][H * hd], precision 3,      */
-/* vilco_pack_bytes long, 256-byte aligned) of the output projection -- the hd = 64 kernels only (when                       */
-/* vilco_attn_amax_parts(...) > 0, or XLNet's relative attention at hd = 64).  Scale from the bound max|o| <= max|v| / keep. */
 int32_t vilco_attn_planes_supported(int32_t Tq, int32_t Tk, int32_t hd, int32_t mode, int32_t precision, int32_t has_bias,
                                     float drop_p);
-int vilco_attn_fwd_planes(const float* q, const float* k, const float* v, const float* bias,
-                   const int32_t* kv_len, float* o, float* lse, int32_t B, int32_t H, int32_t Tq,
-                   int32_t Tk, int32_t hd, float scale, int32_t mode, int32_t window, int32_t precision, float drop_p,
-                   uint32_t drop_seed, const vilco_attn_amax_in* amax_in, float* o_amax, void* workspace,
-                   size_t workspace_bytes, void* o_planes, size_t o_planes_bytes, void* stream);
+int vilco_attn_fwd(const vilco_attn_desc* d, void* stream);
 size_t vilco_attn_bwd_workspace(int32_t B, int32_t H, int32_t Tq, int32_t Tk, int32_t hd, int32_t precision);
-/* dq/dk/dv are overwritten; dbias (optional, [B,H,Tq,Tk]) receives dS.  Deterministic (no atomics). */
-int vilco_attn_bwd(const float* q, const float* k, const float* v, const float* bias,
-                   const int32_t* kv_len, const float* o, const float* lse, const float* dout,
-                   float* dq, float* dk, float* dv, float* dbias, int32_t B, int32_t H, int32_t Tq,
-                   int32_t Tk, int32_t hd, float scale, int32_t mode, int32_t window, int32_t precision, float drop_p,
-                   uint32_t drop_seed, const vilco_attn_amax_in* amax_in, float* dq_amax, float* dk_amax, float* dv_amax,
-                   float* dbias_amax, void* workspace, size_t workspace_bytes, void* stream);
-/* Round 5, XLNet's relative attention (mask mode 3, hd = 64, precision 3, Tq = Tk): the backward writes dS -- the gradient  */
-/* of the position scores, modeling_xlnet_x.py:256-288 -- directly as the fp16 x2 operand planes of the UNSHIFTED            */
-/* [Tq][Tq + Tk] view (the layout vilco_pack_many gives an item with relshift = 1, nbatch = B*H), ready for the two          */
-/* band-limited products d(qr) = d(bd) kr and d(kr) = d(bd)^T qr (vilco_gemm_desc.a_planes, band 2 / 3), instead of fp32     */
-/* dS + a pack pass (0.68 GB written, 0.68 GB read and 1.36 GB written again at config P).  `ds_planes`: at least            */
-/* vilco_attn_dsplanes_bytes(B, H, Tq) bytes, 256-byte aligned, whose out-of-band columns (p < Tq - i, p >= Tq + Tk - i of   */
-/* row i) and padding are ZERO: the kernel writes the band only, so a buffer zeroed once can be reused call after call.      */
-/* `dbias` and `dbias_amax` must be NULL with it and Tk a multiple of 64.  ds_planes NULL: exactly vilco_attn_bwd.          */
+size_t vilco_attn_dsplanes_bytes(int32_t B, int32_t H, int32_t T);
+int vilco_attn_bwd(const vilco_attn_desc* d, void* stream);
 /* XLNet's position scores bd[b][h][i][p] = qr[b][i][h] . kr[(b)][p][h] for the band p in [T - i, 2T - i) of the unshifted    */
 /* [T][2T] matrix -- the part rel_shift_bnij keeps (modeling_xlnet_x.py:204-214, 256-288); the rest of bd is left unwritten.   */
 /* qr [B][T][H*hd], kr [2T][H*hd] (per_clip 0) or [B][2T][H*hd] (per_clip 1: the reference drops out the expanded position     */
@@ -343,14 +384,6 @@ int vilco_attn_bwd(const float* q, const float* k, const float* v, const float* 
 size_t vilco_xl_scores_workspace(int32_t B, int32_t H, int32_t T, int32_t per_clip);
 int vilco_xl_scores(const float* qr, const float* kr, float* bd, int32_t B, int32_t H, int32_t T, int32_t hd,
                     int32_t per_clip, int32_t precision, void* workspace, size_t workspace_bytes, void* stream);
-size_t vilco_attn_dsplanes_bytes(int32_t B, int32_t H, int32_t T);
-int vilco_attn_bwd_dsplanes(const float* q, const float* k, const float* v, const float* bias,
-                   const int32_t* kv_len, const float* o, const float* lse, const float* dout,
-                   float* dq, float* dk, float* dv, float* dbias, int32_t B, int32_t H, int32_t Tq,
-                   int32_t Tk, int32_t hd, float scale, int32_t mode, int32_t window, int32_t precision, float drop_p,
-                   uint32_t drop_seed, const vilco_attn_amax_in* amax_in, float* dq_amax, float* dk_amax, float* dv_amax,
-                   float* dbias_amax, void* workspace, size_t workspace_bytes, void* ds_planes, size_t ds_planes_bytes,
-                   void* stream);
 
 /* ------------------------------------------------------------------------------------------ */
 /* Candidate decode of PtTransformer.inference_single_video (MQ meta_archs.py:1594-1692, NLQ meta_archs.py:1253-1338)   */
@@ -376,19 +409,27 @@ int vilco_scale_add_fwd(float* out, const float* a, const float* bval, const flo
                         const float* rowscale, const int32_t* len, int32_t mask_a, int32_t B,
                         int32_t T, int32_t C, void* stream);
 size_t vilco_colsum_workspace(int64_t rows, int32_t C);
-/* da = dout*(mask_a?m:1) ; db = dout*colscale*rowscale ; dcolscale = sum_rows dout*bval*rowscale.
- * da / db / dcolscale may be null to skip. */
-int vilco_scale_add_bwd(const float* dout, const float* bval, const float* colscale,
-                        const float* rowscale, const int32_t* len, int32_t mask_a, float* da,
-                        float* db, float* dcolscale, int32_t B, int32_t T, int32_t C,
-                        void* workspace, size_t workspace_bytes, void* stream);
-/* the same + partial maxima of |db| (db_amax_parts: device, >= 2048 floats; *n_parts = how many were written): db is the upstream
- * gradient of the residual branch's last layer, whose activation-backward kernel turns it into operand planes
- * (vilco_act_bwd_planes) */
-int vilco_scale_add_bwd_amax(const float* dout, const float* bval, const float* colscale, const float* rowscale,
-                             const int32_t* len, int32_t mask_a, float* da, float* db, float* dcolscale, int32_t B,
-                             int32_t T, int32_t C, void* workspace, size_t workspace_bytes, float* db_amax_parts,
-                             int32_t* n_parts, void* stream);
+/* da = dout*(mask_a?m:1) ; db = dout*colscale*rowscale ; dcolscale = sum_rows dout*bval*rowscale. */
+typedef struct vilco_scale_add_bwd_desc {
+  const float* dout;     /* [B][T][C] */
+  const float* bval;     /* needed for dcolscale */
+  const float* colscale; /* [C] or NULL */
+  const float* rowscale; /* [B] or NULL */
+  const int32_t* len;    /* [B] or NULL */
+  int32_t mask_a;
+  float* da;             /* da / db / dcolscale may be NULL to skip */
+  float* db;
+  float* dcolscale;
+  int32_t B, T, C;
+  void* workspace;       /* vilco_colsum_workspace(B * T, C) bytes when dcolscale is wanted */
+  size_t workspace_bytes;
+  /* optional: partial maxima of |db| (device, >= 2048 floats; *n_parts, HOST int32 = how many were written): db is the upstream    */
+  /* gradient of the residual branch's last layer, whose activation-backward kernel turns it into operand planes                     */
+  /* (vilco_act_bwd_desc.planes)                                                                                                     */
+  float* db_amax_parts;
+  int32_t* n_parts;
+} vilco_scale_add_bwd_desc;
+int vilco_scale_add_bwd(const vilco_scale_add_bwd_desc* d, void* stream);
 /* Inverted dropout y = keep ? x/(1-p) : 0 with a counter-based mask (element i of the stream `seed` at `offset + i`):   */
 /* the backward pass is the same call on dy.  x = NULL writes the mask factors (0 or 1/(1-p)) -- what the parity tests  */
 /* hand to the oracle.  nn.Dropout in modeling_xlnet_x.py:308,327,486,488,1201,1228,1280 and blocks.py:226,268,349.      */
@@ -410,37 +451,43 @@ int vilco_seed_word_get(uint32_t* out);
 /* out = alpha*a + beta*b (b may be null) */
 int vilco_axpby(float* out, const float* a, const float* b, float alpha, float beta, int64_t n,
                 void* stream);
-/* dz = dropmask(dy) * act'(aux) * rowmask ; aux = pre-activation (gelu) or output (relu); act NONE = mask only;
- * drop_p > 0: the dropout mask (p, seed) of vilco_gemm's fused epilogue dropout, element index r*C + c.
- * Optional dbias[C] = column sums of dz (needs workspace). */
-int vilco_act_bwd(const float* dy, const float* aux, float* dz, float* dbias, int32_t act,
-                  const int32_t* len, int32_t T, int64_t rows, int32_t C, float drop_p, uint32_t drop_seed,
-                  void* workspace, size_t workspace_bytes, void* stream);
-/* the same + partial maxima of |dz| (amax_parts: device, >= 2048 floats; *n_parts = how many were written) */
-int vilco_act_bwd_amax(const float* dy, const float* aux, float* dz, float* dbias, int32_t act,
-                       const int32_t* len, int32_t T, int64_t rows, int32_t C, float drop_p, uint32_t drop_seed,
-                       void* workspace, size_t workspace_bytes, float* amax_parts, int32_t* n_parts, void* stream);
-/* the same, and dz written by this kernel as the fp16 x2 operand planes of its consumers (`planes`: vilco_pack's layout for
- * [rows][C] at precision 3, vilco_pack_bytes() long, 256-byte aligned; C % 32 == 0) -- no vilco_pack of dz follows.  The
- * planes' scale comes from a BOUND instead of the exact maximum: max|dy| (dy_amax: n_dy_amax partial maxima of |dy| left by
- * the producer of dy, e.g. vilco_gemm_desc.amax_out) x 1 / (1 - drop_p) x max|act'|; it is the same power-of-two rule, at
- * most two binary orders below the exact-maximum scale.  dz may be NULL (planes only). */
-int vilco_act_bwd_planes(const float* dy, const float* aux, float* dz, float* dbias, int32_t act,
-                         const int32_t* len, int32_t T, int64_t rows, int32_t C, float drop_p, uint32_t drop_seed,
-                         void* workspace, size_t workspace_bytes, float* amax_parts, int32_t* n_parts,
-                         const float* dy_amax, int32_t n_dy_amax, void* planes, size_t planes_bytes,
-                         const float* row_mask, void* stream);      /* row_mask: as vilco_gemm_desc.row_mask (rows floats) or NULL */
-/* Round 6: the same with the planes in the k=3 convs' zero-padded per-sequence image when seq_len > 0 (vilco_pack_item.seq_len: row
- * (b, t) at b * (seq_len + 2) + 1 + t, the pad rows and the slack zeroed here; C % 8 == 0, rows % seq_len == 0) -- the output gradient
- * of a masked k=3 conv (MQ/libs/modeling/blocks.py:79-84: conv output * mask) goes from the mask multiply straight into the operand
- * image of its dX and weight-gradient products, no fp32 dz, no vilco_pack_many.  seq_len = 0: vilco_act_bwd_planes.
- * vilco_act_bwd_planes_bytes: size of `planes` for either layout. */
-size_t vilco_act_bwd_planes_bytes(int64_t rows, int32_t C, int32_t seq_len);
-int vilco_act_bwd_planes_seq(const float* dy, const float* aux, float* dz, float* dbias, int32_t act,
-                             const int32_t* len, int32_t T, int64_t rows, int32_t C, float drop_p, uint32_t drop_seed,
-                             void* workspace, size_t workspace_bytes, float* amax_parts, int32_t* n_parts,
-                             const float* dy_amax, int32_t n_dy_amax, void* planes, size_t planes_bytes, int32_t seq_len,
-                             const float* row_mask, void* stream);
+/* dz = dropmask(dy) * act'(aux) * rowmask ; aux = pre-activation (gelu) or output (relu); act NONE = mask only */
+typedef struct vilco_act_bwd_desc {
+  const float* dy;       /* [rows][C] */
+  const float* aux;
+  float* dz;             /* may be NULL with planes (planes only) */
+  float* dbias;          /* optional [C] = column sums of dz (needs workspace) */
+  int32_t act;           /* VILCO_ACT_* */
+  const int32_t* len;    /* optional prefix mask: row r -> b = r / T, t = r % T, zero when t >= len[b] */
+  int32_t T;
+  int64_t rows;
+  int32_t C;
+  /* drop_p > 0: the dropout mask (p, seed) of vilco_gemm's fused epilogue dropout, element index r*C + c */
+  float drop_p;
+  uint32_t drop_seed;
+  void* workspace;       /* vilco_colsum_workspace(rows, C) bytes when dbias is wanted */
+  size_t workspace_bytes;
+  /* optional: partial maxima of |dz| (device, >= 2048 floats; *n_parts, HOST int32 = how many were written) */
+  float* amax_parts;
+  int32_t* n_parts;
+  /* optional: dz written by this kernel as the fp16 x2 operand planes of its consumers -- no vilco_pack of dz follows.  `planes`:    */
+  /* 256-byte aligned, vilco_act_bwd_planes_bytes() long.  seq_len = 0: vilco_pack's layout for [rows][C] at precision 3              */
+  /* (C % 32 == 0).  seq_len > 0 (round 6): the k=3 convs' zero-padded per-sequence image (vilco_pack_item.seq_len: row (b, t) at      */
+  /* b * (seq_len + 2) + 1 + t, the pad rows and the slack zeroed here; C % 8 == 0, rows % seq_len == 0) -- the output gradient of a   */
+  /* masked k=3 conv (MQ/libs/modeling/blocks.py:79-84: conv output * mask) goes from the mask multiply straight into the operand      */
+  /* image of its dX and weight-gradient products, no fp32 dz, no vilco_pack_many.  The planes' scale comes from a BOUND instead of    */
+  /* the exact maximum: max|dy| (dy_amax: n_dy_amax partial maxima of |dy| left by the producer of dy, e.g.                            */
+  /* vilco_gemm_desc.amax_out; required with planes) x 1 / (1 - drop_p) x max|act'|; it is the same power-of-two rule, at most two     */
+  /* binary orders below the exact-maximum scale.                                                                                     */
+  const float* dy_amax;
+  int32_t n_dy_amax;
+  void* planes;
+  size_t planes_bytes;
+  int32_t seq_len;
+  const float* row_mask; /* as vilco_gemm_desc.row_mask (rows floats) or NULL */
+} vilco_act_bwd_desc;
+size_t vilco_act_bwd_planes_bytes(int64_t rows, int32_t C, int32_t seq_len);   /* size of `planes` for either layout */
+int vilco_act_bwd(const vilco_act_bwd_desc* d, void* stream);
 /* out[c] = sum_r x[r][c] */
 int vilco_colsum(const float* x, float* out, int64_t rows, int32_t C, void* workspace,
                  size_t workspace_bytes, void* stream);
@@ -468,28 +515,31 @@ int vilco_permute3(const float* in, float* out, int32_t d0, int32_t d1, int32_t 
 int vilco_grad_norm(const int64_t* ptrs, const int64_t* numel, const int32_t* chunk_tensor,
                     const int64_t* chunk_off, int32_t n, int32_t nchunks, int32_t chunk, float max_norm,
                     float* partial, float* norm_coef, void* stream);
-int vilco_optim_step(int32_t kind, const int64_t* ptrs, const int64_t* numel, const int32_t* chunk_tensor,
-                     const int64_t* chunk_off, const int32_t* group, int32_t n, int32_t nchunks, int32_t chunk,
-                     const float* lr, const float* wd, int32_t ngroups, float beta1, float beta2, float eps,
-                     float momentum, const float* tensor_step, const float* norm_coef, void* stream);
-/* the same, and chunk_amax[c] (device float[nchunks], or null) = max|p| of the UPDATED parameter over chunk c: the   */
-/* chunks of one tensor are consecutive, so chunk_amax + first_chunk(t) with count chunks(t) is a vilco_pack_item.amax */
-/* for next step's pack of weight t -- the optimizer produces the scale of the fp16 x2 weight planes, the pack skips   */
-/* its own amax pass over the weight.                                                                                  */
-int vilco_optim_step_amax(int32_t kind, const int64_t* ptrs, const int64_t* numel, const int32_t* chunk_tensor,
-                          const int64_t* chunk_off, const int32_t* group, int32_t n, int32_t nchunks, int32_t chunk,
-                          const float* lr, const float* wd, int32_t ngroups, float beta1, float beta2, float eps,
-                          float momentum, const float* tensor_step, const float* norm_coef, float* chunk_amax,
-                          void* stream);
-/* the same with the learning rates read from DEVICE memory when lr_dev != null (float[ngroups]; `lr` is then ignored):  */
-/* a training iteration captured as a hipGraph replays its arguments, so the per-iteration schedule value               */
-/* (MQ/libs/utils/lr_schedulers.py:71-104, stepped at train_utils.py:351) and the per-tensor step counts `tensor_step`   */
-/* are memory the host (or a captured increment) rewrites between replays.                                              */
-int vilco_optim_step_dev(int32_t kind, const int64_t* ptrs, const int64_t* numel, const int32_t* chunk_tensor,
-                         const int64_t* chunk_off, const int32_t* group, int32_t n, int32_t nchunks, int32_t chunk,
-                         const float* lr, const float* wd, int32_t ngroups, float beta1, float beta2, float eps,
-                         float momentum, const float* tensor_step, const float* norm_coef, float* chunk_amax,
-                         const float* lr_dev, void* stream);
+typedef struct vilco_optim_desc {
+  int32_t kind;                /* 0 = AdamW, 1 = SGD with momentum */
+  const int64_t* ptrs;         /* device [4][n] */
+  const int64_t* numel;        /* device [n] */
+  const int32_t* chunk_tensor; /* device [nchunks] */
+  const int64_t* chunk_off;    /* device [nchunks] */
+  const int32_t* group;        /* device [n]: parameter group of every tensor */
+  int32_t n, nchunks, chunk;
+  const float* lr;             /* HOST [ngroups] */
+  const float* wd;             /* HOST [ngroups] */
+  int32_t ngroups;             /* 1..8 */
+  float beta1, beta2, eps, momentum;
+  const float* tensor_step;    /* device [n] */
+  const float* norm_coef;      /* vilco_grad_norm's, or NULL: gradients unscaled */
+  /* optional: chunk_amax[c] (device float[nchunks]) = max|p| of the UPDATED parameter over chunk c: the chunks of one tensor are   */
+  /* consecutive, so chunk_amax + first_chunk(t) with count chunks(t) is a vilco_pack_item.amax for next step's pack of weight t -- */
+  /* the optimizer produces the scale of the fp16 x2 weight planes, the pack skips its own amax pass over the weight.               */
+  float* chunk_amax;
+  /* optional: the learning rates read from DEVICE memory (float[ngroups]; `lr` is then ignored): a training iteration captured as  */
+  /* a hipGraph replays its arguments, so the per-iteration schedule value (MQ/libs/utils/lr_schedulers.py:71-104, stepped at       */
+  /* train_utils.py:351) and the per-tensor step counts `tensor_step` are memory the host (or a captured increment) rewrites        */
+  /* between replays.                                                                                                               */
+  const float* lr_dev;
+} vilco_optim_desc;
+int vilco_optim_step(const vilco_optim_desc* d, void* stream);
 /* dst[0..n) = vals[0..n): n <= 16 HOST floats carried as kernel arguments (stream-ordered, no staging buffer) -- how the */
 /* host hands this iteration's learning rates to a captured optimizer step.                                              */
 int vilco_store_f32(float* dst, const float* vals, int32_t n, void* stream);

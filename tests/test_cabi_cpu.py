@@ -39,7 +39,8 @@ def test_bad_arguments_are_rejected_without_a_gpu():
     lib = _lib.load()
     d = _lib.GemmDesc()
     assert lib.vilco_gemm(ctypes.byref(d), None) == -1              # null operands
-    assert lib.vilco_layernorm_fwd(None, None, None, None, None, None, 4, 64, 1e-5, 0, None) == -1
+    assert lib.vilco_layernorm_fwd(ctypes.byref(_lib.LnFwdDesc(rows=4, C=64, eps=1e-5)), None) == -1     # null operands
+    assert lib.vilco_layernorm_fwd(None, None) == -1
     assert lib.vilco_nms_1d(None, None, None, -1, 0, 0.5, None, None, None, 0, None) == -1
     with pytest.raises(RuntimeError, match="bad argument"):
         _lib.check(-1)
@@ -103,13 +104,20 @@ def test_producer_plane_entry_points_validate_on_the_host():
     assert lib.vilco_layernorm_planes_bytes(2 * 4541, 1024, 4541) == lib.vilco_pack_item_bytes(ctypes.byref(it), 3)
     x = 4096                                            # dummy, suitably aligned addresses: every check below precedes the launch
     # natural planes need C % 32 == 0, the convs' image whole sequences; a short buffer is a workspace error
-    assert lib.vilco_layernorm_fwd_planes(x, None, None, x, x, x, 64, 40, 1e-5, 0, None, None, x, 1 << 30, 0, None, 0, None) == -2
-    assert lib.vilco_layernorm_fwd_planes(x, None, None, x, x, x, 65, 64, 1e-5, 0, None, None, x, 1 << 30, 16, None, 0, None) == -2
-    assert lib.vilco_layernorm_fwd_planes(x, None, None, x, x, x, 64, 64, 1e-5, 0, None, None, x, 128, 0, None, 0, None) == -4
+    def ln_fwd(**kw):
+        d = _lib.LnFwdDesc(x=x, y=x, mean=x, rstd=x, eps=1e-5, planes=x, **kw)
+        return lib.vilco_layernorm_fwd(ctypes.byref(d), None)
+    assert ln_fwd(rows=64, C=40, planes_bytes=1 << 30) == -2
+    assert ln_fwd(rows=65, C=64, planes_bytes=1 << 30, seq_len=16) == -2
+    assert ln_fwd(rows=64, C=64, planes_bytes=128) == -4
     # activation backward: planes need the partial maxima of dy, C % 32 == 0 and a buffer of vilco_pack_bytes
-    assert lib.vilco_act_bwd_planes(x, None, None, None, 0, None, 0, 64, 64, 0.0, 0, None, 0, None, None, None, 0, x, 1 << 30, None, None) == -1
-    assert lib.vilco_act_bwd_planes(x, None, None, None, 0, None, 0, 64, 40, 0.0, 0, None, 0, None, None, x, 4, x, 1 << 30, None, None) == -1
-    assert lib.vilco_act_bwd_planes(x, None, None, None, 0, None, 0, 64, 64, 0.0, 0, None, 0, None, None, x, 4, x, 128, None, None) == -4
+
+    def act_bwd(**kw):
+        d = _lib.ActBwdDesc(dy=x, rows=64, planes=x, **kw)
+        return lib.vilco_act_bwd(ctypes.byref(d), None)
+    assert act_bwd(C=64, planes_bytes=1 << 30) == -1
+    assert act_bwd(C=40, planes_bytes=1 << 30, dy_amax=x, n_dy_amax=4) == -1
+    assert act_bwd(C=64, planes_bytes=128, dy_amax=x, n_dy_amax=4) == -4
     # a row mask on a batched product is not supported
     d = _lib.GemmDesc()
     d.A = d.B = d.C = d.row_mask = 4096
@@ -119,3 +127,36 @@ def test_producer_plane_entry_points_validate_on_the_host():
     d.ldc = 128
     d.batch_outer, d.batch_inner, d.precision = 2, 1, 3
     assert lib.vilco_gemm(ctypes.byref(d), None) == -2
+
+
+def test_optional_parts_of_the_descriptors_validate_on_the_host():
+    """what the descriptors' optional fields exclude, refused before anything is launched (dummy aligned addresses)"""
+    from vilco_amd import _lib
+    lib = _lib.load()
+    x = 4096
+    # XLNet's relative attention at hd = 64 (mask mode 3, bias, precision 3): dS leaves either as dbias or as ds_planes, not both
+    xl = dict(q=x, k=x, v=x, bias=x, kv_len=x, o=x, lse=x, B=1, H=1, Tq=64, Tk=64, scale=0.125, mode=3, precision=3,
+              workspace=x, workspace_bytes=1 << 40)
+    d = _lib.AttnDesc(hd=64, dout=x, dq=x, dk=x, dv=x, dbias=x, ds_planes=x, ds_planes_bytes=1 << 40, **xl)
+    assert lib.vilco_attn_bwd(ctypes.byref(d), None) == -2
+    # the output's operand planes come from the hd = 64 forward kernels only
+    d = _lib.AttnDesc(hd=32, o_planes=x, o_planes_bytes=1 << 40, **xl)
+    assert lib.vilco_attn_fwd(ctypes.byref(d), None) == -2
+    # at most 8 parameter groups travel as kernel arguments
+    lr = (ctypes.c_float * 9)()
+    d = _lib.OptimDesc(ptrs=x, numel=x, chunk_tensor=x, chunk_off=x, group=x, n=1, nchunks=1, chunk=1024, lr=ctypes.addressof(lr),
+                       wd=ctypes.addressof(lr), ngroups=9, tensor_step=x)
+    assert lib.vilco_optim_step(ctypes.byref(d), None) == -1
+    # LayerNorm backward: dgamma and dbeta come together or not at all
+    d = _lib.LnBwdDesc(dy=x, x=x, mean=x, rstd=x, dx=x, dgamma=x, rows=64, C=64, workspace=x, workspace_bytes=1 << 40)
+    assert lib.vilco_layernorm_bwd(ctypes.byref(d), None) == -1
+
+
+def test_struct_mirrors_have_the_size_the_compiler_gave_the_c_structs():
+    from vilco_amd import _lib
+    lib = _lib.load()
+    mirrors = [c for c in vars(_lib).values() if isinstance(c, type) and issubclass(c, ctypes.Structure) and c is not ctypes.Structure]
+    assert len(mirrors) >= 10
+    for c in mirrors:
+        assert ctypes.sizeof(c) == lib.vilco_abi_sizeof(c._cname_.encode()) > 0, c.__name__
+    assert lib.vilco_abi_sizeof(b"vilco_no_such_struct") == 0

@@ -839,7 +839,7 @@ def test_single_part_products_two_k_steps_per_interval(dev, M, N, K, form):
 
 @pytest.mark.parametrize("rows,C,act,p,masked", [(4608, 1024, 2, 0.1, True), (100, 96, 0, 0.0, True), (333, 64, 1, 0.3, False), (77, 1024, 2, 0.0, False)])
 def test_act_bwd_writes_operand_planes(dev, rows, C, act, p, masked):
-    """vilco_act_bwd_planes: dz written by the activation-backward kernel as fp16 x2 operand planes (scale from a bound on
+    """vilco_act_bwd_desc.planes: dz written by the activation-backward kernel as fp16 x2 operand planes (scale from a bound on
     max|dz| instead of the exact maximum) -- the planes decode to the fp32 dz of the plain kernel to 22 bits, their zero rows
     are zero, the bias gradient is unchanged, and both backward products read them like the planes `pack` makes."""
     from vilco_amd import ops, _lib
@@ -914,7 +914,7 @@ def test_linear_backward_takes_producer_planes(dev, monkeypatch):
 
 
 def test_scale_add_backward_tags_branch_gradient(dev):
-    """the branch gradient scale_add's backward writes carries its exact max|db| partials (vilco_scale_add_bwd_amax)"""
+    """the branch gradient scale_add's backward writes carries its exact max|db| partials (vilco_scale_add_bwd_desc.db_amax_parts)"""
     from vilco_amd import ops
     torch.manual_seed(8)
     B, T, C = 2, 50, 96
@@ -932,7 +932,7 @@ def test_scale_add_backward_tags_branch_gradient(dev):
 @pytest.mark.parametrize("B,T,C,relu,layout", [(2, 2304, 1024, False, "nat"), (3, 37, 96, False, "nat"), (2, 50, 64, True, "seq"),
                                                (2, 4541, 1024, True, "seq"), (1, 77, 1000, False, "nat"), (2, 40, 72, True, "seq")])
 def test_layernorm_writes_operand_planes(dev, B, T, C, relu, layout):
-    """vilco_layernorm_fwd_planes: the LayerNorm kernel also writes its output as fp16 x2 operand planes, scaled by the bound
+    """vilco_ln_fwd_desc.planes: the LayerNorm kernel also writes its output as fp16 x2 operand planes, scaled by the bound
     max|gamma| sqrt(C) + max|beta| -- natural rows (a Linear's input) or the k=3 convs' zero-padded per-sequence image.  The
     planes decode to y to 22 bits, every padding row is zero, the consumer's pack finds them, and the products on them equal
     the products on packed planes."""
@@ -1013,7 +1013,7 @@ def test_layernorm_row_mask_equals_masking_afterwards(dev):
 
 
 def test_conv3_row_mask_equals_masking_afterwards(dev):
-    """vilco_gemm_desc.row_mask / vilco_act_bwd_planes(row_mask): a k=3 conv whose output rows are zeroed by a per-row 0 / 1 mask in
+    """vilco_gemm_desc.row_mask / vilco_act_bwd_desc.row_mask: a k=3 conv whose output rows are zeroed by a per-row 0 / 1 mask in
     the GEMM epilogue == the conv followed by the multiply, forward and all three gradients"""
     from vilco_amd import ops
     torch.manual_seed(21)
@@ -1072,7 +1072,7 @@ def test_pack_group_equals_single_packs_and_keeps_the_cache(dev):
 
 @pytest.mark.parametrize("masked_by", ["row_mask", "lens"])
 def test_conv3_backward_writes_dz_image_from_the_mask_kernel(dev, masked_by):
-    """Round 6 (vilco_act_bwd_planes_seq + vilco_layernorm_bwd_res_amax): conv k=3 -> LayerNorm -> ReLU, the heads' / embeddings'
+    """Round 6 (vilco_act_bwd_desc.seq_len + vilco_ln_bwd_desc.dx_amax_parts): conv k=3 -> LayerNorm -> ReLU, the heads' / embeddings'
     pattern (MQ/libs/modeling/meta_archs.py:216-235).  LayerNorm backward leaves max|dx| partials, so the conv's mask kernel
     writes dZ straight into the zero-padded operand image of the dX and weight-gradient products (no fp32 dZ, no pack_tap): the
     decoded image equals the masked gradient to 22 bits with zero pad rows, and all gradients equal the VILCO_CONV_DZ_PLANES=0
@@ -1123,7 +1123,7 @@ def test_conv3_backward_writes_dz_image_from_the_mask_kernel(dev, masked_by):
 
 @pytest.mark.parametrize("B,Tq,Tk,H,lens", [(2, 300, 300, 2, [300, 211]), (1, 129, 77, 4, [77]), (2, 2304, 2304, 2, [2304, 1500])])
 def test_attention_writes_output_planes(dev, B, Tq, Tk, H, lens):
-    """vilco_attn_fwd_planes (hd = 64 forward kernels): the attention output also leaves the kernel as the fp16 x2 operand planes
+    """vilco_attn_desc.o_planes (hd = 64 forward kernels): the attention output also leaves the kernel as the fp16 x2 operand planes
     of the output projection, scaled by max|v| (a convex combination of rows of v cannot exceed it): decode == o to 22 bits,
     zero rows zero, the projection finds the planes, and its forward + backward equal the VILCO_ATTN_PLANES=0 path"""
     from vilco_amd import ops

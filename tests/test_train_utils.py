@@ -114,7 +114,7 @@ def test_fused_optimizer_duplicate_param_uses_clipped_grad(dev):
 @pytest.mark.gpu
 @pytest.mark.parametrize("kind", ["AdamW", "SGD"])
 def test_optimizer_leaves_weight_amax_for_the_packs(dev, kind):
-    """the update kernels emit max|p| per chunk (vilco_optim_step_amax); FusedOptimizer tags every matrix parameter with
+    """the update kernels emit max|p| per chunk (vilco_optim_desc.chunk_amax); FusedOptimizer tags every matrix parameter with
     its slice; the weight pack built from the tag is bit-identical to the pack that runs its own amax pass; a
     parameter stepped twice carries the partials of its LAST update; any later write invalidates the tag"""
     import warnings

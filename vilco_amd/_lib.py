@@ -17,8 +17,10 @@ c_fp = C.c_void_p   # device pointers travel as integers (tensor.data_ptr())
 i32, i64, f32, sz = C.c_int32, C.c_int64, C.c_float, C.c_size_t
 
 
+# Every Structure below mirrors the C struct `_cname_` of include/vilco_hip.h field for field; tests/test_cabi_cpu.py holds
+# each to the size the library reports for that name (vilco_abi_sizeof).
 class GemmDesc(C.Structure):
-    """Mirror of `vilco_gemm_desc` (include/vilco_hip.h)."""
+    _cname_ = "vilco_gemm_desc"
     _fields_ = [
         ("A", c_fp), ("B", c_fp), ("C", c_fp),
         ("M", i32), ("N", i32), ("K", i32),
@@ -44,7 +46,7 @@ class GemmDesc(C.Structure):
 
 
 class LossDesc(C.Structure):
-    """Mirror of `vilco_loss_desc`."""
+    _cname_ = "vilco_loss_desc"
     _fields_ = [("logits", c_fp), ("offsets", c_fp), ("level_scale", c_fp), ("points", c_fp), ("row_level", c_fp),
                 ("row_pos", c_fp), ("level_len", c_fp), ("gt", c_fp), ("gauss", c_fp), ("loss_norm", c_fp),
                 ("B", i32), ("R", i32), ("C", i32), ("L", i32), ("Nmax", i32),
@@ -53,20 +55,72 @@ class LossDesc(C.Structure):
 
 
 class AttnAmaxIn(C.Structure):
-    """Mirror of `vilco_attn_amax_in`."""
+    _cname_ = "vilco_attn_amax_in"
     _fields_ = [("q", c_fp), ("nq", i32), ("k", c_fp), ("nk", i32), ("v", c_fp), ("nv", i32), ("dout", c_fp), ("ndo", i32)]
 
 
 class PackItem(C.Structure):
-    """Mirror of `vilco_pack_item`."""
+    _cname_ = "vilco_pack_item"
     _fields_ = [("src", c_fp), ("rows", i64), ("cols", i64), ("ld", i64), ("planes", c_fp), ("planes_bytes", sz),
                 ("nbatch", i32), ("batch_stride", i64), ("relshift", i32), ("amax", c_fp), ("namax", i32), ("seq_len", i32)]
+
+
+# host addresses travel as integers too (C.addressof): the `n_parts` c_int32 a call writes, AttnDesc.amax_in, OptimDesc.lr / wd
+class LnFwdDesc(C.Structure):
+    _cname_ = "vilco_ln_fwd_desc"
+    _fields_ = [("x", c_fp), ("gamma", c_fp), ("beta", c_fp), ("y", c_fp), ("mean", c_fp), ("rstd", c_fp),
+                ("rows", i64), ("C", i32), ("eps", f32), ("relu", i32), ("amax_parts", c_fp), ("n_parts", c_fp),
+                ("planes", c_fp), ("planes_bytes", sz), ("seq_len", i32), ("row_mask", c_fp), ("mask_rows", i64)]
+
+
+class LnBwdDesc(C.Structure):
+    _cname_ = "vilco_ln_bwd_desc"
+    _fields_ = [("dy", c_fp), ("x", c_fp), ("y", c_fp), ("gamma", c_fp), ("mean", c_fp), ("rstd", c_fp), ("dres", c_fp),
+                ("dx", c_fp), ("dgamma", c_fp), ("dbeta", c_fp), ("rows", i64), ("C", i32), ("relu", i32),
+                ("workspace", c_fp), ("workspace_bytes", sz), ("dx_amax_parts", c_fp), ("n_parts", c_fp)]
+
+
+class AttnDesc(C.Structure):
+    _cname_ = "vilco_attn_desc"
+    _fields_ = [("q", c_fp), ("k", c_fp), ("v", c_fp), ("bias", c_fp), ("kv_len", c_fp), ("o", c_fp), ("lse", c_fp),
+                ("B", i32), ("H", i32), ("Tq", i32), ("Tk", i32), ("hd", i32), ("scale", f32),
+                ("mode", i32), ("window", i32), ("precision", i32), ("drop_p", f32), ("drop_seed", C.c_uint32),
+                ("amax_in", c_fp), ("workspace", c_fp), ("workspace_bytes", sz),
+                ("o_amax", c_fp), ("o_planes", c_fp), ("o_planes_bytes", sz),
+                ("dout", c_fp), ("dq", c_fp), ("dk", c_fp), ("dv", c_fp), ("dbias", c_fp),
+                ("dq_amax", c_fp), ("dk_amax", c_fp), ("dv_amax", c_fp), ("dbias_amax", c_fp),
+                ("ds_planes", c_fp), ("ds_planes_bytes", sz)]
+
+
+class ScaleAddBwdDesc(C.Structure):
+    _cname_ = "vilco_scale_add_bwd_desc"
+    _fields_ = [("dout", c_fp), ("bval", c_fp), ("colscale", c_fp), ("rowscale", c_fp), ("len", c_fp), ("mask_a", i32),
+                ("da", c_fp), ("db", c_fp), ("dcolscale", c_fp), ("B", i32), ("T", i32), ("C", i32),
+                ("workspace", c_fp), ("workspace_bytes", sz), ("db_amax_parts", c_fp), ("n_parts", c_fp)]
+
+
+class ActBwdDesc(C.Structure):
+    _cname_ = "vilco_act_bwd_desc"
+    _fields_ = [("dy", c_fp), ("aux", c_fp), ("dz", c_fp), ("dbias", c_fp), ("act", i32), ("len", c_fp), ("T", i32),
+                ("rows", i64), ("C", i32), ("drop_p", f32), ("drop_seed", C.c_uint32),
+                ("workspace", c_fp), ("workspace_bytes", sz), ("amax_parts", c_fp), ("n_parts", c_fp),
+                ("dy_amax", c_fp), ("n_dy_amax", i32), ("planes", c_fp), ("planes_bytes", sz), ("seq_len", i32),
+                ("row_mask", c_fp)]
+
+
+class OptimDesc(C.Structure):
+    _cname_ = "vilco_optim_desc"
+    _fields_ = [("kind", i32), ("ptrs", c_fp), ("numel", c_fp), ("chunk_tensor", c_fp), ("chunk_off", c_fp), ("group", c_fp),
+                ("n", i32), ("nchunks", i32), ("chunk", i32), ("lr", c_fp), ("wd", c_fp), ("ngroups", i32),
+                ("beta1", f32), ("beta2", f32), ("eps", f32), ("momentum", f32), ("tensor_step", c_fp), ("norm_coef", c_fp),
+                ("chunk_amax", c_fp), ("lr_dev", c_fp)]
 
 
 # name -> (restype, argtypes); must list every symbol include/vilco_hip.h declares
 SIGNATURES = {
     "vilco_status_str": (C.c_char_p, [C.c_int]),
     "vilco_version": (C.c_char_p, []),
+    "vilco_abi_sizeof": (sz, [C.c_char_p]),
     "vilco_defer_set": (C.c_int, [i32]),
     "vilco_defer_pending": (i64, []),
     "vilco_defer_flush": (C.c_int, [c_fp]),
@@ -84,18 +138,10 @@ SIGNATURES = {
     "vilco_pack_item_bytes": (sz, [C.POINTER(PackItem), i32]),
     "vilco_pack": (C.c_int, [c_fp, i64, i64, i64, i32, c_fp, sz, c_fp]),
     "vilco_pack_many": (C.c_int, [C.POINTER(PackItem), i32, i32, c_fp]),
-    "vilco_layernorm_fwd": (C.c_int, [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, i64, i32, f32, i32, c_fp]),
-    "vilco_layernorm_fwd_amax": (C.c_int, [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, i64, i32, f32, i32, c_fp, C.POINTER(i32), c_fp]),
+    "vilco_layernorm_fwd": (C.c_int, [C.POINTER(LnFwdDesc), c_fp]),
     "vilco_layernorm_planes_bytes": (sz, [i64, i32, i32]),
-    "vilco_layernorm_fwd_planes": (C.c_int, [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, i64, i32, f32, i32, c_fp, C.POINTER(i32), c_fp, sz,
-                                             i32, c_fp, i64, c_fp]),
     "vilco_layernorm_bwd_workspace": (sz, [i64, i32]),
-    "vilco_layernorm_bwd": (C.c_int, [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, i64, i32,
-                                      i32, c_fp, sz, c_fp]),
-    "vilco_layernorm_bwd_res": (C.c_int, [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, i64, i32,
-                                          i32, c_fp, sz, c_fp]),
-    "vilco_layernorm_bwd_res_amax": (C.c_int, [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, i64, i32,
-                                               i32, c_fp, sz, c_fp, C.POINTER(i32), c_fp]),
+    "vilco_layernorm_bwd": (C.c_int, [C.POINTER(LnBwdDesc), c_fp]),
     "vilco_dwconv3_fwd": (C.c_int, [c_fp, c_fp, c_fp, c_fp, i32, i32, i32, i32, c_fp]),
     "vilco_dwconv3_bwd_workspace": (sz, [i32, i32, i32, i32]),
     "vilco_dwconv3_bwd": (C.c_int, [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, i32, i32, i32, i32, c_fp, sz, c_fp]),
@@ -108,55 +154,33 @@ SIGNATURES = {
     "vilco_attn_supported": (C.c_int, [i32]),
     "vilco_attn_fwd_workspace": (sz, [i32, i32, i32, i32, i32, i32]),
     "vilco_attn_amax_parts": (i32, [i32, i32, i32, i32, i32, i32, i32, f32, i32]),
-    "vilco_attn_fwd": (C.c_int, [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, i32, i32, i32, i32, i32, f32, i32, i32, i32, f32,
-                                 C.c_uint32, C.POINTER(AttnAmaxIn), c_fp, c_fp, sz, c_fp]),
-    "vilco_attn_fwd_planes": (C.c_int, [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, i32, i32, i32, i32, i32, f32, i32, i32, i32, f32,
-                                        C.c_uint32, C.POINTER(AttnAmaxIn), c_fp, c_fp, sz, c_fp, sz, c_fp]),
+    "vilco_attn_fwd": (C.c_int, [C.POINTER(AttnDesc), c_fp]),
     "vilco_attn_planes_supported": (i32, [i32, i32, i32, i32, i32, i32, f32]),
     "vilco_attn_bwd_workspace": (sz, [i32, i32, i32, i32, i32, i32]),
-    "vilco_attn_bwd": (C.c_int, [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, i32, i32,
-                                 i32, i32, i32, f32, i32, i32, i32, f32, C.c_uint32, C.POINTER(AttnAmaxIn), c_fp, c_fp, c_fp, c_fp, c_fp, sz,
-                                 c_fp]),
+    "vilco_attn_bwd": (C.c_int, [C.POINTER(AttnDesc), c_fp]),
     "vilco_attn_dsplanes_bytes": (sz, [i32, i32, i32]),
     "vilco_xl_scores_workspace": (sz, [i32, i32, i32, i32]),
     "vilco_xl_scores": (C.c_int, [c_fp, c_fp, c_fp, i32, i32, i32, i32, i32, i32, c_fp, sz, c_fp]),
-    "vilco_attn_bwd_dsplanes": (C.c_int, [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, i32, i32,
-                                          i32, i32, i32, f32, i32, i32, i32, f32, C.c_uint32, C.POINTER(AttnAmaxIn), c_fp, c_fp, c_fp, c_fp,
-                                          c_fp, sz, c_fp, sz, c_fp]),
     "vilco_decode_workspace": (sz, [i32, i32]),
     "vilco_decode": (C.c_int, [c_fp, c_fp, c_fp, c_fp, c_fp, i32, i32, i32, f32, f32, c_fp, c_fp, c_fp, c_fp, c_fp, sz, c_fp]),
     "vilco_scale_add_fwd": (C.c_int, [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, i32, i32, i32, i32, c_fp]),
     "vilco_colsum_workspace": (sz, [i64, i32]),
-    "vilco_scale_add_bwd": (C.c_int, [c_fp, c_fp, c_fp, c_fp, c_fp, i32, c_fp, c_fp, c_fp, i32, i32, i32,
-                                      c_fp, sz, c_fp]),
-    "vilco_scale_add_bwd_amax": (C.c_int, [c_fp, c_fp, c_fp, c_fp, c_fp, i32, c_fp, c_fp, c_fp, i32, i32, i32,
-                                           c_fp, sz, c_fp, C.POINTER(i32), c_fp]),
+    "vilco_scale_add_bwd": (C.c_int, [C.POINTER(ScaleAddBwdDesc), c_fp]),
     "vilco_dropout": (C.c_int, [c_fp, c_fp, i64, f32, C.c_uint32, C.c_uint64, c_fp]),
     "vilco_attn_dropout_mask": (C.c_int, [c_fp, i64, i32, f32, C.c_uint32, c_fp]),
     "vilco_seed_word_set": (C.c_int, [C.c_uint32, c_fp]),
     "vilco_seed_word_bump": (C.c_int, [c_fp]),
     "vilco_seed_word_get": (C.c_int, [C.POINTER(C.c_uint32)]),
     "vilco_axpby": (C.c_int, [c_fp, c_fp, c_fp, f32, f32, i64, c_fp]),
-    "vilco_act_bwd": (C.c_int, [c_fp, c_fp, c_fp, c_fp, i32, c_fp, i32, i64, i32, f32, C.c_uint32, c_fp, sz, c_fp]),
-    "vilco_act_bwd_amax": (C.c_int, [c_fp, c_fp, c_fp, c_fp, i32, c_fp, i32, i64, i32, f32, C.c_uint32, c_fp, sz, c_fp,
-                                     C.POINTER(i32), c_fp]),
-    "vilco_act_bwd_planes": (C.c_int, [c_fp, c_fp, c_fp, c_fp, i32, c_fp, i32, i64, i32, f32, C.c_uint32, c_fp, sz, c_fp,
-                                       C.POINTER(i32), c_fp, i32, c_fp, sz, c_fp, c_fp]),
+    "vilco_act_bwd": (C.c_int, [C.POINTER(ActBwdDesc), c_fp]),
     "vilco_act_bwd_planes_bytes": (sz, [i64, i32, i32]),
-    "vilco_act_bwd_planes_seq": (C.c_int, [c_fp, c_fp, c_fp, c_fp, i32, c_fp, i32, i64, i32, f32, C.c_uint32, c_fp, sz, c_fp,
-                                           C.POINTER(i32), c_fp, i32, c_fp, sz, i32, c_fp, c_fp]),
     "vilco_colsum": (C.c_int, [c_fp, c_fp, i64, i32, c_fp, sz, c_fp]),
     "vilco_mask_rows": (C.c_int, [c_fp, c_fp, i32, i32, i32, c_fp]),
     "vilco_add_pe": (C.c_int, [c_fp, c_fp, c_fp, c_fp, i32, i32, i32, c_fp]),
     "vilco_transpose2d": (C.c_int, [c_fp, c_fp, i32, i32, i32, c_fp]),
     "vilco_permute3": (C.c_int, [c_fp, c_fp, i32, i32, i32, i64, i64, i64, i64, c_fp]),
     "vilco_grad_norm": (C.c_int, [c_fp, c_fp, c_fp, c_fp, i32, i32, i32, f32, c_fp, c_fp, c_fp]),
-    "vilco_optim_step": (C.c_int, [i32, c_fp, c_fp, c_fp, c_fp, c_fp, i32, i32, i32, C.POINTER(f32), C.POINTER(f32), i32,
-                                   f32, f32, f32, f32, c_fp, c_fp, c_fp]),
-    "vilco_optim_step_amax": (C.c_int, [i32, c_fp, c_fp, c_fp, c_fp, c_fp, i32, i32, i32, C.POINTER(f32), C.POINTER(f32), i32,
-                                        f32, f32, f32, f32, c_fp, c_fp, c_fp, c_fp]),
-    "vilco_optim_step_dev": (C.c_int, [i32, c_fp, c_fp, c_fp, c_fp, c_fp, i32, i32, i32, C.POINTER(f32), C.POINTER(f32), i32,
-                                       f32, f32, f32, f32, c_fp, c_fp, c_fp, c_fp, c_fp]),
+    "vilco_optim_step": (C.c_int, [C.POINTER(OptimDesc), c_fp]),
     "vilco_store_f32": (C.c_int, [c_fp, C.POINTER(f32), i32, c_fp]),
     "vilco_qkv_pre_supported": (C.c_int, [i32]),
     "vilco_qkv_pre_amax_parts": (C.c_int, [i32, i32, i32]),

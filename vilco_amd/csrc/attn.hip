@@ -2204,7 +2204,7 @@ extern "C" int32_t vilco_attn_amax_parts(int32_t B, int32_t H, int32_t T, int32_
   return n <= 8192 ? (int32_t)n : 0;
 }
 
-// 1 when vilco_attn_fwd_planes can write o's operand planes for this configuration (the hd = 64 forward kernels)
+// 1 when vilco_attn_fwd can write o's operand planes (vilco_attn_desc.o_planes) for this configuration (the hd = 64 forward kernels)
 extern "C" int32_t vilco_attn_planes_supported(int32_t Tq, int32_t Tk, int32_t hd, int32_t mode, int32_t precision, int32_t has_bias,
                                                float drop_p) {
   AttnArgs a = {};
@@ -2219,20 +2219,18 @@ extern "C" size_t vilco_attn_fwd_workspace(int32_t B, int32_t H, int32_t Tq, int
                   planes_bytes(spec_tr(B, H, Tk, hd), NP) + 1024 + ATT_SCALE_BYTES);
 }
 
-extern "C" int vilco_attn_fwd(const float* q, const float* k, const float* v, const float* bias,
-                              const int32_t* kv_len, float* o, float* lse, int32_t B, int32_t H, int32_t Tq,
-                              int32_t Tk, int32_t hd, float scale, int32_t mode, int32_t window, int32_t precision, float drop_p,
-                              uint32_t drop_seed, const vilco_attn_amax_in* amax_in, float* o_amax, void* workspace,
-                              size_t workspace_bytes, void* stream) {
-  return vilco_attn_fwd_planes(q, k, v, bias, kv_len, o, lse, B, H, Tq, Tk, hd, scale, mode, window, precision, drop_p, drop_seed,
-                               amax_in, o_amax, workspace, workspace_bytes, nullptr, 0, stream);
-}
-
-extern "C" int vilco_attn_fwd_planes(const float* q, const float* k, const float* v, const float* bias,
-                              const int32_t* kv_len, float* o, float* lse, int32_t B, int32_t H, int32_t Tq,
-                              int32_t Tk, int32_t hd, float scale, int32_t mode, int32_t window, int32_t precision, float drop_p,
-                              uint32_t drop_seed, const vilco_attn_amax_in* amax_in, float* o_amax, void* workspace,
-                              size_t workspace_bytes, void* o_planes, size_t o_planes_bytes, void* stream) {
+extern "C" int vilco_attn_fwd(const vilco_attn_desc* d, void* stream) {
+  if (!d) return VILCO_ERR_BADARG;
+  const float *q = d->q, *k = d->k, *v = d->v, *bias = d->bias;
+  const int32_t* kv_len = d->kv_len;
+  const int32_t B = d->B, H = d->H, Tq = d->Tq, Tk = d->Tk, hd = d->hd, mode = d->mode, window = d->window, precision = d->precision;
+  const float scale = d->scale, drop_p = d->drop_p;
+  const uint32_t drop_seed = d->drop_seed;
+  const vilco_attn_amax_in* amax_in = d->amax_in;
+  void* workspace = d->workspace;
+  const size_t workspace_bytes = d->workspace_bytes;
+  float *o = d->o, *lse = d->lse, *o_amax = d->o_amax;
+  void* o_planes = d->o_planes;
   int rc = check_common(B, H, Tq, Tk, hd, mode, precision, window);
   if (!(drop_p >= 0.f) || drop_p >= 1.f) return VILCO_ERR_BADARG;
   if (rc != VILCO_OK) return rc;
@@ -2251,13 +2249,9 @@ extern "C" int vilco_attn_fwd_planes(const float* q, const float* k, const float
   a.am_o = o_amax;
   if (o_planes) {                  // the hd = 64 forward kernels only (fast64 / fast64_xl_fwd)
     if (!(fast64(a, precision) || fast64_xl_fwd(a, precision)) || !vilco_aligned(o_planes, 256)) return VILCO_ERR_UNSUPPORTED;
-    const long rows32 = ((long)B * Tq + 31) / 32 * 32;
-    if (o_planes_bytes < (size_t)(VILCO_PACK_HDR + rows32 * (long)(H * hd) * 4)) return VILCO_ERR_WORKSPACE;
-    unsigned char* u = reinterpret_cast<unsigned char*>(o_planes);
-    a.op0 = reinterpret_cast<_Float16*>(u + VILCO_PACK_HDR);
-    a.o_plane_stride = rows32 * (long)(H * hd);
-    a.o_inv_scale = reinterpret_cast<float*>(u) + VILCO_AMAX_MAX_BLOCKS;
-    a.o_rows32 = rows32;
+    VilcoPlaneView pv;
+    if (d->o_planes_bytes < vilco_plane_view(o_planes, (long)B * Tq, H * hd, 0, &pv)) return VILCO_ERR_WORKSPACE;
+    a.op0 = pv.p0; a.o_plane_stride = pv.plane_stride; a.o_inv_scale = pv.inv_scale; a.o_rows32 = pv.rows_out;
     a.o_scale_mul = 1.f;
     for (float ik = a.drop_thresh ? a.drop_inv_keep : 1.f; ik > 1.f; ik *= 0.5f) a.o_scale_mul *= 0.5f;      // 2^-ceil(log2(1 / keep))
   }
@@ -2328,29 +2322,26 @@ extern "C" size_t vilco_attn_bwd_workspace(int32_t B, int32_t H, int32_t Tq, int
   return (size_t)bytes;
 }
 
-extern "C" int vilco_attn_bwd(const float* q, const float* k, const float* v, const float* bias,
-                              const int32_t* kv_len, const float* o, const float* lse, const float* dout,
-                              float* dq, float* dk, float* dv, float* dbias, int32_t B, int32_t H, int32_t Tq,
-                              int32_t Tk, int32_t hd, float scale, int32_t mode, int32_t window, int32_t precision, float drop_p,
-                              uint32_t drop_seed, const vilco_attn_amax_in* amax_in, float* dq_amax, float* dk_amax,
-                              float* dv_amax, float* dbias_amax, void* workspace, size_t workspace_bytes, void* stream) {
-  return vilco_attn_bwd_dsplanes(q, k, v, bias, kv_len, o, lse, dout, dq, dk, dv, dbias, B, H, Tq, Tk, hd, scale, mode, window, precision,
-                                 drop_p, drop_seed, amax_in, dq_amax, dk_amax, dv_amax, dbias_amax, workspace, workspace_bytes, nullptr, 0,
-                                 stream);
-}
-
 extern "C" size_t vilco_attn_dsplanes_bytes(int32_t B, int32_t H, int32_t T) {
   const long r32 = ((long)T + 31) / 32 * 32, c32 = (2L * T + 31) / 32 * 32;
   return (size_t)(VILCO_PACK_HDR + (long)B * H * r32 * c32 * 2 * 2);
 }
 
-extern "C" int vilco_attn_bwd_dsplanes(const float* q, const float* k, const float* v, const float* bias,
-                              const int32_t* kv_len, const float* o, const float* lse, const float* dout,
-                              float* dq, float* dk, float* dv, float* dbias, int32_t B, int32_t H, int32_t Tq,
-                              int32_t Tk, int32_t hd, float scale, int32_t mode, int32_t window, int32_t precision, float drop_p,
-                              uint32_t drop_seed, const vilco_attn_amax_in* amax_in, float* dq_amax, float* dk_amax,
-                              float* dv_amax, float* dbias_amax, void* workspace, size_t workspace_bytes, void* ds_planes,
-                              size_t ds_planes_bytes, void* stream) {
+extern "C" int vilco_attn_bwd(const vilco_attn_desc* d, void* stream) {
+  if (!d) return VILCO_ERR_BADARG;
+  const float *q = d->q, *k = d->k, *v = d->v, *bias = d->bias;
+  const int32_t* kv_len = d->kv_len;
+  const int32_t B = d->B, H = d->H, Tq = d->Tq, Tk = d->Tk, hd = d->hd, mode = d->mode, window = d->window, precision = d->precision;
+  const float scale = d->scale, drop_p = d->drop_p;
+  const uint32_t drop_seed = d->drop_seed;
+  const vilco_attn_amax_in* amax_in = d->amax_in;
+  void* workspace = d->workspace;
+  const size_t workspace_bytes = d->workspace_bytes;
+  const float *o = d->o, *lse = d->lse, *dout = d->dout;
+  float *dq = d->dq, *dk = d->dk, *dv = d->dv, *dbias = d->dbias;
+  float *dq_amax = d->dq_amax, *dk_amax = d->dk_amax, *dv_amax = d->dv_amax, *dbias_amax = d->dbias_amax;
+  void* ds_planes = d->ds_planes;
+  const size_t ds_planes_bytes = d->ds_planes_bytes;
   int rc = check_common(B, H, Tq, Tk, hd, mode, precision, window);
   if (!(drop_p >= 0.f) || drop_p >= 1.f) return VILCO_ERR_BADARG;
   if (rc != VILCO_OK) return rc;

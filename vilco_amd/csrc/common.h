@@ -138,5 +138,23 @@ constexpr long VILCO_PACK_HDR = VILCO_AMAX_MAX_BLOCKS * 4 + 512;
 // rows of a zero-padded per-sequence plane image (vilco_pack_item.seq_len): nseq * (T + 2) padded rows + enough zero rows for
 // both readers -- the forward / dX conv's overlapped spans and the weight-gradient product's contraction over the padded rows
 static inline long vilco_tap_plane_rows(long nseq, long T) { return (nseq * (T + 2) + 31) / 32 * 32 + 64; }
+// Where a kernel that writes the fp16 x2 operand planes of its own output [rows][C] (LayerNorm forward, activation backward, the
+// hd = 64 attention forward) puts them inside a vilco_pack buffer: seq_len <= 0: natural rows (padded to 32, at least 32; C % 32 == 0:
+// no column padding); seq_len = T > 0: the convs' image above.  Returns the buffer's size in bytes; `planes` may be null (size only).
+struct VilcoPlaneView {
+  _Float16* p0;        // part 0, behind the header
+  long plane_stride;   // elements between the two parts
+  float* inv_scale;    // {1/s, s} in the header
+  long rows_out;       // rows of one plane
+};
+static inline size_t vilco_plane_view(void* planes, long rows, long C, long seq_len, VilcoPlaneView* v) {
+  const long rows32 = (rows + 31) / 32 * 32;
+  v->rows_out = seq_len > 0 ? vilco_tap_plane_rows(rows / seq_len, seq_len) : (rows32 > 0 ? rows32 : 32);
+  v->plane_stride = seq_len > 0 ? (v->rows_out * C + 7) / 8 * 8 : v->rows_out * C;
+  unsigned char* u = reinterpret_cast<unsigned char*>(planes);
+  v->p0 = u ? reinterpret_cast<_Float16*>(u + VILCO_PACK_HDR) : nullptr;
+  v->inv_scale = u ? reinterpret_cast<float*>(u) + VILCO_AMAX_MAX_BLOCKS : nullptr;
+  return (size_t)(VILCO_PACK_HDR + v->plane_stride * 4);
+}
 void vilco_defer_push_rr(const float* ws, float* out0, float* out1, int nrows, int ncols, int split);
 void vilco_defer_push_sk(const float* part, float* out, long split_stride, long ldc, int M, int N, int ksplit);

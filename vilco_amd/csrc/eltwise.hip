@@ -563,19 +563,15 @@ extern "C" size_t vilco_colsum_workspace(int64_t rows, int32_t C) {
   return (size_t)col_blocks(rows) * (size_t)C * sizeof(float);
 }
 
-extern "C" int vilco_scale_add_bwd(const float* dout, const float* bval, const float* colscale,
-                                   const float* rowscale, const int32_t* len, int32_t mask_a,
-                                   float* da, float* db, float* dcolscale, int32_t B, int32_t T,
-                                   int32_t C, void* workspace, size_t workspace_bytes, void* stream) {
-  return vilco_scale_add_bwd_amax(dout, bval, colscale, rowscale, len, mask_a, da, db, dcolscale, B, T, C, workspace, workspace_bytes,
-                                  nullptr, nullptr, stream);
-}
-
-extern "C" int vilco_scale_add_bwd_amax(const float* dout, const float* bval, const float* colscale,
-                                        const float* rowscale, const int32_t* len, int32_t mask_a,
-                                        float* da, float* db, float* dcolscale, int32_t B, int32_t T,
-                                        int32_t C, void* workspace, size_t workspace_bytes, float* db_amax_parts,
-                                        int32_t* n_parts, void* stream) {
+extern "C" int vilco_scale_add_bwd(const vilco_scale_add_bwd_desc* d, void* stream) {
+  if (!d) return VILCO_ERR_BADARG;
+  const float *dout = d->dout, *bval = d->bval, *colscale = d->colscale, *rowscale = d->rowscale;
+  const int32_t* len = d->len;
+  float *da = d->da, *db = d->db, *dcolscale = d->dcolscale, *db_amax_parts = d->db_amax_parts;
+  int32_t* n_parts = d->n_parts;
+  const int32_t mask_a = d->mask_a, B = d->B, T = d->T, C = d->C;
+  void* workspace = d->workspace;
+  const size_t workspace_bytes = d->workspace_bytes;
   if (n_parts) *n_parts = 0;
   if (!dout || B < 0 || T < 0 || C <= 0) return VILCO_ERR_BADARG;
   if (dcolscale && !bval) return VILCO_ERR_BADARG;
@@ -642,71 +638,40 @@ extern "C" int vilco_axpby(float* out, const float* a, const float* b, float alp
   return vilco_launch_status();
 }
 
-extern "C" int vilco_act_bwd(const float* dy, const float* aux, float* dz, float* dbias, int32_t act,
-                             const int32_t* len, int32_t T, int64_t rows, int32_t C, float drop_p,
-                             uint32_t drop_seed, void* workspace, size_t workspace_bytes, void* stream) {
-  return vilco_act_bwd_amax(dy, aux, dz, dbias, act, len, T, rows, C, drop_p, drop_seed, workspace, workspace_bytes, nullptr,
-                            nullptr, stream);
-}
-
-extern "C" int vilco_act_bwd_amax(const float* dy, const float* aux, float* dz, float* dbias, int32_t act,
-                                  const int32_t* len, int32_t T, int64_t rows, int32_t C, float drop_p,
-                                  uint32_t drop_seed, void* workspace, size_t workspace_bytes, float* amax_parts,
-                                  int32_t* n_parts, void* stream) {
-  return vilco_act_bwd_planes(dy, aux, dz, dbias, act, len, T, rows, C, drop_p, drop_seed, workspace, workspace_bytes, amax_parts,
-                              n_parts, nullptr, 0, nullptr, 0, nullptr, stream);
-}
-
-extern "C" int vilco_act_bwd_planes(const float* dy, const float* aux, float* dz, float* dbias, int32_t act,
-                                    const int32_t* len, int32_t T, int64_t rows, int32_t C, float drop_p,
-                                    uint32_t drop_seed, void* workspace, size_t workspace_bytes, float* amax_parts,
-                                    int32_t* n_parts, const float* dy_amax, int32_t n_dy_amax, void* planes, size_t planes_bytes,
-                                    const float* row_mask, void* stream) {
-  return vilco_act_bwd_planes_seq(dy, aux, dz, dbias, act, len, T, rows, C, drop_p, drop_seed, workspace, workspace_bytes, amax_parts,
-                                  n_parts, dy_amax, n_dy_amax, planes, planes_bytes, 0, row_mask, stream);
-}
-
 extern "C" size_t vilco_act_bwd_planes_bytes(int64_t rows, int32_t C, int32_t seq_len) {
   if (rows < 0 || C <= 0 || seq_len < 0) return 0;
-  if (seq_len > 0) return (size_t)(VILCO_PACK_HDR + (vilco_tap_plane_rows(rows / seq_len, seq_len) * C + 7) / 8 * 8 * 4);
-  const long rows32 = (rows + 31) / 32 * 32;
-  return (size_t)(VILCO_PACK_HDR + (rows32 > 0 ? rows32 : 32) * (long)C * 4);
+  VilcoPlaneView v;
+  return vilco_plane_view(nullptr, rows, C, seq_len, &v);
 }
 
-extern "C" int vilco_act_bwd_planes_seq(const float* dy, const float* aux, float* dz, float* dbias, int32_t act,
-                                        const int32_t* len, int32_t T, int64_t rows, int32_t C, float drop_p,
-                                        uint32_t drop_seed, void* workspace, size_t workspace_bytes, float* amax_parts,
-                                        int32_t* n_parts, const float* dy_amax, int32_t n_dy_amax, void* planes,
-                                        size_t planes_bytes, int32_t seq_len, const float* row_mask, void* stream) {
+extern "C" int vilco_act_bwd(const vilco_act_bwd_desc* d, void* stream) {
+  if (!d) return VILCO_ERR_BADARG;
+  const float *dy = d->dy, *aux = d->aux, *dy_amax = d->dy_amax, *row_mask = d->row_mask;
+  float *dz = d->dz, *dbias = d->dbias, *amax_parts = d->amax_parts;
+  int32_t* n_parts = d->n_parts;
+  const int32_t* len = d->len;
+  const int32_t act = d->act, T = d->T, C = d->C, n_dy_amax = d->n_dy_amax, seq_len = d->seq_len;
+  const int64_t rows = d->rows;
+  const float drop_p = d->drop_p;
+  const uint32_t drop_seed = d->drop_seed;
+  void *workspace = d->workspace, *planes = d->planes;
+  const size_t workspace_bytes = d->workspace_bytes;
   if (n_parts) *n_parts = 0;
   if (!(drop_p >= 0.f) || drop_p >= 1.f) return VILCO_ERR_BADARG;
   if (!dy || (!dz && !planes) || rows < 0 || C <= 0 || act < 0 || act > 2 || seq_len < 0) return VILCO_ERR_BADARG;
   PlaneOut po = {nullptr, 0, nullptr, 0, 1.f, nullptr, 0, 0, 0};
-  if (planes && seq_len > 0) {
-    // the k=3 convs' zero-padded per-sequence image (vilco_pack_item.seq_len): C % 8 == 0, whole sequences
-    if (!dy_amax || n_dy_amax <= 0 || (C % 8) != 0 || (rows % seq_len) != 0 || !vilco_aligned(planes, 256)) return VILCO_ERR_BADARG;
-    if (planes_bytes < vilco_act_bwd_planes_bytes(rows, C, seq_len)) return VILCO_ERR_WORKSPACE;
-    unsigned char* u = reinterpret_cast<unsigned char*>(planes);
-    po.p0 = reinterpret_cast<_Float16*>(u + VILCO_PACK_HDR);
-    po.rows_out = vilco_tap_plane_rows(rows / seq_len, seq_len);
-    po.plane_stride = (po.rows_out * C + 7) / 8 * 8;
+  if (planes) {
+    // the planes of dz (precision 3) need the partial maxima of |dy| for the scale bound; vilco_pack's layout for [rows][C] needs
+    // C % 32 == 0, the k=3 convs' zero-padded per-sequence image (vilco_pack_item.seq_len) C % 8 == 0 and whole sequences
+    if (!dy_amax || n_dy_amax <= 0 || !vilco_aligned(planes, 256)) return VILCO_ERR_BADARG;
+    if (seq_len > 0 ? ((C % 8) != 0 || (rows % seq_len) != 0) : (C % 32) != 0) return VILCO_ERR_BADARG;
+    VilcoPlaneView v;
+    if (d->planes_bytes < vilco_plane_view(planes, rows, C, seq_len, &v)) return VILCO_ERR_WORKSPACE;
+    po.p0 = v.p0; po.plane_stride = v.plane_stride; po.inv_scale = v.inv_scale;
+    po.rows32 = po.rows_out = v.rows_out;
     po.seqT = seq_len;
     po.in_amax = dy_amax; po.n_in_amax = n_dy_amax;
     po.bound_factor = (1.f / (1.f - drop_p)) * (act == VILCO_ACT_GELU ? 1.13f : 1.f);
-    po.inv_scale = reinterpret_cast<float*>(u) + VILCO_AMAX_MAX_BLOCKS;
-    po.rows32 = po.rows_out;
-  } else if (planes) {
-    // the planes of dz in vilco_pack's layout (precision 3, [rows][C]); needs the partial maxima of |dy| for the scale bound
-    if (!dy_amax || n_dy_amax <= 0 || (C % 32) != 0 || !vilco_aligned(planes, 256)) return VILCO_ERR_BADARG;
-    const long rows32 = (rows + 31) / 32 * 32;
-    if (planes_bytes < (size_t)(VILCO_PACK_HDR + (rows32 > 0 ? rows32 : 32) * (long)C * 4)) return VILCO_ERR_WORKSPACE;
-    unsigned char* u = reinterpret_cast<unsigned char*>(planes);
-    po.p0 = reinterpret_cast<_Float16*>(u + VILCO_PACK_HDR);
-    po.plane_stride = (rows32 > 0 ? rows32 : 32) * (long)C;
-    po.in_amax = dy_amax; po.n_in_amax = n_dy_amax;
-    po.bound_factor = (1.f / (1.f - drop_p)) * (act == VILCO_ACT_GELU ? 1.13f : 1.f);
-    po.inv_scale = reinterpret_cast<float*>(u) + VILCO_AMAX_MAX_BLOCKS;
-    po.rows32 = rows32;
   }
   if (act != VILCO_ACT_NONE && !aux) return VILCO_ERR_BADARG;
   if (len && T <= 0) return VILCO_ERR_BADARG;

@@ -351,29 +351,21 @@ void vilco_reduce_rows(const float* ws, float* out0, float* out1, int nrows, int
     default: LN_CASE_B(16, KERNEL, R_, __VA_ARGS__)                                     \
   }
 
-extern "C" int vilco_layernorm_fwd(const float* x, const float* gamma, const float* beta, float* y,
-                                   float* mean, float* rstd, int64_t rows, int32_t C, float eps,
-                                   int32_t relu, void* stream) {
-  return vilco_layernorm_fwd_amax(x, gamma, beta, y, mean, rstd, rows, C, eps, relu, nullptr, nullptr, stream);
-}
-
-extern "C" int vilco_layernorm_fwd_amax(const float* x, const float* gamma, const float* beta, float* y,
-                                        float* mean, float* rstd, int64_t rows, int32_t C, float eps,
-                                        int32_t relu, float* amax_parts, int32_t* n_parts, void* stream) {
-  return vilco_layernorm_fwd_planes(x, gamma, beta, y, mean, rstd, rows, C, eps, relu, amax_parts, n_parts, nullptr, 0, 0, nullptr, 0,
-                                    stream);
-}
-
 extern "C" size_t vilco_layernorm_planes_bytes(int64_t rows, int32_t C, int32_t seq_len) {
   if (rows <= 0 || C <= 0) return 0;
-  if (seq_len > 0) return (size_t)(VILCO_PACK_HDR + (vilco_tap_plane_rows(rows / seq_len, seq_len) * C + 7) / 8 * 8 * 4);
-  return (size_t)(VILCO_PACK_HDR + (rows + 31) / 32 * 32 * (long)C * 4);
+  VilcoPlaneView v;
+  return vilco_plane_view(nullptr, rows, C, seq_len, &v);
 }
 
-extern "C" int vilco_layernorm_fwd_planes(const float* x, const float* gamma, const float* beta, float* y,
-                                          float* mean, float* rstd, int64_t rows, int32_t C, float eps,
-                                          int32_t relu, float* amax_parts, int32_t* n_parts, void* planes, size_t planes_bytes,
-                                          int32_t seq_len, const float* row_mask, int64_t mask_rows, void* stream) {
+extern "C" int vilco_layernorm_fwd(const vilco_ln_fwd_desc* d, void* stream) {
+  if (!d) return VILCO_ERR_BADARG;
+  const float *x = d->x, *gamma = d->gamma, *beta = d->beta, *row_mask = d->row_mask;
+  float *y = d->y, *mean = d->mean, *rstd = d->rstd, *amax_parts = d->amax_parts;
+  int32_t* n_parts = d->n_parts;
+  const int64_t rows = d->rows, mask_rows = d->mask_rows;
+  const int32_t C = d->C, relu = d->relu, seq_len = d->seq_len;
+  const float eps = d->eps;
+  void* planes = d->planes;
   if (!x || !y || rows < 0 || C <= 0) return VILCO_ERR_BADARG;
   if (n_parts) *n_parts = 0;
   if (rows == 0) return VILCO_OK;
@@ -385,12 +377,9 @@ extern "C" int vilco_layernorm_fwd_planes(const float* x, const float* gamma, co
     // natural rows need C % 32 == 0 (no column padding); the convs' image C % 8 == 0 and whole sequences
     if (seq_len < 0 || !vilco_aligned(planes, 256)) return VILCO_ERR_BADARG;
     if (seq_len > 0 ? ((C % 8) != 0 || (rows % seq_len) != 0) : (C % 32) != 0) return VILCO_ERR_UNSUPPORTED;
-    if (planes_bytes < vilco_layernorm_planes_bytes(rows, C, seq_len)) return VILCO_ERR_WORKSPACE;
-    unsigned char* u = reinterpret_cast<unsigned char*>(planes);
-    po.p0 = reinterpret_cast<_Float16*>(u + VILCO_PACK_HDR);
-    po.rows_out = seq_len > 0 ? vilco_tap_plane_rows(rows / seq_len, seq_len) : (rows + 31) / 32 * 32;
-    po.plane_stride = seq_len > 0 ? (po.rows_out * C + 7) / 8 * 8 : po.rows_out * (long)C;
-    po.inv_scale = reinterpret_cast<float*>(u) + VILCO_AMAX_MAX_BLOCKS;
+    VilcoPlaneView v;
+    if (d->planes_bytes < vilco_plane_view(planes, rows, C, seq_len, &v)) return VILCO_ERR_WORKSPACE;
+    po.p0 = v.p0; po.plane_stride = v.plane_stride; po.inv_scale = v.inv_scale; po.rows_out = v.rows_out;
     po.seqT = seq_len;
   }
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
@@ -415,28 +404,15 @@ extern "C" size_t vilco_layernorm_bwd_workspace(int64_t rows, int32_t C) {
   return (size_t)ln_blocks(rows) * 2 * (size_t)C * sizeof(float);
 }
 
-extern "C" int vilco_layernorm_bwd(const float* dy, const float* x, const float* y,
-                                   const float* gamma, const float* mean, const float* rstd,
-                                   float* dx, float* dgamma, float* dbeta, int64_t rows, int32_t C,
-                                   int32_t relu, void* workspace, size_t workspace_bytes,
-                                   void* stream) {
-  return vilco_layernorm_bwd_res(dy, x, y, gamma, mean, rstd, nullptr, dx, dgamma, dbeta, rows, C, relu, workspace, workspace_bytes, stream);
-}
-
-extern "C" int vilco_layernorm_bwd_res(const float* dy, const float* x, const float* y,
-                                       const float* gamma, const float* mean, const float* rstd, const float* dres,
-                                       float* dx, float* dgamma, float* dbeta, int64_t rows, int32_t C,
-                                       int32_t relu, void* workspace, size_t workspace_bytes,
-                                       void* stream) {
-  return vilco_layernorm_bwd_res_amax(dy, x, y, gamma, mean, rstd, dres, dx, dgamma, dbeta, rows, C, relu, workspace, workspace_bytes,
-                                      nullptr, nullptr, stream);
-}
-
-extern "C" int vilco_layernorm_bwd_res_amax(const float* dy, const float* x, const float* y,
-                                            const float* gamma, const float* mean, const float* rstd, const float* dres,
-                                            float* dx, float* dgamma, float* dbeta, int64_t rows, int32_t C,
-                                            int32_t relu, void* workspace, size_t workspace_bytes,
-                                            float* dx_amax_parts, int32_t* n_parts, void* stream) {
+extern "C" int vilco_layernorm_bwd(const vilco_ln_bwd_desc* d, void* stream) {
+  if (!d) return VILCO_ERR_BADARG;
+  const float *dy = d->dy, *x = d->x, *y = d->y, *gamma = d->gamma, *mean = d->mean, *rstd = d->rstd, *dres = d->dres;
+  float *dx = d->dx, *dgamma = d->dgamma, *dbeta = d->dbeta, *dx_amax_parts = d->dx_amax_parts;
+  int32_t* n_parts = d->n_parts;
+  const int64_t rows = d->rows;
+  const int32_t C = d->C, relu = d->relu;
+  void* workspace = d->workspace;
+  const size_t workspace_bytes = d->workspace_bytes;
   if (n_parts) *n_parts = 0;
   if (!dy || !x || !mean || !rstd || !dx || rows < 0 || C <= 0) return VILCO_ERR_BADARG;
   if (relu && !y) return VILCO_ERR_BADARG;

@@ -321,19 +321,21 @@ extern "C" int vilco_grad_norm(const int64_t* ptrs, const int64_t* numel, const 
   return vilco_launch_status();
 }
 
-extern "C" int vilco_optim_step_dev(int32_t kind, const int64_t* ptrs, const int64_t* numel, const int32_t* chunk_tensor,
-                                    const int64_t* chunk_off, const int32_t* group, int32_t n, int32_t nchunks,
-                                    int32_t chunk, const float* lr, const float* wd, int32_t ngroups, float beta1,
-                                    float beta2, float eps, float momentum, const float* tensor_step,
-                                    const float* norm_coef, float* chunk_amax, const float* lr_dev, void* stream) {
+extern "C" int vilco_optim_step(const vilco_optim_desc* d, void* stream) {
+  if (!d) return VILCO_ERR_BADARG;
+  const int64_t *ptrs = d->ptrs, *numel = d->numel, *chunk_off = d->chunk_off;
+  const int32_t *chunk_tensor = d->chunk_tensor, *group = d->group;
+  const int32_t kind = d->kind, n = d->n, nchunks = d->nchunks, chunk = d->chunk, ngroups = d->ngroups;
+  const float *lr = d->lr, *wd = d->wd, *tensor_step = d->tensor_step, *norm_coef = d->norm_coef, *lr_dev = d->lr_dev;
+  float* chunk_amax = d->chunk_amax;
   if (!ptrs || !numel || !chunk_tensor || !chunk_off || !group || !lr || !wd || n < 0 || nchunks < 0 || chunk <= 0)
     return VILCO_ERR_BADARG;
   if (ngroups < 1 || ngroups > 8 || !tensor_step || (kind != 0 && kind != 1)) return VILCO_ERR_BADARG;
   if (nchunks == 0) return VILCO_OK;
   Hyper h;
   for (int i = 0; i < 8; ++i) { h.lr[i] = i < ngroups ? lr[i] : 0.f; h.wd[i] = i < ngroups ? wd[i] : 0.f; }
-  h.beta1 = beta1; h.beta2 = beta2; h.eps = eps;
-  h.momentum = momentum;
+  h.beta1 = d->beta1; h.beta2 = d->beta2; h.eps = d->eps;
+  h.momentum = d->momentum;
   h.tstep = tensor_step;
   h.lr_dev = lr_dev;
   MultiArgs a{reinterpret_cast<const long*>(ptrs), reinterpret_cast<const long*>(numel), chunk_tensor,
@@ -342,22 +344,4 @@ extern "C" int vilco_optim_step_dev(int32_t kind, const int64_t* ptrs, const int
   if (kind == 0) hipLaunchKernelGGL(adamw_kernel, dim3(nchunks), dim3(OPT_THREADS), 0, s, a, h, norm_coef, chunk_amax);
   else hipLaunchKernelGGL(sgd_kernel, dim3(nchunks), dim3(OPT_THREADS), 0, s, a, h, norm_coef, chunk_amax);
   return vilco_launch_status();
-}
-
-extern "C" int vilco_optim_step_amax(int32_t kind, const int64_t* ptrs, const int64_t* numel, const int32_t* chunk_tensor,
-                                     const int64_t* chunk_off, const int32_t* group, int32_t n, int32_t nchunks,
-                                     int32_t chunk, const float* lr, const float* wd, int32_t ngroups, float beta1,
-                                     float beta2, float eps, float momentum, const float* tensor_step,
-                                     const float* norm_coef, float* chunk_amax, void* stream) {
-  return vilco_optim_step_dev(kind, ptrs, numel, chunk_tensor, chunk_off, group, n, nchunks, chunk, lr, wd, ngroups, beta1,
-                              beta2, eps, momentum, tensor_step, norm_coef, chunk_amax, nullptr, stream);
-}
-
-extern "C" int vilco_optim_step(int32_t kind, const int64_t* ptrs, const int64_t* numel, const int32_t* chunk_tensor,
-                                const int64_t* chunk_off, const int32_t* group, int32_t n, int32_t nchunks,
-                                int32_t chunk, const float* lr, const float* wd, int32_t ngroups, float beta1,
-                                float beta2, float eps, float momentum, const float* tensor_step,
-                                const float* norm_coef, void* stream) {
-  return vilco_optim_step_amax(kind, ptrs, numel, chunk_tensor, chunk_off, group, n, nchunks, chunk, lr, wd, ngroups, beta1,
-                               beta2, eps, momentum, tensor_step, norm_coef, nullptr, stream);
 }

@@ -15,7 +15,7 @@ and from then on an iteration is: copy the batch into the static input buffers, 
 between backward and update: a gradient all-reduce, an EWC / MAS penalty), hand the learning rates over, replay 2.
 What must differ between replays lives in device memory: the inputs, the dropout step word (common.h: vilco_step_seed),
 the stochastic-depth factors (torch's graph-safe Philox draw, captured), the loss-normaliser EMA, the optimizer's step
-counts and learning rates (vilco_optim_step_dev), the narration memory bank and its ring word (csrc/ssl.hip: the update
+counts and learning rates (vilco_optim_desc.lr_dev), the narration memory bank and its ring word (csrc/ssl.hip: the update
 advances the word on the device by the number of narrated clips, which differs from batch to batch).
 
 What is captured is what ran: graphs are keyed by the input shapes, task id and the identity / requires_grad of every

@@ -678,7 +678,7 @@ def _cached(w, tag, build):
 
 
 def tag_weight_amax(p, parts, n):
-    """max|p| partials of parameter p left by whoever wrote it (FusedOptimizer.step: vilco_optim_step_amax); valid until
+    """max|p| partials of parameter p left by whoever wrote it (FusedOptimizer.step: vilco_optim_desc.chunk_amax); valid until
     p's version counter or the weight generation moves.  Call after weights_changed()."""
     p._vilco_wamax = (parts, int(n), p._version, _weight_gen[0])
 
@@ -705,7 +705,7 @@ def weight_planes(w, rows, cols):
 
 
 # dz of a layer goes nowhere but into its two backward products: `_act_bwd(planes=True)` has the kernel write dz as operand planes
-# (vilco_act_bwd_planes: scale from a bound on max|dz|, no pack launch, no fp32 dz) when dy carries its producer's amax partials.
+# (vilco_act_bwd_desc.planes: scale from a bound on max|dz|, no pack launch, no fp32 dz) when dy carries its producer's amax partials.
 # VILCO_PRODUCER_PLANES=0: fp32 dz + pack, as before.
 producer_planes = os.environ.get("VILCO_PRODUCER_PLANES", "1") != "0"
 ln_planes = os.environ.get("VILCO_LN_PLANES", "1") != "0"          # the LayerNorm half of it (ops.layernorm(planes=...))
@@ -732,15 +732,12 @@ def _act_bwd(dy, aux, act, lens, T, want_bias, drop=(0.0, 0), bias_param=None, p
         ws = _ws(lib.vilco_colsum_workspace(rows, Cn), dy.device) if want_bias else None
         parts = torch.empty(AMAX_PARTS, dtype=torch.float32, device=dy.device) if (produce_amax and _precision == 3 and pz is None) else None
         n = C.c_int32(0)
-        if pz is None:
-            _lib.check(lib.vilco_act_bwd_planes(dy.data_ptr(), _p(aux), dz.data_ptr(), _p(db), act, _p(lens),
-                                                int(T or 0), rows, Cn, float(drop[0]), int(drop[1]), _p(ws), ws.numel() if ws is not None else 0,
-                                                _p(parts), C.byref(n), None, 0, None, 0, _p(row_mask), _stream()))
-        else:
-            _lib.check(lib.vilco_act_bwd_planes_seq(dy.data_ptr(), _p(aux), None, _p(db), act, _p(lens),
-                                                    int(T or 0), rows, Cn, float(drop[0]), int(drop[1]), _p(ws), ws.numel() if ws is not None else 0,
-                                                    None, None, dy_parts.data_ptr(), int(dy_n), pz.data_ptr(), pz.numel(), seq,
-                                                    _p(row_mask), _stream()))
+        d = _lib.ActBwdDesc(dy=dy.data_ptr(), aux=_p(aux), dz=_p(dz), dbias=_p(db), act=act, len=_p(lens), T=int(T or 0), rows=rows,
+                            C=Cn, drop_p=float(drop[0]), drop_seed=int(drop[1]), workspace=_p(ws),
+                            workspace_bytes=ws.numel() if ws is not None else 0, amax_parts=_p(parts), n_parts=C.addressof(n),
+                            dy_amax=_p(dy_parts), n_dy_amax=int(dy_n), planes=_p(pz),
+                            planes_bytes=pz.numel() if pz is not None else 0, seq_len=seq, row_mask=_p(row_mask))
+        _lib.check(lib.vilco_act_bwd(C.byref(d), _stream()))
         dfr.hold(db)
     if parts is not None:
         _tag_amax(dz, parts, n.value)
@@ -1125,10 +1122,11 @@ class _LayerNorm(torch.autograd.Function):
         if ok:
             nbytes = lib.vilco_layernorm_planes_bytes(rows, Cn, seq)
             buf = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
-        _lib.check(lib.vilco_layernorm_fwd_planes(x.data_ptr(), _p(gamma), _p(beta), y.data_ptr(),
-                                                  mean.data_ptr(), rstd.data_ptr(), rows, Cn, eps,
-                                                  int(relu), _p(parts), C.byref(n), _p(buf), buf.numel() if buf is not None else 0,
-                                                  seq, _p(row_mask), row_mask.numel() if row_mask is not None else 0, _stream()))
+        d = _lib.LnFwdDesc(x=x.data_ptr(), gamma=_p(gamma), beta=_p(beta), y=y.data_ptr(), mean=mean.data_ptr(), rstd=rstd.data_ptr(),
+                           rows=rows, C=Cn, eps=eps, relu=int(relu), amax_parts=_p(parts), n_parts=C.addressof(n), planes=_p(buf),
+                           planes_bytes=buf.numel() if buf is not None else 0, seq_len=seq, row_mask=_p(row_mask),
+                           mask_rows=row_mask.numel() if row_mask is not None else 0)
+        _lib.check(lib.vilco_layernorm_fwd(C.byref(d), _stream()))
         ctx.relu = bool(relu)
         ctx.save_for_backward(x, gamma, mean, rstd, y if relu else None)
         _LayerNorm.last_amax = (parts, n.value)          # picked up by `layernorm` (attributes set here do not survive apply)
@@ -1159,10 +1157,11 @@ class _LayerNorm(torch.autograd.Function):
             parts = (torch.empty(AMAX_PARTS, dtype=torch.float32, device=x.device)
                      if (ln_bwd_amax and produce_amax and producer_planes and _precision == 3) else None)
             n = C.c_int32(0)
-            _lib.check(lib.vilco_layernorm_bwd_res_amax(dy.data_ptr(), x.data_ptr(), _p(y), _p(gamma),
-                                                        mean.data_ptr(), rstd.data_ptr(), _p(dskip), dx.data_ptr(),
-                                                        dg.data_ptr(), db.data_ptr(), rows, Cn, int(ctx.relu),
-                                                        ws.data_ptr(), ws.numel(), _p(parts), C.byref(n), _stream()))
+            d = _lib.LnBwdDesc(dy=dy.data_ptr(), x=x.data_ptr(), y=_p(y), gamma=_p(gamma), mean=mean.data_ptr(), rstd=rstd.data_ptr(),
+                               dres=_p(dskip), dx=dx.data_ptr(), dgamma=dg.data_ptr(), dbeta=db.data_ptr(), rows=rows, C=Cn,
+                               relu=int(ctx.relu), workspace=ws.data_ptr(), workspace_bytes=ws.numel(),
+                               dx_amax_parts=_p(parts), n_parts=C.addressof(n))
+            _lib.check(lib.vilco_layernorm_bwd(C.byref(d), _stream()))
             dfr.hold(dg, db)
             if parts is not None and n.value > 0:
                 _tag_amax(dx, parts, n.value)
@@ -1180,7 +1179,7 @@ def layernorm(x, gamma, beta, eps=1e-5, relu=False, planes=None, row_mask=None, 
     skip: return (y, x_skip) -- x_skip is x as an output of this op; use it for the residual connection around the branch
     that y feeds, and the backward kernel adds the skip gradient to dx itself (see _LayerNorm.forward).
     planes: "nat" when y feeds a Linear, "seq" when it feeds a k=3 conv -- the kernel then writes y's operand planes as well
-    (vilco_layernorm_fwd_planes) and the consumer's `pack` / `pack_tap` finds them on the tensor.
+    (vilco_ln_fwd_desc.planes) and the consumer's `pack` / `pack_tap` finds them on the tensor.
     row_mask (relu only): a contiguous 0 / 1 float mask over the token rows, repeated over the batch -- y[b, t] *= row_mask[t]."""
     _LayerNorm.last_planes = None
     y = _LayerNorm.apply(x, gamma, beta, float(eps), bool(relu), planes, row_mask, bool(skip and fold_skip_grads and x.requires_grad))
@@ -1305,10 +1304,12 @@ class _ScaleAdd(torch.autograd.Function):
             n = C.c_int32(0)
             with _Deferring(colscale if need_cs else None) as dfr:
                 ws = _ws(lib.vilco_colsum_workspace(B * T, Cn), b.device) if need_cs else None
-                _lib.check(lib.vilco_scale_add_bwd_amax(
-                    dout.data_ptr(), b.data_ptr(), _p(colscale), _p(rowscale), _p(lens), ctx.mask_a,
-                    None if plain_a else _p(da), None if plain_b else _p(db), _p(dcs), B, T, Cn, _p(ws),
-                    ws.numel() if ws is not None else 0, _p(parts), C.byref(n), _stream()))
+                d = _lib.ScaleAddBwdDesc(dout=dout.data_ptr(), bval=b.data_ptr(), colscale=_p(colscale), rowscale=_p(rowscale),
+                                         len=_p(lens), mask_a=ctx.mask_a, da=None if plain_a else _p(da),
+                                         db=None if plain_b else _p(db), dcolscale=_p(dcs), B=B, T=T, C=Cn, workspace=_p(ws),
+                                         workspace_bytes=ws.numel() if ws is not None else 0, db_amax_parts=_p(parts),
+                                         n_parts=C.addressof(n))
+                _lib.check(lib.vilco_scale_add_bwd(C.byref(d), _stream()))
                 dfr.hold(dcs)
             if parts is not None:
                 _tag_amax(db, parts, n.value)
@@ -1507,10 +1508,12 @@ def _flash_fwd(q, k, v, bias, kv_len, H, scale, mode, drop=(0.0, 0), window=0):
     if (producer_planes and attn_planes and _pack_cache and _reuse_packs and _precision == 3 and B * Tq > 0 and
             lib.vilco_attn_planes_supported(Tq, Tk, Cn // H, int(mode), _precision, int(bias is not None), float(drop[0]))):
         planes = torch.empty(lib.vilco_pack_bytes(B * Tq, Cn, 3), dtype=torch.uint8, device=q.device)
-    _lib.check(lib.vilco_attn_fwd_planes(q.data_ptr(), k.data_ptr(), v.data_ptr(), _p(bias), _p(kv_len), o.data_ptr(),
-                                         lse.data_ptr(), B, H, Tq, Tk, Cn // H, scale, mode, int(window), _precision, float(drop[0]),
-                                         int(drop[1]), C.byref(ain[0]) if ain else None, _p(am), ws.data_ptr(), nws,
-                                         _p(planes), planes.numel() if planes is not None else 0, _stream()))
+    d = _lib.AttnDesc(q=q.data_ptr(), k=k.data_ptr(), v=v.data_ptr(), bias=_p(bias), kv_len=_p(kv_len), o=o.data_ptr(),
+                      lse=lse.data_ptr(), B=B, H=H, Tq=Tq, Tk=Tk, hd=Cn // H, scale=scale, mode=mode, window=int(window),
+                      precision=_precision, drop_p=float(drop[0]), drop_seed=int(drop[1]), amax_in=C.addressof(ain[0]) if ain else None,
+                      workspace=ws.data_ptr(), workspace_bytes=nws, o_amax=_p(am), o_planes=_p(planes),
+                      o_planes_bytes=planes.numel() if planes is not None else 0)
+    _lib.check(lib.vilco_attn_fwd(C.byref(d), _stream()))
     if na:
         _FlashAttention.last_amax = (am, na)
     _FlashAttention.last_planes = (planes, _cache_mark()) if planes is not None else None
@@ -1526,7 +1529,7 @@ def _attach_attn_planes(o):
     return o
 
 
-# XLNet backward: dS as operand planes of the unshifted view straight from the dQ kernel (vilco_attn_bwd_dsplanes) instead of
+# XLNet backward: dS as operand planes of the unshifted view straight from the dQ kernel (vilco_attn_desc.ds_planes) instead of
 # fp32 dS + a pack of it.  The kernel writes the band only; everything else in the buffer must be zero and stays zero, so ONE
 # buffer per (device, B*H, T) is zeroed when first needed and reused by every later backward (1.36 GB at config P; a step
 # captured as a hipGraph has met it in the eager iterations before the capture).  VILCO_XL_DS_PLANES=0: the fp32 dS + pack path.
@@ -1566,33 +1569,27 @@ def _flash_bwd(q, k, v, bias, kv_len, o, lse, do, H, scale, mode, want_dbias, dr
     B, Tq, Cn = q.shape
     Tk = k.shape[1]
     dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
-    if ds_planes is not None:
-        nws = lib.vilco_attn_bwd_workspace(B, H, Tq, Tk, Cn // H, _precision)
-        ws = _ws(nws, q.device)
-        ain = _attn_amax_in(q, k, v, do)
-        _lib.check(lib.vilco_attn_bwd_dsplanes(q.data_ptr(), k.data_ptr(), v.data_ptr(), _p(bias), _p(kv_len), o.data_ptr(),
-                                               lse.data_ptr(), do.data_ptr(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), None,
-                                               B, H, Tq, Tk, Cn // H, scale, mode, int(window), _precision, float(drop[0]),
-                                               int(drop[1]), C.byref(ain[0]) if ain else None, None, None, None, None,
-                                               ws.data_ptr(), nws, ds_planes.data_ptr(), ds_planes.numel(), _stream()))
-        return dq, dk, dv, None
+    want_dbias = bool(want_dbias) and ds_planes is None
     dbias = torch.empty(B, H, Tq, Tk, dtype=torch.float32, device=q.device) if want_dbias else None
     nws = lib.vilco_attn_bwd_workspace(B, H, Tq, Tk, Cn // H, _precision)
     ws = _ws(nws, q.device)
-    nq = 0 if want_dbias else _attn_amax_parts(B, H, Tq, Cn // H, mode, bias, drop, 0)
-    nk = 0 if want_dbias else _attn_amax_parts(B, H, Tk, Cn // H, mode, bias, drop, 1)
+    nq = nk = nds = 0
+    if ds_planes is None and not want_dbias:
+        nq = _attn_amax_parts(B, H, Tq, Cn // H, mode, bias, drop, 0)
+        nk = _attn_amax_parts(B, H, Tk, Cn // H, mode, bias, drop, 1)
     am = torch.empty(nq + 2 * nk, dtype=torch.float32, device=q.device) if nq and nk else None
     aq, ak, av = (am[:nq], am[nq:nq + nk], am[nq + nk:]) if am is not None else (None, None, None)
     ain = _attn_amax_in(q, k, v, do)
-    nds = 0
     if want_dbias and bias is not None and produce_amax and _precision == 3 and mode == MASK_XLNET_REL and Tq == Tk:
         nds = int(lib.vilco_attn_amax_parts(B, H, Tq, Cn // H, int(mode), _precision, 2, float(drop[0]), 0))
     ads = torch.empty(nds, dtype=torch.float32, device=q.device) if nds else None
-    _lib.check(lib.vilco_attn_bwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), _p(bias), _p(kv_len), o.data_ptr(),
-                                  lse.data_ptr(), do.data_ptr(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(),
-                                  _p(dbias), B, H, Tq, Tk, Cn // H, scale, mode, int(window), _precision, float(drop[0]),
-                                  int(drop[1]), C.byref(ain[0]) if ain else None, _p(aq), _p(ak), _p(av), _p(ads), ws.data_ptr(),
-                                  nws, _stream()))
+    d = _lib.AttnDesc(q=q.data_ptr(), k=k.data_ptr(), v=v.data_ptr(), bias=_p(bias), kv_len=_p(kv_len), o=o.data_ptr(),
+                      lse=lse.data_ptr(), B=B, H=H, Tq=Tq, Tk=Tk, hd=Cn // H, scale=scale, mode=mode, window=int(window),
+                      precision=_precision, drop_p=float(drop[0]), drop_seed=int(drop[1]), amax_in=C.addressof(ain[0]) if ain else None,
+                      workspace=ws.data_ptr(), workspace_bytes=nws, dout=do.data_ptr(), dq=dq.data_ptr(), dk=dk.data_ptr(),
+                      dv=dv.data_ptr(), dbias=_p(dbias), dq_amax=_p(aq), dk_amax=_p(ak), dv_amax=_p(av), dbias_amax=_p(ads),
+                      ds_planes=_p(ds_planes), ds_planes_bytes=ds_planes.numel() if ds_planes is not None else 0)
+    _lib.check(lib.vilco_attn_bwd(C.byref(d), _stream()))
     if ads is not None:
         _tag_amax(dbias, ads, nds)
     if am is not None:
@@ -2169,8 +2166,8 @@ class _QkvPre(torch.autograd.Function):
         dev = x.device
         if h is None:        # nobody else needed h in forward: rebuild it (one LayerNorm pass) for the conv recomputation
             h = torch.empty_like(x)
-            _lib.check(lib.vilco_layernorm_fwd(x.data_ptr(), _p(g1), _p(b1), h.data_ptr(), None, None, B * T, Cn, ctx.eps1, 0,
-                                               _stream()))
+            d = _lib.LnFwdDesc(x=x.data_ptr(), gamma=_p(g1), beta=_p(b1), y=h.data_ptr(), rows=B * T, C=Cn, eps=ctx.eps1)
+            _lib.check(lib.vilco_layernorm_fwd(C.byref(d), _stream()))
         dys = [torch.zeros(B, To, Cn, dtype=torch.float32, device=dev) if g is None else g.contiguous() for g in (dq, dk, dv)]
         dcs = [torch.empty(B, To, Cn, dtype=torch.float32, device=dev) for _ in range(3)]
         dh = torch.empty_like(x)
@@ -2188,9 +2185,10 @@ class _QkvPre(torch.autograd.Function):
                                              B, T, Cn, ctx.stride, ws.data_ptr(), nws, _stream()))
             del dcs
             ws1 = _ws(lib.vilco_layernorm_bwd_workspace(B * T, Cn), dev)
-            _lib.check(lib.vilco_layernorm_bwd_res(dh.data_ptr(), x.data_ptr(), None, _p(g1), stats1[0].data_ptr(),
-                                                   stats1[1].data_ptr(), _p(dskip), dx.data_ptr(), dg1.data_ptr(), db1.data_ptr(),
-                                                   B * T, Cn, 0, ws1.data_ptr(), ws1.numel(), _stream()))
+            d = _lib.LnBwdDesc(dy=dh.data_ptr(), x=x.data_ptr(), gamma=_p(g1), mean=stats1[0].data_ptr(), rstd=stats1[1].data_ptr(),
+                               dres=_p(dskip), dx=dx.data_ptr(), dgamma=dg1.data_ptr(), dbeta=db1.data_ptr(), rows=B * T, C=Cn,
+                               workspace=ws1.data_ptr(), workspace_bytes=ws1.numel())
+            _lib.check(lib.vilco_layernorm_bwd(C.byref(d), _stream()))
             dfr.hold(dpar, dg1, db1)
         dws = [dpar[6 + 3 * j:9 + 3 * j].view_as(w) for j, w in enumerate((wq, wk, wv))]      # already [C][1][3] (qkvpre.hip)
         dgs = [dpar[2 * j].view_as(g) for j, g in enumerate((gq, gk, gv))]

@@ -232,13 +232,15 @@ class FusedOptimizer(optim.Optimizer):
                 plan['tstep'].add_(plan['inc'])
             plan['count'] += 1
             # the update also leaves max|p| of every chunk it wrote: the scale of next step's fp16 x2 weight planes
-            _lib.check(lib.vilco_optim_step_dev(0 if self.kind == "AdamW" else 1, ptrs.data_ptr(), plan['numel'].data_ptr(),
-                                                plan['chunk_tensor'].data_ptr(), plan['chunk_off'].data_ptr(),
-                                                plan['group'].data_ptr(), n, plan['nchunks'], CHUNK, lr, wd, ng,
-                                                g0['betas'][0], g0['betas'][1], g0['eps'], g0['momentum'], plan['tstep'].data_ptr(),
-                                                None if coef is None or clip_grad_l2norm <= 0 else coef.data_ptr(),
-                                                plan['amax'].data_ptr() if OPT_AMAX else None,
-                                                None if lr_dev is None else lr_dev.data_ptr(), stream))
+            d = _lib.OptimDesc(kind=0 if self.kind == "AdamW" else 1, ptrs=ptrs.data_ptr(), numel=plan['numel'].data_ptr(),
+                               chunk_tensor=plan['chunk_tensor'].data_ptr(), chunk_off=plan['chunk_off'].data_ptr(),
+                               group=plan['group'].data_ptr(), n=n, nchunks=plan['nchunks'], chunk=CHUNK, lr=C.addressof(lr),
+                               wd=C.addressof(wd), ngroups=ng, beta1=g0['betas'][0], beta2=g0['betas'][1], eps=g0['eps'],
+                               momentum=g0['momentum'], tensor_step=plan['tstep'].data_ptr(),
+                               norm_coef=None if coef is None or clip_grad_l2norm <= 0 else coef.data_ptr(),
+                               chunk_amax=plan['amax'].data_ptr() if OPT_AMAX else None,
+                               lr_dev=None if lr_dev is None else lr_dev.data_ptr())
+            _lib.check(lib.vilco_optim_step(C.byref(d), stream))
             first = plan['first']
             for i, (p, _) in enumerate(items):
                 if p.dim() >= 2 and OPT_AMAX:    # matrices: the tensors that get packed
