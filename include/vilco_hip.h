@@ -610,6 +610,34 @@ int vilco_mq_loss_bwd(const vilco_loss_desc* d, const float* g_cls, const float*
                       float* d_offsets, float* d_level_scale, float* d_gauss, void* stream);
 
 /* ------------------------------------------------------------------------------------------ */
+/* Distillation term of iCaRL / BiC (MQ/libs/modeling/meta_archs.py:1482-1519) and its gradient (csrc/distill.hip).  */
+/* Per level l (rows level_row[l] .. + level_T[l] of batch row `clip`; padded positions count, as in the reference):  */
+/*   mode 0 (iCaRL): out = 0.01 * sum_l (1/T_l) sum_t sum_{y < n_known} bce_with_logits(x[clip, t, y], p_l[t, y])       */
+/*                   (`scale` is not read)                                                                              */
+/*   mode 1 (BiC):   out = scale * sum_l -(1/T_l) sum_t sum_{y < n_known} p_l[t, y] log_softmax(x[clip, t, :n_known] / 2)[y] */
+/* level_row / level_T are HOST arrays (validated before anything is enqueued); level_dev is their device copy,         */
+/* int32 [2][L] (rows, then lengths), which the kernels walk -- rows it places outside the validated bounds are skipped.   */
+/* fwd: two launches, fixed-order sums, out = device float[1].  bwd: one launch; g_out = device scalar, the upstream       */
+/* gradient; ONLY d_logits[clip, level rows, :n_known] is written (assigned, not accumulated).  Same bits on every call.   */
+/* ------------------------------------------------------------------------------------------ */
+typedef struct vilco_distill_desc {
+  const float* logits;        /* [B][R][C] */
+  const float* targets;       /* [sum T_l][ldt]: levels end to end, no separator rows */
+  const int32_t* level_row;   /* host [L]: first row of every level inside R */
+  const int32_t* level_T;     /* host [L]: rows of every level */
+  const int32_t* level_dev;   /* device [2][L]: level_row, level_T */
+  int32_t B, R, C, L;
+  int32_t clip;               /* batch row the term reads (the reference: 0) */
+  int32_t ldt;                /* row stride of targets, >= n_known */
+  int32_t n_known;            /* 1 <= n_known <= min(C, ldt) */
+  int32_t mode;               /* 0 iCaRL, 1 BiC */
+  float scale;                /* BiC: 0.01 * n_known / n_classes */
+} vilco_distill_desc;
+size_t vilco_cl_distill_workspace(int64_t n_rows);      /* n_rows = sum T_l */
+int vilco_cl_distill_fwd(const vilco_distill_desc* d, float* out, void* workspace, size_t workspace_bytes, void* stream);
+int vilco_cl_distill_bwd(const vilco_distill_desc* d, const float* g_out, float* d_logits, void* stream);
+
+/* ------------------------------------------------------------------------------------------ */
 /* Continual-learning regularisers of MQ/libs/cl_methods/EWC.py:6-22 (get_regularized_loss) and MAS.py:5-21   */
 /* (get_mas_regularized_loss), called per iteration from train_utils.py:337-344, as ONE multi-tensor launch:    */
 /*   out[0] = lambda * sum_t sum_{i < numel[t]} F_t[i] (opt_t[i] - p_t[i])^2,   grad_t[i] -= 2 lambda F (opt - p) */

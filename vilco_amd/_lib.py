@@ -116,6 +116,13 @@ class OptimDesc(C.Structure):
                 ("chunk_amax", c_fp), ("lr_dev", c_fp)]
 
 
+class DistillDesc(C.Structure):
+    _cname_ = "vilco_distill_desc"
+    _fields_ = [("logits", c_fp), ("targets", c_fp), ("level_row", c_fp), ("level_T", c_fp), ("level_dev", c_fp),
+                ("B", i32), ("R", i32), ("C", i32), ("L", i32), ("clip", i32), ("ldt", i32), ("n_known", i32), ("mode", i32),
+                ("scale", f32)]
+
+
 # name -> (restype, argtypes); must list every symbol include/vilco_hip.h declares
 SIGNATURES = {
     "vilco_status_str": (C.c_char_p, [C.c_int]),
@@ -195,6 +202,9 @@ SIGNATURES = {
     "vilco_mq_loss_fwd": (C.c_int, [C.POINTER(LossDesc), c_fp, c_fp, c_fp, c_fp, sz, c_fp]),
     "vilco_mq_loss_bwd": (C.c_int, [C.POINTER(LossDesc), c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp,
                                     c_fp]),
+    "vilco_cl_distill_workspace": (sz, [i64]),
+    "vilco_cl_distill_fwd": (C.c_int, [C.POINTER(DistillDesc), c_fp, c_fp, sz, c_fp]),
+    "vilco_cl_distill_bwd": (C.c_int, [C.POINTER(DistillDesc), c_fp, c_fp, c_fp]),
     "vilco_cl_penalty": (C.c_int, [c_fp, c_fp, c_fp, c_fp, i32, i32, i32, f32, i32, c_fp, c_fp, c_fp]),
     "vilco_cl_accumulate": (C.c_int, [c_fp, c_fp, c_fp, c_fp, i32, i32, i32, i32, f32, f32, c_fp]),
     "vilco_nms_workspace": (sz, [i64, i32]),

@@ -8,12 +8,14 @@ no counterpart of this file (eager PyTorch); this is the MI355X answer to its st
 `GraphedStep(model, optimizer)` runs the first iterations of every input signature eagerly, then captures
 
   graph 1: [bump the dropout step word] -> layout change -> backbone -> heads -> fused labels + losses
+           [-> iCaRL distillation against the step's cached targets (csrc/distill.hip)]
            [-> narration SSL: encoder, poolings, memory-bank ring update, InfoNCE] -> backward
   graph 2: global-norm clip coefficient -> fused AdamW / SGD update (+ max|w| partials for the next weight packs)
 
 and from then on an iteration is: copy the batch into the static input buffers, replay 1, (eager work the caller wants
 between backward and update: a gradient all-reduce, an EWC / MAS penalty), hand the learning rates over, replay 2.
-What must differ between replays lives in device memory: the inputs, the dropout step word (common.h: vilco_step_seed),
+What must differ between replays lives in device memory: the inputs (with them `StepInputs.dist_tgt`, the contiguous
+buffer of the distillation targets of the batch's first cached clip), the dropout step word (common.h: vilco_step_seed),
 the stochastic-depth factors (torch's graph-safe Philox draw, captured), the loss-normaliser EMA, the optimizer's step
 counts and learning rates (vilco_optim_desc.lr_dev), the narration memory bank and its ring word (csrc/ssl.hip: the update
 advances the word on the device by the number of narrated clips, which differs from batch to batch).
@@ -21,8 +23,8 @@ advances the word on the device by the number of narrated clips, which differs f
 What is captured is what ran: graphs are keyed by the input shapes, task id and the identity / requires_grad of every
 parameter, and dropped when parameters were written from outside (load_state_dict, an eager optimizer step) -- cached
 operand planes and max|w| partials would be stale otherwise.  Steps the device half cannot run alone (distillation
-against host-side logits, BiC, narration SSL with its fused path switched off by VILCO_FUSED_SSL=0) fall back to the eager
-path.
+against host-side NumPy targets or in a batch without a cached clip, BiC -- its bias layers are ATen autograd --, narration
+SSL with its fused path switched off by VILCO_FUSED_SSL=0) fall back to the eager path.
 """
 import ctypes as C
 import gc
@@ -131,10 +133,10 @@ class GraphedStep:
     # ------------------------------------------------------------------ one iteration
     def __call__(self, video_list, task_id=0, prev_out_cls_logits=None):
         model = self.model
-        inp = model.prepare(video_list, True, gt_pad=self.gt_pad, narr_pad=self.narr_pad)
+        inp = self._prepare(video_list, prev_out_cls_logits)
         if not (self.enabled and model.training and model.capturable(inp, task_id, prev_out_cls_logits)):
             return self._eager(inp, video_list, task_id, prev_out_cls_logits)
-        key = (inp.signature(), int(task_id), self._param_sig(), int(model.n_known > 0), ops.arithmetic_key())
+        key = (inp.signature(), int(task_id), self._param_sig(), int(model.n_known), ops.arithmetic_key())
         ent = self._graphs.get(key)
         if ent is None:
             ent = self._graphs[key] = {'seen': 0}
@@ -154,18 +156,27 @@ class GraphedStep:
             self._capture(ent, inp, task_id)
         return self._replay(ent, inp)
 
-    def try_capture(self, video_list, task_id=0):
+    def _prepare(self, video_list, prev_out_cls_logits):
+        """the host half of the step; device-resident distillation targets join the inputs as one buffer (`dist_tgt`), which
+        the captured step reads and every replay refreshes"""
+        inp = self.model.prepare(video_list, True, gt_pad=self.gt_pad, narr_pad=self.narr_pad)
+        tgt = self.model.distill_target(prev_out_cls_logits) if hasattr(self.model, "distill_target") else None
+        if tgt is not None:
+            inp.dist_tgt, inp.dist_lens = tgt
+        return inp
+
+    def try_capture(self, video_list, task_id=0, prev_out_cls_logits=None):
         """Capture the graphs of this batch's signature NOW, without replaying them (no collective is issued: a staged capture
         holds none), and report whether that worked instead of raising.  For callers that must agree ACROSS RANKS on replay vs
         eager before the first replayed step (bench.py, N > 1): a capture that fails on one rank only would leave the ranks
         issuing different collectives.  False also when the step is not capturable; the signature then stays eager."""
         model = self.model
-        inp = model.prepare(video_list, True, gt_pad=self.gt_pad, narr_pad=self.narr_pad)
-        if not (self.enabled and model.training and model.capturable(inp, task_id, None)):
+        inp = self._prepare(video_list, prev_out_cls_logits)
+        if not (self.enabled and model.training and model.capturable(inp, task_id, prev_out_cls_logits)):
             return False
         if self.reducer is not None and self.reducer.enabled and self.reducer.planned() is None:
             return False                         # (the bucket plan comes from an eager finish(): run an eager step first)
-        key = (inp.signature(), int(task_id), self._param_sig(), int(model.n_known > 0), ops.arithmetic_key())
+        key = (inp.signature(), int(task_id), self._param_sig(), int(model.n_known), ops.arithmetic_key())
         ent = self._graphs.get(key)
         if ent is None:
             ent = self._graphs[key] = {'seen': 0}
@@ -215,9 +226,9 @@ class GraphedStep:
         from .modeling.meta_archs import StepInputs
         model, lib = self.model, _lib.load()
         static = StepInputs()
-        static.T, static.narr = inp.T, None
+        static.T, static.narr, static.dist_lens = inp.T, None, inp.dist_lens
         for name in StepInputs.__slots__:
-            if name not in ("T", "narr"):
+            if name not in StepInputs.HOST:
                 t = getattr(inp, name)
                 setattr(static, name, None if t is None else t.clone())
         for p in self.params:

@@ -294,16 +294,20 @@ class StepInputs:
     """device-resident inputs of one step (PtTransformer.prepare): feats_cf [B,Cin,T], lens int32 [B], text_cf
     [B,Ctxt,L], text_lens int32 [B], gt float [B, 3*Nmax+1] (training); the narration inputs of the fused SSL path:
     narr_cf [B,Cn,n_pad] tokens, narr_lens int32 [B] token counts, narr_mask float [B] (the clip has a narration); narr =
-    the unfused path's narration tuple or None"""
-    __slots__ = ("feats_cf", "lens", "T", "text_cf", "text_lens", "narr", "gt", "narr_cf", "narr_lens", "narr_mask")
+    the unfused path's narration tuple or None; dist_tgt float [sum T_l, ldt] = the iCaRL distillation targets of the step
+    (the first cached clip's levels end to end, PtTransformer.distill_target) with dist_lens = (T_l, ...), or None"""
+    __slots__ = ("feats_cf", "lens", "T", "text_cf", "text_lens", "narr", "gt", "narr_cf", "narr_lens", "narr_mask",
+                 "dist_tgt", "dist_lens")
+    HOST = ("T", "narr", "dist_lens")          # not device buffers: a captured step takes them over as they are
 
     def tensors(self):
         """(name, tensor) of every device buffer a replayed step reads"""
         return [(k, getattr(self, k)) for k in ("feats_cf", "lens", "text_cf", "text_lens", "gt", "narr_cf", "narr_lens",
-                                                "narr_mask") if getattr(self, k, None) is not None]
+                                                "narr_mask", "dist_tgt") if getattr(self, k, None) is not None]
 
     def signature(self):
-        return tuple((k, tuple(t.shape)) for k, t in self.tensors()) + (("narr", self.narr is not None),)
+        return (tuple((k, tuple(t.shape)) for k, t in self.tensors()) + (("narr", self.narr is not None),) +
+                (("dist_lens", getattr(self, "dist_lens", None)),))
 
 
 @register_meta_arch("LocPointTransformer")
@@ -589,6 +593,7 @@ class PtTransformer(nn.Module):
         inp = StepInputs()
         inp.feats_cf, inp.lens, inp.T = self._batch_cf(video_list, is_training)
         inp.text_cf = inp.text_lens = inp.narr = inp.narr_cf = inp.narr_lens = inp.narr_mask = None
+        inp.dist_tgt = inp.dist_lens = None        # filled by the caller that replays the step (graph.GraphedStep)
         if self.use_cross_modal:
             inp.text_cf, inp.text_lens, narr = self._query_batch_cf(video_list, narr_pad=narr_pad)
             if isinstance(narr, dict):
@@ -634,14 +639,21 @@ class PtTransformer(nn.Module):
     def capturable(self, inp, task_id=-1, prev_out_cls_logits=None):
         """can forward_prepared(inp, None, task_id) + backward run without touching the host?  (the fused label / loss
         kernels, a fixed prompt window, narration SSL only on its fused path -- the unfused one reads the mask sum and
-        keeps the ring pointer on the host --, no distillation against host-side logits)"""
+        keeps the ring pointer on the host).  Distillation: an iCaRL step with n_known > 0 is capturable when its targets
+        are resident on the device and travel in `inp.dist_tgt` (distill_target: the whole term is then ops.cl_distill
+        over a buffer a replay refreshes); NumPy targets are uploaded per step, a batch without a cached clip has no
+        target, and BiC's bias layers are ATen autograd: those steps stay eager, and so does any other step that is
+        handed targets."""
         if not (self.fused_loss and self.sync_free_loss and self.train_loss_weight > 0 and self.num_classes <= 128):
             return False
-        if inp.gt is None or prev_out_cls_logits:
+        if inp.gt is None:
             return False
         if self.training and self.narration_ssl and inp.narr_cf is None:
             return False
-        if self.n_known > 0 and self.cl_name in ('bic', 'icarl'):
+        if self.n_known > 0 and self.cl_name == 'icarl':
+            if getattr(inp, "dist_tgt", None) is None:
+                return False
+        elif prev_out_cls_logits or (self.n_known > 0 and self.cl_name == 'bic'):
             return False
         if hasattr(self, 'prompt') and not (0 <= task_id and (task_id + 1) * self.prompt.top_k <= self.prompt.pool_size):
             return False
@@ -654,6 +666,8 @@ class PtTransformer(nn.Module):
         x_tm, lens = ops.transpose(inp.feats_cf), inp.lens
         text_tm = text_lens = None
         narr = inp.narr
+        # a step prepared for replay carries its distillation targets as one buffer; it wins over the lists it was made of
+        self._dist_tgt = None if getattr(inp, "dist_tgt", None) is None else (inp.dist_tgt, inp.dist_lens)
         if self.use_cross_modal:
             text_tm, text_lens = ops.transpose(inp.text_cf), inp.text_lens
 
@@ -887,8 +901,10 @@ class PtTransformer(nn.Module):
         cls_loss, reg_loss, al_loss, final_loss = ops.mq_loss(
             logits, offsets, scale, gauss, tables, level_len, gt, norm, radius, self.train_label_smoothing,
             self.loss_normalizer_momentum, self.train_loss_weight, self.al_loss_weight, logits.shape[-1] != 1)
+        level_T = [int(p.shape[0]) for p in points]
+        level_row = cat.off if cat is not None else [sum(level_T[:i]) for i in range(len(level_T))]
         return self._cl_terms({'cls_loss': cls_loss, 'reg_loss': reg_loss, 'al_loss': al_loss}, final_loss,
-                              out_cls_logits, prev_out_cls_logits, reduce_sim)
+                              out_cls_logits, prev_out_cls_logits, reduce_sim, cat_logits=(logits, level_row))
 
     # ------------------------------------------------------------------ losses
     @property
@@ -970,13 +986,63 @@ class PtTransformer(nn.Module):
             loss_weight = cls_loss.detach() / max(reg_loss.item(), 0.01)
         final_loss = cls_loss + reg_loss * loss_weight + al_loss * self.al_loss_weight
 
+        level_T = [int(x.shape[1]) for x in out_cls_logits]
         return self._cl_terms({'cls_loss': cls_loss, 'reg_loss': reg_loss, 'al_loss': al_loss}, final_loss, out_cls_logits,
-                              prev_out_cls_logits, reduce_sim)
+                              prev_out_cls_logits, reduce_sim,
+                              cat_logits=(logits_all, [sum(level_T[:i]) for i in range(len(level_T))]))
 
-    def _cl_terms(self, out, final_loss, out_cls_logits, prev_out_cls_logits, reduce_sim):
-        """continual-learning terms on top of the detection loss (meta_archs.py:1478-1519)"""
+    @staticmethod
+    def _icarl_levels(prev_out_cls_logits, len_f):
+        """the reference's choice of iCaRL targets (meta_archs.py:1505-1506): handed a list over the batch's cached clips, the
+        first clip's per-level list"""
+        if len(prev_out_cls_logits) != len_f or len(prev_out_cls_logits) == 1:
+            return prev_out_cls_logits[0]
+        return prev_out_cls_logits
+
+    def distill_target(self, prev_out_cls_logits):
+        """-> (buffer [sum T_l, ldt], (T_l, ...)): the iCaRL targets a step with these cached outputs distils against, as
+        the one contiguous device buffer ops.cl_distill reads (train_cl.cache_prev_logits stores a clip's levels as views
+        of such a buffer: nothing is copied then).  None when there is nothing a replayed step could carry: not an iCaRL
+        step with known classes, no cached clip in the batch, or host-side (NumPy) targets."""
+        if not (self.n_known > 0 and self.cl_name == 'icarl' and prev_out_cls_logits):
+            return None
+        levels = self._icarl_levels(prev_out_cls_logits, len(self.fpn_strides))
+        if not all(torch.is_tensor(t) and t.is_cuda for t in levels):
+            return None
+        return ops.distill_targets(levels, self.device)
+
+    def _device_distill(self, out_cls_logits, prev_out_cls_logits, cat_logits):
+        """both distillation terms as ONE ops.cl_distill call (csrc/distill.hip) over the concatenated head output"""
+        bic = self.cl_name == 'bic'
+        level_T = tuple(int(x.shape[1]) for x in out_cls_logits)
+        tgt, self._dist_tgt = getattr(self, "_dist_tgt", None), None
+        if tgt is None or bic:
+            levels = prev_out_cls_logits if bic else self._icarl_levels(prev_out_cls_logits, len(level_T))
+            if len(levels) != len(level_T):
+                raise ValueError("distillation targets of %d levels for a pyramid of %d" % (len(levels), len(level_T)))
+            tgt = ops.distill_targets(levels, out_cls_logits[0].device)
+        targets, lens = tgt
+        if tuple(lens) != level_T:
+            raise ValueError("the distillation targets' level lengths %s differ from the logits' %s (cached with another "
+                             "max_seq_len?)" % (tuple(lens), level_T))
+        if targets.shape[1] < self.n_known:
+            raise ValueError("the distillation targets hold %d classes, n_known is %d" % (targets.shape[1], self.n_known))
+        logits, level_row = cat_logits if cat_logits is not None else (list(out_cls_logits), None)
+        n_classes = self.cls_head.cls_head.conv.out_channels
+        return ops.cl_distill(logits, level_row, level_T, targets, self.n_known,
+                              ops.DISTILL_BIC if bic else ops.DISTILL_ICARL, 0.01 * self.n_known / n_classes)
+
+    def _cl_terms(self, out, final_loss, out_cls_logits, prev_out_cls_logits, reduce_sim, cat_logits=None):
+        """continual-learning terms on top of the detection loss (meta_archs.py:1478-1519).  On the device the iCaRL / BiC
+        distillation term is one fused op (cat_logits = the concatenated logits and every level's first row in them); a
+        CPU model walks the reference's loops."""
         if self.n_known > 0 and self.cl_name == 'l2p':
             final_loss = final_loss - 0.1 * reduce_sim
+        if self.n_known > 0 and self.cl_name in ('bic', 'icarl') and out_cls_logits[0].is_cuda:
+            dist_loss = self._device_distill(out_cls_logits, prev_out_cls_logits, cat_logits)
+            out['dist_loss'] = dist_loss
+            out['final_loss'] = final_loss + dist_loss
+            return out
         if self.n_known > 0 and self.cl_name == 'bic':
             n_classes = self.cls_head.cls_head.conv.out_channels
             alpha, temp, dist_loss = self.n_known / n_classes, 2, 0

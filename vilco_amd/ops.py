@@ -1924,6 +1924,107 @@ def mq_loss(logits, offsets, level_scale, gauss, tables, level_len, gt, loss_nor
                          loss_norm, cfg)
 
 
+# ---------------------------------------------------------------------------------------- iCaRL / BiC distillation
+DISTILL_ICARL, DISTILL_BIC = 0, 1
+_distill_tabs = {}
+
+
+def _distill_levels(level_row, level_T, device):
+    """(host rows, host lengths, device int32 [2, L]) of a level layout; the device copy is made once per layout and kept (a
+    captured step addresses it)"""
+    rows, lens = tuple(int(r) for r in level_row), tuple(int(t) for t in level_T)
+    if len(rows) != len(lens) or not rows:
+        raise ValueError("cl_distill: level_row and level_T must list the same, non-zero number of levels")
+    key = (rows, lens, str(device))
+    tab = _distill_tabs.get(key)
+    if tab is None:
+        L = len(rows)
+        tab = _distill_tabs[key] = ((C.c_int32 * L)(*rows), (C.c_int32 * L)(*lens),
+                                    torch.tensor([rows, lens], dtype=torch.int32, device=device))
+    return tab
+
+
+def distill_targets(levels, device):
+    """The cached outputs of one clip (a list over pyramid levels of [T_l, ldt] device tensors or NumPy arrays, as
+    train_cl.cache_prev_logits hands them out) -> (fp32 device buffer [sum T_l, ldt], (T_l, ...)).  Views of one
+    contiguous buffer, level after level, are taken as they are; anything else is concatenated once (NumPy: on the host,
+    then one upload)."""
+    lens = tuple(int(t.shape[0]) for t in levels)
+    if all(torch.is_tensor(t) for t in levels):
+        t0 = levels[0]
+        if t0.dim() == 2 and t0.is_cuda and t0.dtype == torch.float32 and t0.device == torch.device(device):
+            ldt, off, ok = t0.shape[1], t0.storage_offset(), True
+            for t in levels:
+                ok = ok and (t.dim() == 2 and t.shape[1] == ldt and t.dtype == t0.dtype and t.is_contiguous() and
+                             t.untyped_storage().data_ptr() == t0.untyped_storage().data_ptr() and t.storage_offset() == off)
+                off += t.shape[0] * ldt
+            if ok:
+                return t0.as_strided((sum(lens), ldt), (ldt, 1), t0.storage_offset()), lens
+        return torch.cat([t.to(device=device, dtype=torch.float32) for t in levels], dim=0).contiguous(), lens
+    import numpy as np
+    host = np.ascontiguousarray(np.concatenate([np.asarray(t, dtype=np.float32) for t in levels], axis=0))
+    return torch.from_numpy(host).to(device), lens
+
+
+def _distill_desc(logits, targets, tab, n_known, mode, scale, clip):
+    d = _lib.DistillDesc()
+    d.logits, d.targets = logits.data_ptr(), targets.data_ptr()
+    d.level_row, d.level_T, d.level_dev = C.addressof(tab[0]), C.addressof(tab[1]), tab[2].data_ptr()
+    d.B, d.R, d.C, d.L = logits.shape[0], logits.shape[1], logits.shape[2], len(tab[0])
+    d.clip, d.ldt, d.n_known, d.mode, d.scale = int(clip), targets.shape[1], int(n_known), int(mode), float(scale)
+    return d
+
+
+class _ClDistill(torch.autograd.Function):
+    """the distillation term of iCaRL / BiC (meta_archs.py:1482-1519) over the concatenated head output: two launches
+    forward, one backward (vilco_cl_distill_fwd / _bwd); the gradient is non-zero on [clip, level rows, :n_known] only"""
+
+    @staticmethod
+    def forward(ctx, logits, targets, tab, cfg):
+        _chk(logits, targets)
+        lib = _lib.load()
+        d = _distill_desc(logits, targets, tab, *cfg)
+        nws = lib.vilco_cl_distill_workspace(targets.shape[0])
+        ws = _ws(nws, logits.device)
+        out = torch.empty(1, dtype=torch.float32, device=logits.device)
+        _lib.check(lib.vilco_cl_distill_fwd(C.byref(d), out.data_ptr(), ws.data_ptr(), nws, _stream()))
+        ctx.desc, ctx.tab = d, tab
+        ctx.save_for_backward(logits, targets)
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        logits, targets = ctx.saved_tensors
+        g = g.contiguous().float()
+        dl = torch.zeros_like(logits)          # the kernel assigns its footprint; autograd adds this to mq_loss' gradient
+        _lib.check(_lib.load().vilco_cl_distill_bwd(C.byref(ctx.desc), g.data_ptr(), dl.data_ptr(), _stream()))
+        return dl, None, None, None
+
+
+def cl_distill(logits, level_row, level_T, targets, n_known, mode, scale, clip=0):
+    """iCaRL (mode DISTILL_ICARL) / BiC (DISTILL_BIC) distillation of batch row `clip` against the previous model's cached
+    outputs (include/vilco_hip.h: vilco_distill_desc) -> scalar.
+    logits: [B, R, C] with level l in rows level_row[l] .. level_row[l] + level_T[l], or the list of per-level [B, T_l, C]
+    tensors (concatenated here; level_row may then be None).  targets: [sum T_l, ldt], or the per-level list (device
+    tensors or NumPy arrays: distill_targets).  BiC: scale = 0.01 * n_known / n_classes; iCaRL's 0.01 is fixed."""
+    if isinstance(logits, (list, tuple)):
+        level_T = [int(x.shape[1]) for x in logits]
+        level_row = [sum(level_T[:i]) for i in range(len(level_T))]
+        logits = torch.cat(list(logits), dim=1)
+    if not torch.is_tensor(targets):
+        targets, lens = distill_targets(targets, logits.device)
+        if lens != tuple(int(t) for t in level_T):
+            raise ValueError("cl_distill: the targets' level lengths %s differ from the logits' %s" % (lens, tuple(level_T)))
+    if targets.dim() != 2 or targets.shape[0] != sum(int(t) for t in level_T):
+        raise ValueError("cl_distill: targets %s do not hold the %d rows of the levels %s" %
+                         (tuple(targets.shape), sum(int(t) for t in level_T), tuple(level_T)))
+    if not torch.is_tensor(logits) or logits.dim() != 3:
+        raise ValueError("cl_distill: logits must be [B, R, C] or a list of [B, T_l, C]")
+    tab =_distill_levels(level_row, level_T, logits.device)
+    return _ClDistill.apply(logits.contiguous(), targets.contiguous(), tab,
+                            (int(n_known), int(mode), float(scale), int(clip)))
+
+
 # ---------------------------------------------------------------------------------------- inference decode
 def decode(logits, offsets, points, level_row0, level_len, topk, pre_nms_thresh, duration_thresh):
     """vilco_decode: threshold -> exact top-k -> segment decode -> duration filter of one clip's pyramid (all levels, one

@@ -63,7 +63,7 @@ def memory_quota(memory_size, n_classes):
 @torch.no_grad()
 def cache_prev_logits(model, loader, task_id, as_numpy=False, kind='sigmoid'):
     """{video_id: [sigmoid(cls logits) per pyramid level]} of the incoming model (train_cl.py:226-235): the distillation
-    targets of iCaRL.  They stay ON THE DEVICE (one small tensor per level and clip; the reference round-trips them
+    targets of iCaRL.  They stay ON THE DEVICE (one buffer per clip, its levels views of it; the reference round-trips them
     through numpy and uploads them again in every iteration, meta_archs.py:1492,1508); as_numpy=True gives the
     reference's format.  kind='softmax_T2': softmax(logits[:, :n_known] / 2) instead, the targets of BiC's distillation
     term (train_bic.py:241), which multiplies them with a log-softmax."""
@@ -76,7 +76,11 @@ def cache_prev_logits(model, loader, task_id, as_numpy=False, kind='sigmoid'):
             if kind == 'softmax_T2':
                 probs = [torch.softmax(lvl[i][:, :model.n_known] / 2, dim=1) for lvl in cls_logits]
             else:
-                probs = [torch.sigmoid(lvl[i]).clone() for lvl in cls_logits]
+                probs = [torch.sigmoid(lvl[i]) for lvl in cls_logits]
+            # a clip's levels are views of ONE contiguous [sum T_l, .] buffer: the distillation kernel (ops.cl_distill) and a
+            # replayed step's input slot (StepInputs.dist_tgt) take it as it is
+            buf = torch.cat(probs, dim=0).contiguous()
+            probs = list(buf.split([int(t.shape[0]) for t in probs], dim=0))
             out[v['video_id']] = [np.array(t.cpu().numpy()) for t in probs] if as_numpy else probs
     return out
 
