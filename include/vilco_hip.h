@@ -638,6 +638,40 @@ int vilco_cl_distill_fwd(const vilco_distill_desc* d, float* out, void* workspac
 int vilco_cl_distill_bwd(const vilco_distill_desc* d, const float* g_out, float* d_logits, void* stream);
 
 /* ------------------------------------------------------------------------------------------ */
+/* BiC bias correction of the classification head's output (MQ/libs/modeling/meta_archs.py:26-35: BiasLayer,           */
+/* alpha * x + beta; :821-836: one layer per task over its slice of the class columns, the slices concatenated again)    */
+/* as one launch over the concatenated head output (csrc/bic.hip):                                                       */
+/*   y[r][c] = alpha[s(c)] * x[r][c] + beta[s(c)]   for every r < rows, c < C;   s(c) = i with splits[i-1] <= c < splits[i] */
+/* The product and the sum are rounded separately (no FMA).  Every row gets the affine: separator rows of a level        */
+/* layout and rows past a clip's valid length are not special.  Nothing outside [rows][C] is written.                    */
+/* splits = HOST array of S cumulative ends, strictly increasing, splits[S-1] == C <= 128; it is validated before any     */
+/* device work (empty, not increasing or not ending at C, n_layers != S: VILCO_ERR_BADARG; C > 128: _UNSUPPORTED).         */
+/* table = DEVICE int64 [3][S]: the addresses of alpha_i (float[1]), the addresses of beta_i, the split ends again.     */
+/* alpha and beta are read through it when the kernel runs -- never by the host -- so a captured launch sees the values  */
+/* written after the capture.  A column the device table does not cover is not written.                                  */
+/* fwd: one launch.  y may equal x (in place, ldy == ldx).                                                                */
+/* bwd: the descriptor's x is the upstream gradient dy and y receives dx = alpha[s(c)] * dy (one launch; y may equal x).  */
+/* dparams != NULL (some layer takes a gradient): device float [2][S] receives dalpha_i = sum dy * x_fwd and              */
+/* dbeta_i = sum dy over all rows and the columns of split i -- two more launches, fixed-order fp64 sums without atomics,  */
+/* the same bits on every call; x_fwd [rows][ld_fwd] is the forward's INPUT and `workspace` holds                         */
+/* vilco_bic_correct_bwd_workspace(rows) bytes.  dparams == NULL: no reduction is launched, x_fwd / workspace are not read. */
+/* ------------------------------------------------------------------------------------------ */
+typedef struct vilco_bic_correct_desc {
+  const float* x;             /* [rows][ldx], the first C columns of every row */
+  float* y;                   /* [rows][ldy] */
+  const int32_t* splits;      /* host [S] */
+  const int64_t* table;       /* device [3][S]: &alpha_i, &beta_i, splits[i] */
+  int64_t rows;               /* B * R */
+  int32_t C, S;
+  int32_t ldx, ldy;           /* row strides in floats, >= C */
+  int32_t n_layers;           /* layers the caller holds: must equal S */
+} vilco_bic_correct_desc;
+int vilco_bic_correct_fwd(const vilco_bic_correct_desc* d, void* stream);
+size_t vilco_bic_correct_bwd_workspace(int64_t rows);
+int vilco_bic_correct_bwd(const vilco_bic_correct_desc* d, const float* x_fwd, int32_t ld_fwd, float* dparams,
+                          void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------ */
 /* Continual-learning regularisers of MQ/libs/cl_methods/EWC.py:6-22 (get_regularized_loss) and MAS.py:5-21   */
 /* (get_mas_regularized_loss), called per iteration from train_utils.py:337-344, as ONE multi-tensor launch:    */
 /*   out[0] = lambda * sum_t sum_{i < numel[t]} F_t[i] (opt_t[i] - p_t[i])^2,   grad_t[i] -= 2 lambda F (opt - p) */

@@ -123,6 +123,12 @@ class DistillDesc(C.Structure):
                 ("scale", f32)]
 
 
+class BicCorrectDesc(C.Structure):
+    _cname_ = "vilco_bic_correct_desc"
+    _fields_ = [("x", c_fp), ("y", c_fp), ("splits", c_fp), ("table", c_fp), ("rows", i64), ("C", i32), ("S", i32),
+                ("ldx", i32), ("ldy", i32), ("n_layers", i32)]
+
+
 # name -> (restype, argtypes); must list every symbol include/vilco_hip.h declares
 SIGNATURES = {
     "vilco_status_str": (C.c_char_p, [C.c_int]),
@@ -238,6 +244,9 @@ SIGNATURES = {
                                 c_fp, c_fp, sz, c_fp]),
     "vilco_bic_eval_ws_bytes": (sz, [i64, i32, i32, i32]),
     "vilco_bic_eval": (C.c_int, [c_fp, c_fp, c_fp, c_fp, c_fp, i64, i32, i32, i32, i32, f32, c_fp, c_fp, c_fp, sz, c_fp]),
+    "vilco_bic_correct_fwd": (C.c_int, [C.POINTER(BicCorrectDesc), c_fp]),
+    "vilco_bic_correct_bwd_workspace": (sz, [i64]),
+    "vilco_bic_correct_bwd": (C.c_int, [C.POINTER(BicCorrectDesc), c_fp, i32, c_fp, c_fp, sz, c_fp]),
     "vilco_ssl_pool_workspace": (sz, [C.POINTER(i32), i32, i32, i32]),
     "vilco_ssl_pool_fwd": (C.c_int, [C.POINTER(c_fp), C.POINTER(i32), i32, c_fp, i32, i32, c_fp, c_fp, sz, c_fp]),
     "vilco_ssl_pool_bwd": (C.c_int, [c_fp, C.POINTER(c_fp), C.POINTER(i32), i32, c_fp, i32, i32, c_fp]),

@@ -204,3 +204,236 @@ extern "C" int vilco_bic_eval(const float* logits, const uint64_t* label_bits, c
                      (float*)nullptr, (double*)nullptr, 0, out3);
   return vilco_launch_status();
 }
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// BiC stage 1 and inference: the bias correction of the classification head's output (MQ/libs/modeling/meta_archs.py:26-35,
+// :821-836 -- one BiasLayer per task over its slice of the class columns, the slices concatenated again) as ONE launch over the
+// concatenated head output x [rows = B * R][ldx >= C], whatever the number of levels and splits:
+//
+//   y[r, c] = alpha[s(c)] * x[r, c] + beta[s(c)],    s(c) = the split i with splits[i-1] <= c < splits[i]
+//
+// for EVERY row r: separator rows of the LevelCat layout and rows past a clip's valid length get the same affine as the rest
+// (the ATen module does that to the padded rows of every level, and the distillation term reads them, distill.hip; nobody
+// reads the separator rows).  Nothing outside [rows][C] is written: the columns C .. ld of a strided buffer are not touched.
+// alpha_i, beta_i are read from the layers' OWN parameters at run time, through a device table of their addresses
+// (table = int64 [3][S]: &alpha_i, &beta_i, the split ends): a replayed hipGraph sees what stage 2 wrote after the capture,
+// and the host never reads them.  The product and the sum are rounded separately, as the ATen module's two kernels round
+// them (no FMA contraction: `fp contract(off)` below), so the result does not depend on how this file is compiled.
+// y may be x (in place): the head's last conv does not need its output for its backward.  With layers that take a gradient
+// the input is needed again (dalpha), so the in-place form is for frozen layers -- stage 1 and inference, the shipped uses.
+//
+//   bic_affine_kernel<true>    forward.  Every block first writes the per-column (alpha, beta) into LDS (C <= 128 columns, a scan
+//                              of the S <= C ends per column), then walks the elements grid-stride: 16-byte accesses when both
+//                              buffers are dense (ld == C) and aligned, 4-byte accesses of consecutive lanes otherwise.
+//   bic_affine_kernel<false>   backward, dx = alpha[s(c)] * dy: the same walk without beta.
+//   bic_pgrad_part_kernel      only when a layer requires a gradient: thread (p, c) of a block adds dy[r, c] * x[r, c] and dy[r, c]
+//                              over the block's rows r = 2 k + p in row order, in fp64 (the product of two floats is exact
+//                              there); the two row phases are added in order: one [2][128] partial per block.
+//   bic_pgrad_finish_kernel    one workgroup: column c adds the partials in block order, then split i adds its columns in
+//                              column order and writes dalpha_i, dbeta_i (fp32).  No atomics: the same bits on every launch.
+namespace {
+
+constexpr int CT = 256;                 // threads per workgroup
+constexpr int CMAX = 128;               // columns (the loss kernel's limit)
+constexpr int C_MAX_BLOCKS = 2048;
+constexpr int PG_MAX_BLOCKS = 256;
+constexpr int PG_ROWS = 32;             // rows per block the reduction grid is sized for
+
+struct AffineArgs {
+  const float* x;
+  float* y;
+  const long long* table;               // device [3][S]
+  long rows;
+  int C, S, ldx, ldy;
+};
+
+// per-column (alpha, beta) of the block; a column no split covers (a device table that disagrees with the validated host
+// table) or a null address keeps `ok` false and nothing is written for it
+__device__ __forceinline__ void load_columns(const long long* __restrict__ table, int C, int S, float* sa, float* sb, int* ok) {
+  for (int c = threadIdx.x; c < CMAX; c += blockDim.x) {
+    float a = 0.f, b = 0.f;
+    int good = 0;
+    if (c < C) {
+      int lo = 0;
+      for (int i = 0; i < S; ++i) {
+        const int hi = (int)table[2 * S + i];
+        if (c >= lo && c < hi) {
+          const float* pa = reinterpret_cast<const float*>(table[i]);
+          const float* pb = reinterpret_cast<const float*>(table[S + i]);
+          if (pa && pb) { a = pa[0]; b = pb[0]; good = 1; }
+          break;
+        }
+        if (hi > lo) lo = hi;
+      }
+    }
+    sa[c] = a; sb[c] = b; ok[c] = good;
+  }
+  __syncthreads();
+}
+
+template <bool BETA>
+__global__ __launch_bounds__(CT) void bic_affine_kernel(AffineArgs a, int vec) {
+#pragma clang fp contract(off)
+  __shared__ float sa[CMAX], sb[CMAX];
+  __shared__ int ok[CMAX];
+  load_columns(a.table, a.C, a.S, sa, sb, ok);
+  const long total = a.rows * a.C;
+  const long stride = (long)gridDim.x * CT;
+  if (vec) {                                                 // dense and 16-byte aligned: total % 4 elements are the tail
+    const long nv = total >> 2;
+    const float4* xv = reinterpret_cast<const float4*>(a.x);
+    float4* yv = reinterpret_cast<float4*>(a.y);
+    for (long v = (long)blockIdx.x * CT + threadIdx.x; v < nv; v += stride) {
+      const float4 in = xv[v];
+      int c = (int)((unsigned)(v << 2) % (unsigned)a.C);        // rows * C < 2^31 (MAX_ROWS)
+      float r[4] = {in.x, in.y, in.z, in.w};
+      bool all = true;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        all = all && ok[c];
+        const float m = sa[c] * r[k];
+        r[k] = BETA ? m + sb[c] : m;
+        c = c + 1 == a.C ? 0 : c + 1;
+      }
+      if (all) {
+        yv[v] = make_float4(r[0], r[1], r[2], r[3]);
+      } else {
+        c = (int)((unsigned)(v << 2) % (unsigned)a.C);
+        for (int k = 0; k < 4; ++k) {
+          if (ok[c]) a.y[(v << 2) + k] = r[k];
+          c = c + 1 == a.C ? 0 : c + 1;
+        }
+      }
+    }
+    for (long e = (nv << 2) + (long)blockIdx.x * CT + threadIdx.x; e < total; e += stride) {
+      const int c = (int)((unsigned)e % (unsigned)a.C);
+      if (!ok[c]) continue;
+      const float m = sa[c] * a.x[e];
+      a.y[e] = BETA ? m + sb[c] : m;
+    }
+    return;
+  }
+  for (long e = (long)blockIdx.x * CT + threadIdx.x; e < total; e += stride) {
+    const long r = (long)((unsigned)e / (unsigned)a.C);
+    const int c = (int)(e - r * a.C);
+    if (!ok[c]) continue;
+    const float m = sa[c] * a.x[r * a.ldx + c];
+    a.y[r * a.ldy + c] = BETA ? m + sb[c] : m;
+  }
+}
+
+__global__ __launch_bounds__(CT) void bic_pgrad_part_kernel(const float* __restrict__ dy, const float* __restrict__ x, long rows, int C,
+                                                            int lddy, int ldx, double* __restrict__ part) {
+  __shared__ double sd[2][CT];
+  const int c = threadIdx.x & (CMAX - 1), p = threadIdx.x >> 7;
+  double s_a = 0.0, s_b = 0.0;
+  if (c < C) {
+    for (long r = (long)blockIdx.x * 2 + p; r < rows; r += (long)gridDim.x * 2) {
+      const double g = (double)dy[r * lddy + c];
+      s_a = s_a + g * (double)x[r * ldx + c];
+      s_b = s_b + g;
+    }
+  }
+  sd[0][threadIdx.x] = s_a; sd[1][threadIdx.x] = s_b;
+  __syncthreads();
+  if (threadIdx.x < CMAX) {
+    double* out = part + (long)blockIdx.x * 2 * CMAX;
+    out[c] = sd[0][c] + sd[0][c + CMAX];
+    out[CMAX + c] = sd[1][c] + sd[1][c + CMAX];
+  }
+}
+
+__global__ __launch_bounds__(CMAX) void bic_pgrad_finish_kernel(const double* __restrict__ part, int nblk, const long long* __restrict__ table,
+                                                                int C, int S, float* __restrict__ dparams) {
+  __shared__ double sc[2][CMAX];
+  const int c = threadIdx.x;
+  double va = 0.0, vb = 0.0;
+  for (int b = 0; b < nblk; ++b) {
+    va = va + part[(long)b * 2 * CMAX + c];
+    vb = vb + part[(long)b * 2 * CMAX + CMAX + c];
+  }
+  sc[0][c] = va; sc[1][c] = vb;
+  __syncthreads();
+  if (c < S) {
+    int lo = c ? (int)table[2 * S + c - 1] : 0, hi = (int)table[2 * S + c];
+    if (lo < 0) lo = 0;
+    if (hi > C) hi = C;
+    double da = 0.0, db = 0.0;
+    for (int j = lo; j < hi; ++j) { da = da + sc[0][j]; db = db + sc[1][j]; }
+    dparams[c] = (float)da;
+    dparams[S + c] = (float)db;
+  }
+}
+
+int pgrad_blocks(long rows) {
+  const long g = (rows + PG_ROWS - 1) / PG_ROWS;
+  return (int)(g < 1 ? 1 : (g > PG_MAX_BLOCKS ? PG_MAX_BLOCKS : g));
+}
+
+// the split table first (host memory only), then the operands: nothing is enqueued for a table that is not cumulative ends
+int check_correct(const vilco_bic_correct_desc* d) {
+  if (!d) return VILCO_ERR_BADARG;
+  if (d->C < 1 || d->S < 1 || !d->splits) return VILCO_ERR_BADARG;              // an empty table
+  if (d->C > CMAX) return VILCO_ERR_UNSUPPORTED;
+  if (d->n_layers != d->S) return VILCO_ERR_BADARG;                              // one layer per split
+  int lo = 0;
+  for (int i = 0; i < d->S; ++i) {
+    if (d->splits[i] <= lo) return VILCO_ERR_BADARG;                             // strictly increasing, first > 0
+    lo = d->splits[i];
+  }
+  if (lo != d->C) return VILCO_ERR_BADARG;                                       // the last split ends the row
+  if (d->rows < 0 || d->ldx < d->C || d->ldy < d->C) return VILCO_ERR_BADARG;
+  if (d->rows > MAX_ROWS) return VILCO_ERR_UNSUPPORTED;
+  if (!d->table || (d->rows > 0 && (!d->x || !d->y))) return VILCO_ERR_BADARG;
+  if (!vilco_aligned(d->x, 4) || !vilco_aligned(d->y, 4) || !vilco_aligned(d->table, 8)) return VILCO_ERR_BADARG;
+  if (d->x == d->y && d->ldx != d->ldy) return VILCO_ERR_BADARG;
+  return VILCO_OK;
+}
+
+template <bool BETA>
+void launch_affine(const vilco_bic_correct_desc* d, hipStream_t s) {
+  AffineArgs a;
+  a.x = d->x; a.y = d->y; a.table = reinterpret_cast<const long long*>(d->table);
+  a.rows = d->rows; a.C = d->C; a.S = d->S; a.ldx = d->ldx; a.ldy = d->ldy;
+  const int vec = d->ldx == d->C && d->ldy == d->C && vilco_aligned(d->x, 16) && vilco_aligned(d->y, 16);
+  const long total = d->rows * d->C;
+  const long per_block = (long)CT * 4;
+  long g = (total + per_block - 1) / per_block;
+  g = g < 1 ? 1 : (g > C_MAX_BLOCKS ? C_MAX_BLOCKS : g);
+  hipLaunchKernelGGL(bic_affine_kernel<BETA>, dim3((unsigned)g), dim3(CT), 0, s, a, vec);
+}
+
+}  // namespace
+
+extern "C" int vilco_bic_correct_fwd(const vilco_bic_correct_desc* d, void* stream) {
+  const int rc = check_correct(d);
+  if (rc != VILCO_OK) return rc;
+  if (d->rows == 0) return VILCO_OK;
+  launch_affine<true>(d, reinterpret_cast<hipStream_t>(stream));
+  return vilco_launch_status();
+}
+
+extern "C" size_t vilco_bic_correct_bwd_workspace(int64_t rows) {
+  return rows < 0 ? 0 : (size_t)pgrad_blocks(rows) * 2 * CMAX * sizeof(double) + 256;
+}
+
+extern "C" int vilco_bic_correct_bwd(const vilco_bic_correct_desc* d, const float* x_fwd, int32_t ld_fwd, float* dparams,
+                                     void* workspace, size_t workspace_bytes, void* stream) {
+  const int rc = check_correct(d);
+  if (rc != VILCO_OK) return rc;
+  if (dparams) {
+    if (!workspace || (d->rows > 0 && !x_fwd) || ld_fwd < d->C || !vilco_aligned(x_fwd, 4)) return VILCO_ERR_BADARG;
+    if (workspace_bytes < vilco_bic_correct_bwd_workspace(d->rows)) return VILCO_ERR_WORKSPACE;
+  }
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  if (dparams) {                                             // before dx: d->y may be d->x (the gradient scaled in place)
+    double* part = ws_base(workspace);
+    const int nblk = pgrad_blocks(d->rows);
+    hipLaunchKernelGGL(bic_pgrad_part_kernel, dim3(nblk), dim3(CT), 0, s, d->x, x_fwd, (long)d->rows, (int)d->C, (int)d->ldx,
+                       (int)ld_fwd, part);
+    hipLaunchKernelGGL(bic_pgrad_finish_kernel, dim3(1), dim3(CMAX), 0, s, (const double*)part, nblk,
+                       reinterpret_cast<const long long*>(d->table), (int)d->C, (int)d->S, dparams);
+  }
+  if (d->rows > 0) launch_affine<false>(d, s);
+  return vilco_launch_status();
+}

@@ -8,7 +8,8 @@ no counterpart of this file (eager PyTorch); this is the MI355X answer to its st
 `GraphedStep(model, optimizer)` runs the first iterations of every input signature eagerly, then captures
 
   graph 1: [bump the dropout step word] -> layout change -> backbone -> heads -> fused labels + losses
-           [-> iCaRL distillation against the step's cached targets (csrc/distill.hip)]
+           [BiC: the head's logits through the bias correction (csrc/bic.hip) first]
+           [-> iCaRL / BiC distillation against the step's cached targets (csrc/distill.hip)]
            [-> narration SSL: encoder, poolings, memory-bank ring update, InfoNCE] -> backward
   graph 2: global-norm clip coefficient -> fused AdamW / SGD update (+ max|w| partials for the next weight packs)
 
@@ -16,15 +17,16 @@ and from then on an iteration is: copy the batch into the static input buffers, 
 between backward and update: a gradient all-reduce, an EWC / MAS penalty), hand the learning rates over, replay 2.
 What must differ between replays lives in device memory: the inputs (with them `StepInputs.dist_tgt`, the contiguous
 buffer of the distillation targets of the batch's first cached clip), the dropout step word (common.h: vilco_step_seed),
-the stochastic-depth factors (torch's graph-safe Philox draw, captured), the loss-normaliser EMA, the optimizer's step
+the stochastic-depth factors (torch's graph-safe Philox draw, captured), BiC's alpha / beta (the correction kernel reads them
+through a table of the layers' addresses: stage 2 writes them after the capture), the loss-normaliser EMA, the optimizer's step
 counts and learning rates (vilco_optim_desc.lr_dev), the narration memory bank and its ring word (csrc/ssl.hip: the update
 advances the word on the device by the number of narrated clips, which differs from batch to batch).
 
-What is captured is what ran: graphs are keyed by the input shapes, task id and the identity / requires_grad of every
-parameter, and dropped when parameters were written from outside (load_state_dict, an eager optimizer step) -- cached
+What is captured is what ran: graphs are keyed by the input shapes, task id, the identity / requires_grad of every
+parameter and BiC's split table with the addresses of its layers, and dropped when parameters were written from outside (load_state_dict, an eager optimizer step) -- cached
 operand planes and max|w| partials would be stale otherwise.  Steps the device half cannot run alone (distillation
-against host-side NumPy targets or in a batch without a cached clip, BiC -- its bias layers are ATen autograd --, narration
-SSL with its fused path switched off by VILCO_FUSED_SSL=0) fall back to the eager path.
+against host-side NumPy targets or in a batch without a cached clip, a BiC model whose split table the correction kernel
+does not take, narration SSL with its fused path switched off by VILCO_FUSED_SSL=0) fall back to the eager path.
 """
 import ctypes as C
 import gc
@@ -120,6 +122,17 @@ class GraphedStep:
             self.params = ps
         return hash(tuple((p.data_ptr(), p.requires_grad) for p in ps))
 
+    def _bic_sig(self):
+        """BiC: the split table and WHERE the bias layers' alpha / beta live (they are no parameters of the model: the layers
+        sit in a plain list that grows with the task and is rebuilt when a checkpoint is loaded).  Not their values: the
+        captured correction reads those from memory, so stage 2 may write them between replays."""
+        m = self.model
+        if getattr(m, "cl_name", None) != 'bic' or not getattr(m, "list_bias_layers", None):
+            return None
+        return (tuple(int(v) for v in m.list_splits),
+                tuple((l.alpha.data_ptr(), l.beta.data_ptr(), l.alpha.requires_grad, l.beta.requires_grad)
+                      for l in m.list_bias_layers))
+
     @staticmethod
     def _version_sum(tracked):
         return sum(p._version for p in tracked)
@@ -136,7 +149,7 @@ class GraphedStep:
         inp = self._prepare(video_list, prev_out_cls_logits)
         if not (self.enabled and model.training and model.capturable(inp, task_id, prev_out_cls_logits)):
             return self._eager(inp, video_list, task_id, prev_out_cls_logits)
-        key = (inp.signature(), int(task_id), self._param_sig(), int(model.n_known), ops.arithmetic_key())
+        key = (inp.signature(), int(task_id), self._param_sig(), int(model.n_known), ops.arithmetic_key(), self._bic_sig())
         ent = self._graphs.get(key)
         if ent is None:
             ent = self._graphs[key] = {'seen': 0}
@@ -163,6 +176,7 @@ class GraphedStep:
         tgt = self.model.distill_target(prev_out_cls_logits) if hasattr(self.model, "distill_target") else None
         if tgt is not None:
             inp.dist_tgt, inp.dist_lens = tgt
+            inp.dist_kind = self.model.cl_name       # whom the buffer was attached for (PtTransformer.capturable)
         return inp
 
     def try_capture(self, video_list, task_id=0, prev_out_cls_logits=None):
@@ -176,7 +190,7 @@ class GraphedStep:
             return False
         if self.reducer is not None and self.reducer.enabled and self.reducer.planned() is None:
             return False                         # (the bucket plan comes from an eager finish(): run an eager step first)
-        key = (inp.signature(), int(task_id), self._param_sig(), int(model.n_known), ops.arithmetic_key())
+        key = (inp.signature(), int(task_id), self._param_sig(), int(model.n_known), ops.arithmetic_key(), self._bic_sig())
         ent = self._graphs.get(key)
         if ent is None:
             ent = self._graphs[key] = {'seen': 0}
@@ -227,6 +241,7 @@ class GraphedStep:
         model, lib = self.model, _lib.load()
         static = StepInputs()
         static.T, static.narr, static.dist_lens = inp.T, None, inp.dist_lens
+        static.dist_kind = getattr(inp, "dist_kind", None)
         for name in StepInputs.__slots__:
             if name not in StepInputs.HOST:
                 t = getattr(inp, name)

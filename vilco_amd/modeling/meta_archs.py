@@ -294,11 +294,12 @@ class StepInputs:
     """device-resident inputs of one step (PtTransformer.prepare): feats_cf [B,Cin,T], lens int32 [B], text_cf
     [B,Ctxt,L], text_lens int32 [B], gt float [B, 3*Nmax+1] (training); the narration inputs of the fused SSL path:
     narr_cf [B,Cn,n_pad] tokens, narr_lens int32 [B] token counts, narr_mask float [B] (the clip has a narration); narr =
-    the unfused path's narration tuple or None; dist_tgt float [sum T_l, ldt] = the iCaRL distillation targets of the step
-    (the first cached clip's levels end to end, PtTransformer.distill_target) with dist_lens = (T_l, ...), or None"""
+    the unfused path's narration tuple or None; dist_tgt float [sum T_l, ldt] = the iCaRL / BiC distillation targets of the
+    step (one cached clip's levels end to end, PtTransformer.distill_target) with dist_lens = (T_l, ...), or None; dist_kind =
+    the method ('icarl' / 'bic') the caller that replays the step attached dist_tgt for (graph.GraphedStep._prepare), or None"""
     __slots__ = ("feats_cf", "lens", "T", "text_cf", "text_lens", "narr", "gt", "narr_cf", "narr_lens", "narr_mask",
-                 "dist_tgt", "dist_lens")
-    HOST = ("T", "narr", "dist_lens")          # not device buffers: a captured step takes them over as they are
+                 "dist_tgt", "dist_lens", "dist_kind")
+    HOST = ("T", "narr", "dist_lens", "dist_kind")          # not device buffers: a captured step takes them over as they are
 
     def tensors(self):
         """(name, tensor) of every device buffer a replayed step reads"""
@@ -307,7 +308,7 @@ class StepInputs:
 
     def signature(self):
         return (tuple((k, tuple(t.shape)) for k, t in self.tensors()) + (("narr", self.narr is not None),) +
-                (("dist_lens", getattr(self, "dist_lens", None)),))
+                (("dist_lens", getattr(self, "dist_lens", None)), ("dist_kind", getattr(self, "dist_kind", None))))
 
 
 @register_meta_arch("LocPointTransformer")
@@ -593,7 +594,7 @@ class PtTransformer(nn.Module):
         inp = StepInputs()
         inp.feats_cf, inp.lens, inp.T = self._batch_cf(video_list, is_training)
         inp.text_cf = inp.text_lens = inp.narr = inp.narr_cf = inp.narr_lens = inp.narr_mask = None
-        inp.dist_tgt = inp.dist_lens = None        # filled by the caller that replays the step (graph.GraphedStep)
+        inp.dist_tgt = inp.dist_lens = inp.dist_kind = None        # filled by the caller that replays the step (graph.GraphedStep)
         if self.use_cross_modal:
             inp.text_cf, inp.text_lens, narr = self._query_batch_cf(video_list, narr_pad=narr_pad)
             if isinstance(narr, dict):
@@ -641,9 +642,11 @@ class PtTransformer(nn.Module):
         kernels, a fixed prompt window, narration SSL only on its fused path -- the unfused one reads the mask sum and
         keeps the ring pointer on the host).  Distillation: an iCaRL step with n_known > 0 is capturable when its targets
         are resident on the device and travel in `inp.dist_tgt` (distill_target: the whole term is then ops.cl_distill
-        over a buffer a replay refreshes); NumPy targets are uploaded per step, a batch without a cached clip has no
-        target, and BiC's bias layers are ATen autograd: those steps stay eager, and so does any other step that is
-        handed targets."""
+        over a buffer a replay refreshes); NumPy targets are uploaded per step and a batch without a cached clip has no
+        target: those steps stay eager, and so does any other step that is handed targets.  A BiC step with n_known > 0
+        needs the same of its targets -- attached FOR BiC (`inp.dist_kind`, set by GraphedStep._prepare) -- and a bias
+        correction the device op takes (`_bic_op_ready`: one layer per split, the splits ending at the head's class count)
+        with every layer on the model's device; its alpha / beta are read from memory by the replayed kernel."""
         if not (self.fused_loss and self.sync_free_loss and self.train_loss_weight > 0 and self.num_classes <= 128):
             return False
         if inp.gt is None:
@@ -653,7 +656,15 @@ class PtTransformer(nn.Module):
         if self.n_known > 0 and self.cl_name == 'icarl':
             if getattr(inp, "dist_tgt", None) is None:
                 return False
-        elif prev_out_cls_logits or (self.n_known > 0 and self.cl_name == 'bic'):
+        elif self.n_known > 0 and self.cl_name == 'bic':
+            if getattr(inp, "dist_tgt", None) is None or getattr(inp, "dist_kind", None) != 'bic':
+                return False
+            if self.bic_raw_logits or not self._bic_op_ready():
+                return False
+            dev = self.device
+            if any(p.device != dev for l in self.list_bias_layers for p in (l.alpha, l.beta)):
+                return False
+        elif prev_out_cls_logits:
             return False
         if hasattr(self, 'prompt') and not (0 <= task_id and (task_id + 1) * self.prompt.top_k <= self.prompt.pool_size):
             return False
@@ -686,9 +697,12 @@ class PtTransformer(nn.Module):
             reduce_sim = res['reduce_sim']
 
         # training with fixed loss weights: labels + losses are ONE fused kernel pair (ops.mq_loss) that also applies the
-        # regression head's relu(Scale_l(x)); everything else (BiC, dynamic loss weight, get_emb, eval) keeps the lists
+        # regression head's relu(Scale_l(x)); everything else (dynamic loss weight, get_emb, eval, a BiC correction the device
+        # op does not take: a CPU model, a split table that does not end at the class count) keeps the lists
+        bic_loop = (self.n_known > 0 and self.cl_name == 'bic' and not self.bic_raw_logits
+                    and not (x_tm.is_cuda and self._bic_op_ready()))
         fused = (is_training and not get_emb and self.fused_loss and self.sync_free_loss and self.train_loss_weight > 0
-                 and not (self.n_known > 0 and self.cl_name == 'bic') and self.num_classes <= 128)
+                 and not bic_loop and self.num_classes <= 128)
         fpn_feats, fpn_lens, out_cls_logits, out_offsets = self._run_network(x_tm, lens, text_tm, text_lens,
                                                                             raw_offsets=fused)
 
@@ -704,7 +718,7 @@ class PtTransformer(nn.Module):
         points = self.point_generator(fpn_feats, lengths=level_T)
 
         if self.n_known > 0 and self.cl_name == 'bic' and not self.bic_raw_logits:
-            out_cls_logits = [self._bic_correct(x) for x in out_cls_logits]
+            out_cls_logits = self._bic_correct_levels(out_cls_logits)
 
         # [B, T_l] bool per level -- not needed by the fused training losses (they read the prefix lengths): 12 launches less on the
         # chain of a captured step (round 6)
@@ -757,7 +771,28 @@ class PtTransformer(nn.Module):
             return video_list, points, fpn_masks, out_cls_logits, out_offsets
         return results
 
+    def _bic_op_ready(self):
+        """the bias layers are something ops.bic_correct takes: one layer per split and the splits ending at the head's class
+        count (<= 128).  Anything else is the reference's slice-and-concatenate loop, whatever it makes of such a table."""
+        n, n_classes = len(self.list_splits), self.cls_head.cls_head.conv.out_channels
+        return 0 < n == len(self.list_bias_layers) and int(self.list_splits[-1]) == n_classes <= 128
+
+    def _bic_correct_levels(self, levels):
+        """the per-level list of head outputs, corrected (meta_archs.py:821-836).  On the device with the heads run over the
+        LevelCat layout this is ONE ops.bic_correct launch over the concatenated logits, which the fused loss and the
+        distillation term then read (`cat.cls_logits`); the levels are views of its result.  Out of place: the raw buffer is
+        left as the head wrote it."""
+        cat = self._cat
+        if (levels[0].is_cuda and self._bic_op_ready() and cat is not None
+                and getattr(cat, "cls_logits", None) is not None):
+            cat.cls_logits = ops.bic_correct(cat.cls_logits, self.list_splits, self.list_bias_layers)
+            return cat.split(cat.cls_logits)
+        return [self._bic_correct(x) for x in levels]
+
     def _bic_correct(self, logits):
+        """one tensor [..., ncls]: the device op where it applies, the reference's Python loop on a CPU model"""
+        if logits.is_cuda and self._bic_op_ready():
+            return ops.bic_correct(logits, self.list_splits, self.list_bias_layers)
         parts, lo = [], 0
         for i, hi in enumerate(self.list_splits):
             parts.append(self.list_bias_layers[i](logits[..., lo:hi]))
@@ -1000,13 +1035,20 @@ class PtTransformer(nn.Module):
         return prev_out_cls_logits
 
     def distill_target(self, prev_out_cls_logits):
-        """-> (buffer [sum T_l, ldt], (T_l, ...)): the iCaRL targets a step with these cached outputs distils against, as
-        the one contiguous device buffer ops.cl_distill reads (train_cl.cache_prev_logits stores a clip's levels as views
-        of such a buffer: nothing is copied then).  None when there is nothing a replayed step could carry: not an iCaRL
-        step with known classes, no cached clip in the batch, or host-side (NumPy) targets."""
-        if not (self.n_known > 0 and self.cl_name == 'icarl' and prev_out_cls_logits):
+        """-> (buffer [sum T_l, ldt], (T_l, ...)): the iCaRL / BiC targets a step with these cached outputs distils against,
+        as the one contiguous device buffer ops.cl_distill reads (train_cl.cache_prev_logits stores a clip's levels as views
+        of such a buffer: nothing is copied then).  iCaRL is handed the list over the batch's cached clips and takes the
+        first; BiC is handed ONE clip's per-level list (train_one_epoch: the last cached clip's).  None when there is
+        nothing a replayed step could carry: not an iCaRL / BiC step with known classes, no cached clip in the batch, or
+        host-side (NumPy) targets."""
+        if not (self.n_known > 0 and self.cl_name in ('icarl', 'bic') and prev_out_cls_logits):
             return None
-        levels = self._icarl_levels(prev_out_cls_logits, len(self.fpn_strides))
+        if self.cl_name == 'bic':
+            levels = prev_out_cls_logits
+            if len(levels) != len(self.fpn_strides):
+                return None
+        else:
+            levels = self._icarl_levels(prev_out_cls_logits, len(self.fpn_strides))
         if not all(torch.is_tensor(t) and t.is_cuda for t in levels):
             return None
         return ops.distill_targets(levels, self.device)
@@ -1016,7 +1058,7 @@ class PtTransformer(nn.Module):
         bic = self.cl_name == 'bic'
         level_T = tuple(int(x.shape[1]) for x in out_cls_logits)
         tgt, self._dist_tgt = getattr(self, "_dist_tgt", None), None
-        if tgt is None or bic:
+        if tgt is None:
             levels = prev_out_cls_logits if bic else self._icarl_levels(prev_out_cls_logits, len(level_T))
             if len(levels) != len(level_T):
                 raise ValueError("distillation targets of %d levels for a pyramid of %d" % (len(levels), len(level_T)))

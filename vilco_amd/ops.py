@@ -2025,6 +2025,139 @@ def cl_distill(logits, level_row, level_T, targets, n_known, mode, scale, clip=0
                             (int(n_known), int(mode), float(scale), int(clip)))
 
 
+# ---------------------------------------------------------------------------------------- BiC bias correction
+_bic_tabs = {}
+
+
+def bic_split_table(splits, n_classes, n_layers):
+    """list_splits of a BiC model -> the validated tuple of cumulative column ends: non-empty, strictly increasing from above
+    0, ending at n_classes <= 128, one bias layer per split.  Anything else raises (the C launcher checks the same again,
+    before any device work)."""
+    ends = tuple(int(v) for v in splits)
+    if not ends:
+        raise ValueError("bic_correct: the split table is empty")
+    if int(n_layers) != len(ends):
+        raise ValueError("bic_correct: %d bias layers for %d splits" % (int(n_layers), len(ends)))
+    if int(n_classes) > 128:
+        raise ValueError("bic_correct: %d classes, the kernels take at most 128" % int(n_classes))
+    if ends[0] <= 0 or any(b <= a for a, b in zip(ends, ends[1:])):
+        raise ValueError("bic_correct: the splits %s are not strictly increasing cumulative ends" % (ends,))
+    if ends[-1] != int(n_classes):
+        raise ValueError("bic_correct: the last split ends at column %d, the logits have %d" % (ends[-1], int(n_classes)))
+    return ends
+
+
+def _bic_table(ends, params, device):
+    """(host int32 [S] ends, device int64 [3][S]: the addresses of every alpha and beta, the ends) -- the `_ptr_table` of this op,
+    on the device because the kernel walks it.  Made once per (splits, parameter addresses) and kept: a captured step
+    addresses it, and the VALUES behind the addresses are read when the kernel runs."""
+    ptrs = tuple(p.data_ptr() for p in params)
+    key = (ends, ptrs, str(device))
+    tab = _bic_tabs.get(key)
+    if tab is None:
+        S = len(ends)
+        tab = _bic_tabs[key] = ((C.c_int32 * S)(*ends),
+                                torch.tensor([ptrs[0::2], ptrs[1::2], ends], dtype=torch.int64, device=device))
+    return tab
+
+
+def _bic_rows(t, inplace=False):
+    """[..., C] float tensor -> (tensor, rows, row stride): rows laid out at one constant stride are taken as they are (the
+    columns C .. stride of such a buffer are neither read nor written), anything else is made contiguous first"""
+    Cn = t.shape[-1]
+    rows = t.numel() // max(Cn, 1)
+    ok = t.stride(-1) == 1 and t.dim() >= 2 and t.stride(-2) >= Cn
+    if ok:
+        ld = t.stride(-2)
+        exp = ld * t.shape[-2]
+        for k in range(t.dim() - 3, -1, -1):
+            ok = ok and (t.shape[k] == 1 or t.stride(k) == exp)
+            exp *= t.shape[k]
+    if not ok or rows == 0:
+        if inplace:
+            raise ValueError("bic_correct: an in-place call needs rows at one constant stride, got strides %s" % (tuple(t.stride()),))
+        t = t.contiguous()
+        ld = Cn
+    if ld >= 1 << 31:
+        raise ValueError("bic_correct: row stride %d" % ld)
+    return t, rows, ld
+
+
+class _BicCorrect(torch.autograd.Function):
+    """y = alpha[s(c)] x + beta[s(c)] over the concatenated head output (vilco_bic_correct_fwd / _bwd): one launch each way; the
+    parameter gradients (two more launches, fixed-order sums) only when a layer requires one"""
+
+    @staticmethod
+    def forward(ctx, x, tab, inplace, *params):
+        lib = _lib.load()
+        ctx.want = any(ctx.needs_input_grad[3:])
+        if ctx.want and inplace:
+            raise RuntimeError("bic_correct: in place the input is gone, and a layer that requires a gradient needs it")
+        x, rows, ldx = _bic_rows(x, inplace)
+        if inplace:
+            y, ldy = x, ldx
+            ctx.mark_dirty(x)
+        else:
+            y, ldy = torch.empty(x.shape, dtype=torch.float32, device=x.device), x.shape[-1]
+        d = _lib.BicCorrectDesc()
+        d.x, d.y, d.splits, d.table = x.data_ptr(), y.data_ptr(), C.addressof(tab[0]), tab[1].data_ptr()
+        d.rows, d.C, d.S, d.ldx, d.ldy, d.n_layers = rows, x.shape[-1], len(tab[0]), ldx, ldy, len(params) // 2
+        _lib.check(lib.vilco_bic_correct_fwd(C.byref(d), _stream()))
+        ctx.tab, ctx.geom = tab, (rows, x.shape[-1], ldx)
+        ctx.save_for_backward(*((x,) if ctx.want else ()))
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        lib = _lib.load()
+        tab, (rows, Cn, ldx) = ctx.tab, ctx.geom
+        S = len(tab[0])
+        dy = dy.contiguous().float()
+        dx = torch.empty_like(dy)
+        d = _lib.BicCorrectDesc()
+        d.x, d.y, d.splits, d.table = dy.data_ptr(), dx.data_ptr(), C.addressof(tab[0]), tab[1].data_ptr()
+        d.rows, d.C, d.S, d.ldx, d.ldy, d.n_layers = rows, Cn, S, Cn, Cn, S
+        dpar = ws = x = None
+        nws = 0
+        if ctx.want:
+            x, = ctx.saved_tensors
+            dpar = torch.empty(2, S, dtype=torch.float32, device=dy.device)
+            nws = lib.vilco_bic_correct_bwd_workspace(rows)
+            ws = _ws(nws, dy.device)
+        _lib.check(lib.vilco_bic_correct_bwd(C.byref(d), _p(x), ldx, _p(dpar), _p(ws), nws, _stream()))
+        grads = [None] * (2 * S)
+        for i in range(2 * S):
+            if ctx.needs_input_grad[3 + i]:
+                grads[i] = dpar[i % 2, i // 2:i // 2 + 1]
+        return (dx, None, None) + tuple(grads)
+
+
+def bic_correct(logits, splits, layers, inplace=False):
+    """BiC's bias layers over their column ranges of the head output (include/vilco_hip.h: vilco_bic_correct_desc):
+    logits [..., C] fp32 on the device, rows at one constant stride >= C (the LevelCat / loss-table layout, separator rows
+    included: every row gets the affine); splits = list_splits; layers = list_bias_layers (each .alpha, .beta: float32 [1] on
+    the logits' device).  alpha and beta are read on the device when the kernel runs.  inplace=True writes into `logits`
+    (frozen layers only).  A bad split table, a CPU tensor or a layer elsewhere raises."""
+    if not torch.is_tensor(logits) or not logits.is_cuda:
+        raise RuntimeError("vilco_amd ops run on the HIP device only (got a %s tensor); there is no CPU fallback"
+                           % (logits.device if torch.is_tensor(logits) else type(logits).__name__))
+    if logits.dtype != torch.float32:
+        raise RuntimeError("expected scalar type Float, got %s" % logits.dtype)
+    if logits.dim() < 2:
+        raise ValueError("bic_correct: logits must be [..., rows, C]")
+    ends = bic_split_table(splits, logits.shape[-1], len(layers))
+    params = []
+    for l in layers:
+        for p in (l.alpha, l.beta):
+            if p.device != logits.device:
+                raise RuntimeError("bic_correct: a bias layer lives on %s, the logits on %s" % (p.device, logits.device))
+            if p.dtype != torch.float32 or p.numel() != 1:
+                raise RuntimeError("bic_correct: alpha / beta must be float32 [1], got %s %s" % (p.dtype, tuple(p.shape)))
+            params.append(p)
+    tab = _bic_table(ends, params, logits.device)
+    return _BicCorrect.apply(logits, tab, bool(inplace), *params)
+
+
 # ---------------------------------------------------------------------------------------- inference decode
 def decode(logits, offsets, points, level_row0, level_len, topk, pre_nms_thresh, duration_thresh):
     """vilco_decode: threshold -> exact top-k -> segment decode -> duration filter of one clip's pyramid (all levels, one

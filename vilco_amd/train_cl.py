@@ -211,7 +211,7 @@ def run_episodes(cfg, model, train_stream, validate=None, ckpt_folder=None, gpu_
 
 
 def run_episodes_bic(cfg, model, train_stream, validate=None, ckpt_folder=None, gpu_id=0, combine_train=False,
-                     stage2_epochs=None, stage2_lr=0.001, logger=None, print_freq=20, keep_history=True):
+                     stage2_epochs=None, stage2_lr=0.001, logger=None, print_freq=20, keep_history=True, use_graph=False):
     """The episode loop of BiC (cl_cfg.name = 'bic'; MQ/train_bic.py:210-760) in its order of events, through the pieces
     of `run_episodes`.  train_stream: `utils.cl_stream.InMemoryBiCStream`'s contract, next() -> (data, stage-1 loader,
     held-out loader or None, num_next_classes).  Per task j:
@@ -229,11 +229,20 @@ def run_episodes_bic(cfg, model, train_stream, validate=None, ckpt_folder=None, 
       if another task follows: augment_classification, a NEW optimizer and scheduler           (:578-599)
 
     stage2_epochs: epochs of stage 2 (default: as many as stage 1, as in the reference); stage2_lr: its SGD learning rate
-    (:622).  Single process (the reference's stage 2 is not data parallel either).  Returns (model, optimizer, scheduler,
+    (:622).  use_graph: replay the stage-1 iterations as hipGraphs, as in `run_episodes` (a fresh GraphedStep per optimizer,
+    i.e. per task; from the second task on the captured step holds the bias correction, ops.bic_correct, which reads alpha /
+    beta from the layers' memory).  Single process (the reference's stage 2 is not data parallel either).  Returns (model, optimizer, scheduler,
     log); a task's log entry has 'bic' = {'alpha', 'beta', 'before', 'after', 'losses'} after a stage 2."""
     from .cl_methods.bic import BiCCache, fit_bias_layer, newest_split
     from .utils.cl_stream import DistributedBatchLoader
     optimizer = make_optimizer(model, cfg['opt'])
+
+    def make_graph(opt):
+        if not use_graph:
+            return None
+        from .graph import GraphedStep
+        return GraphedStep(model, opt, clip_grad_l2norm=cfg['train_cfg']['clip_grad_l2norm'])
+    graph = make_graph(optimizer)
     it = iter(train_stream)
     num_tasks = train_stream.num_tasks
     max_epochs = cfg['opt'].get('early_stop_epochs', cfg['opt']['epochs'] + cfg['opt']['warmup_epochs'])
@@ -269,7 +278,8 @@ def run_episodes_bic(cfg, model, train_stream, validate=None, ckpt_folder=None, 
             hist = train_one_epoch(loader, model, optimizer, scheduler, epoch, 1, model_ema=None,
                                    clip_grad_l2norm=cfg['train_cfg']['clip_grad_l2norm'], print_freq=print_freq,
                                    logger=logger, cl_name=cfg['cl_cfg']['name'], reg_lambda=cfg['cl_cfg']['reg_lambda'],
-                                   prev_out_cls_logits_dict=prev_logits, current_task_id=j, keep_history=keep_history)
+                                   prev_out_cls_logits_dict=prev_logits, current_task_id=j, graph=graph,
+                                   keep_history=keep_history)
             if keep_history:
                 entry['history'].append(hist)
             if combine_train or epoch < max_epochs // 3:
@@ -318,6 +328,7 @@ def run_episodes_bic(cfg, model, train_stream, validate=None, ckpt_folder=None, 
             model.augment_classification(num_next, torch.device('cuda', gpu_id))
             optimizer = make_optimizer(model, cfg['opt'])
             scheduler = make_scheduler(optimizer, cfg['opt'], len(loader))
+            graph = make_graph(optimizer)          # new parameters, new optimizer: the old task's graphs are dropped
     return model, optimizer, scheduler, log
 
 
