@@ -723,8 +723,12 @@ def test_gemm_output_amax_partials(dev, M, N, K, act):
     # an in-place edit invalidates the tag (and the remembered operand planes)
     planes = ops.pack(C, M, N)
     assert ops.pack(C, M, N) is planes
+    C3 = C.view(1, M, N)                    # (a view shares C's version counter)
+    tap = ops.pack_tap(C3)
+    assert ops.pack_tap(C3) is tap
     C.mul_(2.0)
     assert ops._amax_of(C)[0] is None and ops.pack(C, M, N) is not planes
+    assert ops._planes_of(C3, "seq", C3.shape, ops.get_precision()) is None and ops.pack_tap(C3) is not tap
 
 
 @pytest.mark.parametrize("M,N,K", [(288, 1024, 768), (154, 1024, 768), (144, 1024, 512), (576, 512, 512), (640, 512, 512), (16, 512, 512),
@@ -944,11 +948,11 @@ def test_layernorm_writes_operand_planes(dev, B, T, C, relu, layout):
     y_ref = ops.layernorm(x, g, bt, 1e-5, relu).detach()
     y = ops.layernorm(x, g, bt, 1e-5, relu, planes=layout)
     assert torch.equal(y.detach(), y_ref)
-    hit = getattr(y, "_vilco_planes" if layout == "nat" else "_vilco_tap_planes", None)
+    planes = ops._planes_of(y, layout, (B * T, C) if layout == "nat" else (B, T, C), 3)
     if (C % 32 if layout == "nat" else C % 8):
-        assert hit is None          # unsupported width: the hint is ignored, the consumer packs
+        assert planes is None       # unsupported width: the hint is ignored, the consumer packs
         return
-    planes = hit[0]
+    assert planes is not None
     assert (ops.pack(y, B * T, C) if layout == "nat" else ops.pack_tap(y)) is planes          # what the consumer will find
     hdr = planes[:4096 + 512].view(torch.float32)
     inv_s, s = float(hdr[1024]), float(hdr[1025])
@@ -1000,8 +1004,8 @@ def test_layernorm_row_mask_equals_masking_afterwards(dev):
         x, g, b = x0.clone().requires_grad_(True), g0.clone().requires_grad_(True), b0.clone().requires_grad_(True)
         y = ops.layernorm(x, g, b, 1e-5, True, "seq", mask) if fused else ops.layernorm(x, g, b, 1e-5, True) * mask
         if fused:
-            planes = ops.pack_tap(y)
-            assert planes is y._vilco_tap_planes[0]
+            planes = ops._planes_of(y, "seq", (B, T, C), 3)
+            assert planes is not None and ops.pack_tap(y) is planes
             parts, n = ops._amax_of(y)
             assert float(parts[:n].max()) == float(y.abs().max())
         y.backward(dy)
@@ -1070,6 +1074,61 @@ def test_pack_group_equals_single_packs_and_keeps_the_cache(dev):
     assert mixed[1] is first and torch.equal(mixed[0][hdr:], ops.pack(zs[0].clone(), 300, 96)[hdr:])
 
 
+def test_hints_reach_their_consumers(dev, monkeypatch):
+    """Producer hints at chain level: every hint that is found saves its consumer a pack launch (operand planes) or the amax
+    half of one (max|x| partials: vilco_pack_many instead of vilco_pack), and one that is NOT found costs nothing but that --
+    the results stay equal on the fallback path.  So the calls of the two pack entries are counted, forward and backward, over
+    the three producer -> consumer chains of the model at the smallest shapes that take the producer paths."""
+    from vilco_amd import _lib, ops
+    lib = _lib.load()
+    monkeypatch.setattr(ops, "_precision", 3)                # fp16 x2
+    calls = {"vilco_pack": 0, "vilco_pack_many": 0}
+
+    def spy_on(name):
+        real = getattr(lib, name)
+
+        def spy(*a):
+            calls[name] += 1
+            return real(*a)
+        monkeypatch.setattr(lib, name, spy)
+
+    for name in calls:
+        spy_on(name)
+    torch.manual_seed(17)
+    B, T, C, H = 2, 64, 64, 1
+    lens = torch.tensor([64, 41], dtype=torch.int32, device=dev)
+
+    def leaf(*shape, scale=1.0):
+        return (torch.randn(*shape, device=dev) * scale).requires_grad_(True)
+
+    def ln_mlp():
+        y = ops.layernorm(leaf(B, T, C), leaf(C), leaf(C), 1e-5, False, planes="nat")
+        h = ops.linear(y, leaf(4 * C, C, scale=0.125), leaf(4 * C), ops.ACT_GELU, lens, T)
+        return ops.linear(h, leaf(C, 4 * C, scale=0.0625), leaf(C))
+
+    def ln_conv_ln():
+        y = ops.layernorm(leaf(B, T, C), leaf(C), leaf(C), 1e-5, True, planes="seq")
+        z = ops.conv3(y, leaf(C, C, 3, scale=0.125), leaf(C), lens)
+        return ops.layernorm(z, leaf(C), leaf(C), 1e-5, True)
+
+    def qkv_attn_proj():
+        q, k, v = ops.linear_group([leaf(B, T, C) for _ in range(3)], [leaf(C, C, scale=0.125) for _ in range(3)],
+                                   [leaf(C) for _ in range(3)])
+        return ops.linear(ops.attention(q, k, v, lens, H), leaf(C, C, scale=0.125), leaf(C))
+
+    got = {}
+    for chain in (ln_mlp, ln_conv_ln, qkv_attn_proj):
+        for k in calls:
+            calls[k] = 0
+        out = chain()
+        fwd = (calls["vilco_pack"], calls["vilco_pack_many"])
+        out.backward(torch.ones_like(out) / 8)
+        got[chain.__name__] = (fwd, (calls["vilco_pack"] - fwd[0], calls["vilco_pack_many"] - fwd[1]))
+    print("pack calls (vilco_pack, vilco_pack_many), forward and backward:", got)
+    # counted by running this test body at commit 7840d3f, the last one with per-attribute hints and `last_*` hand-overs
+    assert got == {"ln_mlp": ((2, 1), (1, 0)), "ln_conv_ln": ((1, 0), (1, 0)), "qkv_attn_proj": ((4, 1), (1, 1))}
+
+
 @pytest.mark.parametrize("masked_by", ["row_mask", "lens"])
 def test_conv3_backward_writes_dz_image_from_the_mask_kernel(dev, masked_by):
     """Round 6 (vilco_act_bwd_desc.seq_len + vilco_ln_bwd_desc.dx_amax_parts): conv k=3 -> LayerNorm -> ReLU, the heads' / embeddings'
@@ -1133,9 +1192,8 @@ def test_attention_writes_output_planes(dev, B, Tq, Tk, H, lens):
     v = torch.randn(B, Tk, C, device=dev) * 3
     lt = torch.tensor(lens, dtype=torch.int32, device=dev)
     o = ops.attention(q, k, v, lt, H, 0.125)
-    hit = getattr(o, "_vilco_planes", None)
-    assert hit is not None and ops.pack(o, B * Tq, C) is hit[0]
-    planes = hit[0]
+    planes = ops._planes_of(o, "nat", (B * Tq, C), 3)
+    assert planes is not None and ops.pack(o, B * Tq, C) is planes
     hdr = planes[:4096 + 512].view(torch.float32)
     inv_s, s = float(hdr[1024]), float(hdr[1025])
     vmax = float(v.abs().max())
@@ -1153,7 +1211,7 @@ def test_attention_writes_output_planes(dev, B, Tq, Tk, H, lens):
         try:
             qq, kk, vv, ww = [t.clone().requires_grad_(True) for t in (q, k, v, w)]
             oo = ops.attention(qq, kk, vv, lt, H, 0.125)
-            assert (getattr(oo, "_vilco_planes", None) is not None) == on
+            assert (ops._planes_of(oo, "nat", (B * Tq, C), 3) is not None) == on
             y = ops.linear(oo, ww)
             y.backward(torch.ones_like(y) / 5)
             res.append((y.detach(), qq.grad, vv.grad, ww.grad))

@@ -150,8 +150,7 @@ class _Census:
             am = b[w + "_amax"]
             if am is not None and am[0] is not None and prec in (3, 4) and pl is None and X is not None:
                 mx = float(am[0][:int(am[1])].max())
-                tag = getattr(X, "_vilco_amax", None)
-                if tag is not None and tag[0] is am[0] and tag[2] == X._version:
+                if ops._amax_of(X)[0] is am[0]:
                     whole = float(X.detach().abs().max())
                     if mx != whole:
                         checks.append("%s_amax: the producer's partials give max %r, max|x| of the operand tensor is %r" % (w, mx, whole))
@@ -172,7 +171,7 @@ class _Census:
         snap["colscale"] = None if b["colscale"] is None else b["colscale"].detach().clone()
         snap["row_len"] = None if b["row_len"] is None else b["row_len"].detach().cpu().tolist()
         snap["row_mask"] = None if b["row_mask"] is None else b["row_mask"].detach().clone()
-        snap["amax_tag_before"] = getattr(Cc, "_vilco_amax", (None,))[0]
+        snap["amax_tag_before"] = ops._amax_of(Cc)[0]
         snap["checks"] = checks
         return snap
 
@@ -297,8 +296,8 @@ class _Census:
                 if nbad:
                     msgs.append("%d masked / dropped entries are not exactly %s" % (nbad, "the residual" if res is not None else "zero"))
         # partials of max|C| written by the call
-        tag = getattr(b["Cc"], "_vilco_amax", None)
-        if tag is not None and tag[0] is not snap["amax_tag_before"]:
+        tag = ops._amax_of(b["Cc"])
+        if tag[0] is not None and tag[0] is not snap["amax_tag_before"]:
             mx, whole = float(tag[0][:tag[1]].max()), float(b["Cc"].detach().abs().max())
             if mx != whole:
                 msgs.append("amax_out: partials give max %r, max|C| = %r" % (mx, whole))

@@ -455,13 +455,116 @@ def gemm_group(calls):
             _tag_amax(Cc, parts, n)
 
 
-# ---- amax partials left by the producing kernel.  The fp16 x2 planes need max|x| of the whole tensor before anything can be
+# ---- what a producer already knows about its output.  The fp16 x2 planes need max|x| of the whole tensor before anything can be
 # packed; kernels whose output goes (mostly) straight into a matrix product -- LayerNorm forward, the fused q/k/v
-# pre-projection, the activation backward -- leave per-block partial maxima next to their output, tagged on the tensor
-# as `_vilco_amax = (partials, count, version)`; `pack` hands them to vilco_pack_many, which then skips its amax launch.
-# The tag is ignored once the tensor's version counter moved (in-place edits) or another precision is active.
+# pre-projection, the activation backward, the GEMM epilogues -- leave per-block partial maxima next to their output ("amax":
+# `pack` hands them to vilco_pack_many, which then skips its amax launch), and some write the output's fp16 operand planes
+# themselves ("planes": the consumer's `pack` / `pack_tap` is then a lookup, like for a tensor that was packed before).
+# Both hang on the tensor as ONE record (`_Hints`), read and written through the accessors below and nowhere else.
+# amax is ignored once the tensor's version counter moved (in-place edits) or another precision is active.
 produce_amax = os.environ.get("VILCO_PRODUCER_AMAX", "1") != "0"
 AMAX_PARTS = 2048
+_pack_cache = os.environ.get("VILCO_PACK_CACHE", "1") != "0"
+
+
+class _Hints:
+    """The record of one tensor.  All of it describes the tensor's values at `version` (torch's in-place counter): once the
+    counter has moved the whole record is dead, amax and planes alike.
+    amax: (partials, count) of max|x|, or None;  planes: {layout: (plane buffer, `_plane_key`, `_cache_mark`)}, or None.
+    (No __init__: some 500 of these are made per eager step, and a Python-level constructor doubles their cost.)"""
+    __slots__ = ("version", "amax", "planes")
+
+
+def _hints(t, create=False):
+    """the record on t if it still describes t, else None -- create: else a fresh one, hung on t"""
+    rec = getattr(t, "_vilco_hints", None)
+    if rec is not None and rec.version == t._version:
+        return rec
+    if not create:
+        return None
+    rec = t._vilco_hints = _Hints()
+    rec.version, rec.amax, rec.planes = t._version, None, None
+    return rec
+
+
+def _tag_amax(t, parts, n):
+    if n > 0:
+        _hints(t, True).amax = (parts, int(n))
+    return t
+
+
+def _amax_of(x):
+    rec = _hints(x) if produce_amax else None
+    return (None, 0) if rec is None or rec.amax is None else rec.amax
+
+
+def _cache_mark(x):
+    """the stream the planes remembered on x were written on, while capturing.  Inside a stream capture independent chains run on side
+    streams (fork_enabled), and a chain that finds another chain's planes in this Python-level cache has no edge to the pack
+    that writes them: `_cache_ok` treats such a hit as a miss and the chain packs its own (an event behind every pack would
+    order it, at the price of ~290 extra event records per captured step).  Eager steps run on one stream."""
+    return torch.cuda.current_stream() if x.is_cuda and torch.cuda.is_current_stream_capturing() else None
+
+
+def _cache_ok(mark):
+    return mark is None or not torch.cuda.is_current_stream_capturing() or mark == torch.cuda.current_stream()
+
+
+def _plane_key(layout, shape, prec):
+    """what remembered planes are valid for.  layout "nat": the row-major matrix shape = (rows, cols) that `pack` reads;
+    "seq": the k=3 convs' zero-padded per-sequence image of shape = (B, T, C), `pack_tap`."""
+    return (layout, tuple(shape), prec)
+
+
+def _planes_of(x, layout, shape, prec, any_stream=False):
+    """the planes remembered on x for this layout, shape and precision, or None.  any_stream: also those a capture wrote on
+    another stream (which a consumer must not read: see `_cache_mark`)."""
+    rec = _hints(x) if _pack_cache else None
+    ent = rec.planes.get(layout) if rec is not None and rec.planes is not None else None
+    if ent is None or ent[1] != _plane_key(layout, shape, prec) or not (any_stream or _cache_ok(ent[2])):
+        return None
+    return ent[0]
+
+
+def _remember_planes(x, layout, shape, prec, buf):
+    if _pack_cache:
+        rec = _hints(x, True)
+        if rec.planes is None:
+            rec.planes = {}
+        rec.planes[layout] = (buf, _plane_key(layout, shape, prec), _cache_mark(x))
+    return buf
+
+
+# ---- hints across Function.apply.  Attributes set on a tensor inside `forward` do not survive apply() (autograd hands back
+# other Python objects), so a producer LEAVES its hints (`_leave`) and its public wrapper calls the Function through `_apply`,
+# which hangs them on the tensors apply() returned, by output position.  One frame per `_apply` in flight: a wrapper called
+# from inside another Function's forward has its own, and the outer one is on top again when it returns.
+_handover = []
+
+
+def _leave(fn, i, amax=None, planes=None, layout="nat"):
+    """from fn.forward: output i of this call carries `amax` = (partials, count) of max|x| and / or `planes`, its fp16 x2
+    operand planes in `layout` (producers write no other format).  Kept only when fn was called through `_apply`."""
+    if _handover and _handover[-1][0] is fn:
+        _handover[-1].append((i, amax, planes, layout))
+
+
+def _apply(fn, *args):
+    """fn.apply(*args), with what fn.forward left hung on the outputs"""
+    frame = [fn]                         # then what `_leave` adds
+    _handover.append(frame)
+    try:
+        out = fn.apply(*args)
+    finally:
+        _handover.pop()                  # (also when forward raises: nothing of this call can land on the next one's output)
+    for i, amax, planes, layout in frame[1:]:
+        t = out[i] if isinstance(out, tuple) else out
+        if planes is not None:
+            Cn = t.shape[-1]
+            _remember_planes(t, layout, t.shape if layout == "seq" else (t.numel() // Cn, Cn), 3, planes)
+        if amax is not None and amax[0] is not None:
+            _tag_amax(t, *amax)
+    return out
 
 
 # ---- cuts of the autograd graph (vilco_amd.graph.GraphedStep, data-parallel replays; SURVEY.md 8e).  With a tape active the
@@ -485,55 +588,30 @@ def seg_cut(x, next_stage=False):
     if tape is None or not torch.is_tensor(x) or not x.requires_grad:
         return x
     leaf = x.detach().requires_grad_(True)
-    for k in ("_vilco_amax", "_vilco_planes", "_vilco_tap_planes"):     # producer-written operand planes / maxima travel along
-        if hasattr(x, k):
-            setattr(leaf, k, getattr(x, k))
+    rec = _hints(x)
+    if rec is not None:                    # producer-written operand planes / maxima travel along (the leaf shares x's version counter)
+        mine = _hints(leaf, True)
+        mine.amax, mine.planes = rec.amax, None if rec.planes is None else dict(rec.planes)
     tape.records.append((x, leaf, tape.stage))
     if next_stage:
         tape.stage += 1
     return leaf
 
 
-def _tag_amax(t, parts, n):
-    if n > 0:
-        t._vilco_amax = (parts, int(n), t._version)
-    return t
-
-
-def _amax_of(x):
-    tag = getattr(x, "_vilco_amax", None)
-    if tag is None or tag[2] != x._version or not produce_amax:
-        return None, 0
-    return tag[0], tag[1]
-
-
-_pack_cache = os.environ.get("VILCO_PACK_CACHE", "1") != "0"
-
-
-def _cache_mark():
-    """the stream cached planes were packed on, while capturing.  Inside a stream capture independent chains run on side
-    streams (fork_enabled), and a chain that finds another chain's planes in this Python-level cache has no edge to the pack
-    that writes them: `_cache_ok` treats such a hit as a miss and the chain packs its own (an event behind every pack would
-    order it, at the price of ~290 extra event records per captured step).  Eager steps run on one stream."""
-    if not torch.cuda.is_current_stream_capturing():
-        return None
-    if _cache_events:                      # (A/B toggle: the event form)
-        ev = torch.cuda.Event()
-        ev.record()
-        return (torch.cuda.current_stream(), ev)
-    return (torch.cuda.current_stream(), None)
-
-
-def _cache_ok(mark):
-    if mark is None or not torch.cuda.is_current_stream_capturing() or mark[0] == torch.cuda.current_stream():
-        return True
-    if mark[1] is not None:
-        torch.cuda.current_stream().wait_event(mark[1])
-        return True
-    return False
-
-
-_cache_events = os.environ.get("VILCO_CACHE_EVENTS", "0") == "1"
+def _pack_item(it, x, rows, cols, prec, nbatch=1, relshift=False, seq_len=0, nbytes=None):
+    """fill the vilco_pack_item `it` for the fp32 source x (`nbatch` contiguous [rows, cols] matrices), with the max|x|
+    partials x's producer left and a fresh plane buffer of `nbytes` (None: as many as the item asks for) -> that buffer"""
+    it.src, it.rows, it.cols, it.ld = x.data_ptr(), int(rows), int(cols), int(cols)
+    it.nbatch, it.batch_stride = int(nbatch), int(rows) * int(cols) if nbatch > 1 else 0
+    it.relshift, it.seq_len = int(bool(relshift)), int(seq_len)
+    parts, n = _amax_of(x) if prec == 3 else (None, 0)       # max|x| partials left by the producer of the whole tensor
+    if parts is not None:
+        it.amax, it.namax = parts.data_ptr(), n
+    if nbytes is None:
+        nbytes = _lib.load().vilco_pack_item_bytes(C.byref(it), prec)
+    buf = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+    it.planes, it.planes_bytes = buf.data_ptr(), nbytes
+    return buf
 
 
 def pack(x, rows, cols, precision=None):
@@ -542,72 +620,43 @@ def pack(x, rows, cols, precision=None):
     remembered on the tensor: an activation that feeds several layers (XLNet's h -> q, k, v) is packed once."""
     lib = _lib.load()
     prec = _precision if precision is None else int(precision)
-    key = (int(rows), int(cols), prec, x._version)
-    hit = getattr(x, "_vilco_planes", None) if _pack_cache else None
-    if hit is not None and hit[1] == key and _cache_ok(hit[2]):
-        return hit[0]
+    buf = _planes_of(x, "nat", (rows, cols), prec)
+    if buf is not None:
+        return buf
     nbytes = lib.vilco_pack_bytes(int(rows), int(cols), prec)
-    buf = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
-    parts, n = _amax_of(x) if prec == 3 else (None, 0)
-    if parts is None:
+    if prec != 3 or _amax_of(x)[0] is None:
+        buf = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
         _lib.check(lib.vilco_pack(x.data_ptr(), int(rows), int(cols), int(cols), prec, buf.data_ptr(), nbytes, _stream()))
     else:
         it = _lib.PackItem()
-        it.src, it.rows, it.cols, it.ld = x.data_ptr(), int(rows), int(cols), int(cols)
-        it.planes, it.planes_bytes, it.nbatch, it.batch_stride, it.relshift = buf.data_ptr(), nbytes, 1, 0, 0
-        it.amax, it.namax = parts.data_ptr(), n
+        buf = _pack_item(it, x, rows, cols, prec, nbytes=nbytes)
         _lib.check(lib.vilco_pack_many(C.byref(it), 1, prec, _stream()))
-    if _pack_cache:
-        x._vilco_planes = (buf, key, _cache_mark())
-    return buf
+    return _remember_planes(x, "nat", (rows, cols), prec, buf)
 
 
 def pack_tap(x, precision=None):
     """x [B, T, C] (C % 8 == 0) -> the operand planes the k=3 convs read: every sequence with a zero row before and after it
     (vilco_pack_item.seq_len).  One pack of a conv's input serves its forward product and its weight gradient; one pack of
     the output gradient serves dX and the weight gradient.  Remembered on the tensor like `pack`."""
-    lib = _lib.load()
     prec = _precision if precision is None else int(precision)
+    buf = _planes_of(x, "seq", x.shape, prec)
+    if buf is not None:
+        return buf
     B, T, Cn = x.shape
-    key = ("tap", int(B), int(T), int(Cn), prec, x._version)
-    hit = getattr(x, "_vilco_tap_planes", None) if _pack_cache else None
-    if hit is not None and hit[1] == key and _cache_ok(hit[2]):
-        return hit[0]
     it = _lib.PackItem()
-    it.src, it.rows, it.cols, it.ld = x.data_ptr(), int(B * T), int(Cn), int(Cn)
-    it.nbatch, it.batch_stride, it.relshift, it.seq_len = 1, 0, 0, int(T)
-    parts, n = _amax_of(x) if prec == 3 else (None, 0)
-    if parts is not None:
-        it.amax, it.namax = parts.data_ptr(), n
-    nbytes = lib.vilco_pack_item_bytes(C.byref(it), prec)
-    buf = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
-    it.planes, it.planes_bytes = buf.data_ptr(), nbytes
-    _lib.check(lib.vilco_pack_many(C.byref(it), 1, prec, _stream()))
-    if _pack_cache:
-        x._vilco_tap_planes = (buf, key, _cache_mark())
-    return buf
+    buf = _pack_item(it, x, B * T, Cn, prec, seq_len=T)
+    _lib.check(_lib.load().vilco_pack_many(C.byref(it), 1, prec, _stream()))
+    return _remember_planes(x, "seq", x.shape, prec, buf)
 
 
 def pack_many(items, precision=None, nbatch=1, relshift=False):
     """[(x, rows, cols), ...] (at most four) packed by the same two launches -> list of plane buffers.
     nbatch > 1: every x holds `nbatch` contiguous [rows, cols] matrices (planes for batched GEMMs);
     relshift: pack XLNet's unshifted [rows, rows + cols] view of each matrix (vilco_pack_item.relshift)."""
-    lib = _lib.load()
     prec = _precision if precision is None else int(precision)
     arr = (_lib.PackItem * len(items))()
-    bufs, keep = [], []
-    for it, (x, rows, cols) in zip(arr, items):
-        it.src, it.rows, it.cols, it.ld = x.data_ptr(), int(rows), int(cols), int(cols)
-        it.nbatch, it.batch_stride, it.relshift = int(nbatch), int(rows) * int(cols), int(bool(relshift))
-        parts, n = _amax_of(x) if prec == 3 else (None, 0)       # max|x| partials left by the producer of the whole tensor
-        if parts is not None:
-            it.amax, it.namax = parts.data_ptr(), n
-            keep.append(parts)
-        nbytes = lib.vilco_pack_item_bytes(C.byref(it), prec)
-        buf = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
-        it.planes, it.planes_bytes = buf.data_ptr(), nbytes
-        bufs.append(buf)
-    _lib.check(lib.vilco_pack_many(arr, len(items), prec, _stream()))
+    bufs = [_pack_item(it, x, rows, cols, prec, nbatch, relshift) for it, (x, rows, cols) in zip(arr, items)]
+    _lib.check(_lib.load().vilco_pack_many(arr, len(items), prec, _stream()))
     return bufs
 
 
@@ -623,20 +672,12 @@ def pack_group(xs, rows, cols, precision=None):
     carries its planes (a cache hit must stay a hit), when the tensors repeat, or VILCO_PACK_GROUP=0."""
     prec = _precision if precision is None else int(precision)
     n = len(xs)
-    fresh = True
-    for x in xs:
-        hit = getattr(x, "_vilco_planes", None) if _pack_cache else None
-        if hit is not None and hit[1] == (int(rows), int(cols), prec, x._version):
-            fresh = False
+    fresh = all(_planes_of(x, "nat", (rows, cols), prec, any_stream=True) is None for x in xs)
     if (not pack_group_enabled or not (2 <= n <= 4) or not fresh or len({x.data_ptr() for x in xs}) != n
             or any(not x.is_contiguous() for x in xs)):
         return [pack(x, rows, cols, precision) for x in xs]
     bufs = pack_many([(x, rows, cols) for x in xs], precision=prec)
-    if _pack_cache:
-        mark = _cache_mark()
-        for x, buf in zip(xs, bufs):
-            x._vilco_planes = (buf, (int(rows), int(cols), prec, x._version), mark)
-    return bufs
+    return [_remember_planes(x, "nat", (rows, cols), prec, buf) for x, buf in zip(xs, bufs)]
 
 
 # packed operands are shared between forward, dX and dW (env VILCO_PACK_REUSE=0: every GEMM packs its own operands)
@@ -788,7 +829,6 @@ def bias_add(x, b):
 
 class _Linear(torch.autograd.Function):
     """y = act(x W^T + b) * rowmask.  x [..., K] token-major, W [N, K] (conv1x1 / nn.Linear weight)."""
-    last_amax = (None, 0)
 
     @staticmethod
     def forward(ctx, x, w, b, act, lens, T, drop_p=0.0, drop_site="dropout", bwd_precision=None):
@@ -810,7 +850,7 @@ class _Linear(torch.autograd.Function):
         ctx.drop = _new_drop(drop_site, drop_p, y.shape)      # nn.Dropout after the layer, fused into the epilogue
         gemm(x, w, y, M, N, K, 1, 1, K, K, N, bias=b, preact=pre, act=act, row_len=lens,
              rowT=T or 0, a_planes=px, b_planes=pw, drop=ctx.drop, want_amax=True)
-        _Linear.last_amax = _amax_of(y)
+        _leave(_Linear, 0, amax=_amax_of(y))             # max|y| partials left by the GEMM epilogue
         ctx.act, ctx.T = act, T
         ctx.has_bias = b is not None
         ctx.save_for_backward(x, w, pre if act == ACT_GELU else (y if act == ACT_RELU else None), lens, px, pw, b)
@@ -867,7 +907,6 @@ class _LinearGroup(torch.autograd.Function):
     """(y_i = x_i W_i^T + b_i) for n independent plain Linear layers of ONE shape -- an attention block's q / k / v projections
     (MQ/libs/modeling/blocks.py:332-344) -- with the n forward products and the n dX products each as one grouped launch
     (vilco_gemm_group).  Per layer it is _Linear without activation / mask / dropout: same packs, same kernels, same sums."""
-    last_amax = []
 
     @staticmethod
     def forward(ctx, n, *args):
@@ -881,7 +920,8 @@ class _LinearGroup(torch.autograd.Function):
         gemm_group([((x, w, y, M, N, K, 1, 1, K, K, N), dict(bias=b, a_planes=px, b_planes=pw, want_amax=True))
                     for x, w, b, y, px, pw in zip(xs, ws, bs, ys, pxs, pws)])
         ctx.n, ctx.prec = n, _precision
-        _LinearGroup.last_amax = [_amax_of(y) for y in ys]       # (attributes set here do not survive apply(): re-tagged by the caller)
+        for i, y in enumerate(ys):
+            _leave(_LinearGroup, i, amax=_amax_of(y))            # max|y| partials left by the GEMM epilogue
         ctx.save_for_backward(*xs, *ws, *bs, *pxs, *pws)
         return tuple(ys)
 
@@ -928,13 +968,7 @@ def linear_group(xs, ws, bs):
             and all(x.shape == xs[0].shape and w.shape == ws[0].shape for x, w in zip(xs, ws)))
     if not same:
         return [linear(x, w, b) for x, w, b in zip(xs, ws, bs)]
-    _LinearGroup.last_amax = []
-    ys = _LinearGroup.apply(n, *xs, *ws, *bs)
-    for y, am in zip(ys, _LinearGroup.last_amax):
-        if am[0] is not None:                       # max|y| partials left by the GEMM epilogue
-            _tag_amax(y, *am)
-    _LinearGroup.last_amax = []
-    return list(ys)
+    return list(_apply(_LinearGroup, n, *xs, *ws, *bs))
 
 
 def linear(x, w, b=None, act=ACT_NONE, lens=None, T=None, drop_p=0.0, drop_site="dropout", bwd_precision=None):
@@ -942,13 +976,8 @@ def linear(x, w, b=None, act=ACT_NONE, lens=None, T=None, drop_p=0.0, drop_site=
     With a ReLU (output saved as the activation witness) the dropout stays a separate op.
     bwd_precision: operand format of this layer's two backward products when not the ambient one (2 = bf16 x3)."""
     if drop_p > 0.0 and act == ACT_RELU:
-        return dropout(_Linear.apply(x, w, b, act, lens, T, 0.0, drop_site, bwd_precision), drop_p, True, drop_site)
-    _Linear.last_amax = (None, 0)
-    y = _Linear.apply(x, w, b, act, lens, T, float(drop_p), drop_site, bwd_precision)
-    if _Linear.last_amax[0] is not None:            # max|y| partials left by the GEMM epilogue
-        _tag_amax(y, *_Linear.last_amax)
-    _Linear.last_amax = (None, 0)
-    return y
+        return dropout(_apply(_Linear, x, w, b, act, lens, T, 0.0, drop_site, bwd_precision), drop_p, True, drop_site)
+    return _apply(_Linear, x, w, b, act, lens, T, float(drop_p), drop_site, bwd_precision)
 
 
 class _LinearKN(torch.autograd.Function):
@@ -1097,9 +1126,6 @@ def conv3(x, w, b=None, lens=None, row_mask=None):
 
 # ---------------------------------------------------------------------------------------- LayerNorm
 class _LayerNorm(torch.autograd.Function):
-    last_amax = (None, 0)
-    last_planes = None
-
     @staticmethod
     def forward(ctx, x, gamma, beta, eps, relu, planes=None, row_mask=None, skip=False):
         _chk(x, gamma, beta, row_mask)
@@ -1129,8 +1155,7 @@ class _LayerNorm(torch.autograd.Function):
         _lib.check(lib.vilco_layernorm_fwd(C.byref(d), _stream()))
         ctx.relu = bool(relu)
         ctx.save_for_backward(x, gamma, mean, rstd, y if relu else None)
-        _LayerNorm.last_amax = (parts, n.value)          # picked up by `layernorm` (attributes set here do not survive apply)
-        _LayerNorm.last_planes = (buf, seq, _cache_mark()) if buf is not None else None
+        _leave(_LayerNorm, 0, amax=(parts, n.value), planes=buf, layout="seq" if seq else "nat")
         # skip: x is returned as a second output (autograd makes it a view of x).  A block that opens a residual branch with
         # this LayerNorm takes its skip connection from THAT tensor: the gradient over the skip then arrives here, and the
         # backward kernel adds it to dx itself instead of autograd summing the two with a launch of its own (55 per P step).
@@ -1181,24 +1206,12 @@ def layernorm(x, gamma, beta, eps=1e-5, relu=False, planes=None, row_mask=None, 
     planes: "nat" when y feeds a Linear, "seq" when it feeds a k=3 conv -- the kernel then writes y's operand planes as well
     (vilco_ln_fwd_desc.planes) and the consumer's `pack` / `pack_tap` finds them on the tensor.
     row_mask (relu only): a contiguous 0 / 1 float mask over the token rows, repeated over the batch -- y[b, t] *= row_mask[t]."""
-    _LayerNorm.last_planes = None
-    y = _LayerNorm.apply(x, gamma, beta, float(eps), bool(relu), planes, row_mask, bool(skip and fold_skip_grads and x.requires_grad))
+    y = _apply(_LayerNorm, x, gamma, beta, float(eps), bool(relu), planes, row_mask, bool(skip and fold_skip_grads and x.requires_grad))
     xs = x
     if isinstance(y, tuple):
         y, xs = y
     if relu and relu_log is not None:
         relu_log.append((site, y.detach() > 0, y.detach().clone()) if relu_log_values else (site, y.detach() > 0))
-    parts, n = _LayerNorm.last_amax
-    _LayerNorm.last_amax = (None, 0)
-    made, _LayerNorm.last_planes = _LayerNorm.last_planes, None
-    if made is not None:
-        buf, seq, mark = made
-        Cn = y.shape[-1]
-        if seq:
-            y._vilco_tap_planes = (buf, ("tap", int(y.shape[0]), int(y.shape[1]), int(Cn), 3, y._version), mark)
-        else:
-            y._vilco_planes = (buf, (int(y.numel() // Cn), int(Cn), 3, y._version), mark)
-    y = _tag_amax(y, parts, n) if parts is not None else y
     return (y, xs) if skip else y
 
 
@@ -1492,7 +1505,9 @@ def _attn_amax_in(q, k, v, do=None):
     return (a, keep) if keep else None
 
 
-def _flash_fwd(q, k, v, bias, kv_len, H, scale, mode, drop=(0.0, 0), window=0):
+def _flash_fwd(q, k, v, bias, kv_len, H, scale, mode, drop=(0.0, 0), window=0, hints_to=None, hint_amax=True):
+    """-> (o, lse).  hints_to: the Function this call is the forward of -- its output 0 is o, and carries what the kernel
+    leaves for the output projection: o's operand planes, and (hint_amax) its max|o| partials."""
     lib = _lib.load()
     B, Tq, Cn = q.shape
     Tk = k.shape[1]
@@ -1514,19 +1529,9 @@ def _flash_fwd(q, k, v, bias, kv_len, H, scale, mode, drop=(0.0, 0), window=0):
                       workspace=ws.data_ptr(), workspace_bytes=nws, o_amax=_p(am), o_planes=_p(planes),
                       o_planes_bytes=planes.numel() if planes is not None else 0)
     _lib.check(lib.vilco_attn_fwd(C.byref(d), _stream()))
-    if na:
-        _FlashAttention.last_amax = (am, na)
-    _FlashAttention.last_planes = (planes, _cache_mark()) if planes is not None else None
+    if hints_to is not None:
+        _leave(hints_to, 0, amax=(am, na) if hint_amax else None, planes=planes)
     return o, lse
-
-
-def _attach_attn_planes(o):
-    """hang the planes the forward kernel wrote on its output (attributes set inside apply do not survive it)"""
-    made, _FlashAttention.last_planes = _FlashAttention.last_planes, None
-    if made is not None:
-        Cn = o.shape[-1]
-        o._vilco_planes = (made[0], (int(o.numel() // Cn), int(Cn), 3, o._version), made[1])
-    return o
 
 
 # XLNet backward: dS as operand planes of the unshifted view straight from the dQ kernel (vilco_attn_desc.ds_planes) instead of
@@ -1602,14 +1607,12 @@ def _flash_bwd(q, k, v, bias, kv_len, o, lse, do, H, scale, mode, want_dbias, dr
 class _FlashAttention(torch.autograd.Function):
     """fused attention (vilco_attn_fwd / vilco_attn_bwd): scores never reach HBM; backward recomputes P
     from (q, k, lse)."""
-    last_amax = None        # (partials, count) the forward kernel left for the pack of its output, or None
-    last_planes = None      # (operand planes of the output written by the forward kernel, cache mark), or None
 
     @staticmethod
     def forward(ctx, q, k, v, kv_len, H, scale, mode, drop_p=0.0, window=0):
         _chk(q, k, v)
         ctx.drop = _new_drop("attn_prob", drop_p, (q.shape[0], H, q.shape[1], k.shape[1]))
-        o, lse = _flash_fwd(q, k, v, None, kv_len, H, scale, mode, ctx.drop, window)
+        o, lse = _flash_fwd(q, k, v, None, kv_len, H, scale, mode, ctx.drop, window, hints_to=_FlashAttention)
         ctx.H, ctx.scale, ctx.mode, ctx.window = H, scale, mode, window
         ctx.save_for_backward(q, k, v, kv_len, o, lse)
         return o
@@ -1628,13 +1631,7 @@ def attention(q, k, v, kv_len, n_head, scale=None, mode=MASK_KEYS, drop_p=0.0, w
     if scale is None:
         scale = 1.0 / math.sqrt(q.shape[-1] // n_head)
     if use_flash and flash_supported(q.shape[-1] // n_head):
-        _FlashAttention.last_amax = None
-        _FlashAttention.last_planes = None
-        o = _FlashAttention.apply(q, k, v, kv_len, int(n_head), float(scale), int(mode), float(drop_p), int(window))
-        if _FlashAttention.last_amax is not None:        # left by the fused kernel for the pack of the output projection
-            _tag_amax(o, *_FlashAttention.last_amax)
-            _FlashAttention.last_amax = None
-        return _attach_attn_planes(o)
+        return _apply(_FlashAttention, q, k, v, kv_len, int(n_head), float(scale), int(mode), float(drop_p), int(window))
     if mode == MASK_LOCAL:
         raise NotImplementedError("local-window attention needs the fused kernels (head dim <= 160, multiple of 4)")
     if drop_p > 0.0:
@@ -1726,7 +1723,9 @@ class _FlashRelAttention(torch.autograd.Function):
                  sC=(H * T * 2 * T, T * 2 * T), band=1, bandT=T)      # only the band p in [T-i, 2T-i) is ever read
         ctx.drop = _new_drop("attn_prob", drop_p, (B, H, T, T))
         # the flash kernel reads the unshifted scores in place (mask mode 3): no [T,T] bias tensor, no shift pass
-        o, lse = _flash_fwd(qw, k, v, bd, kv_len, H, scale, MASK_XLNET_REL, ctx.drop)
+        # (the planes only: this output has never carried its max|o| partials, and where the kernel writes no planes they
+        # would send the output projection's pack through another library entry)
+        o, lse = _flash_fwd(qw, k, v, bd, kv_len, H, scale, MASK_XLNET_REL, ctx.drop, hints_to=_FlashRelAttention, hint_amax=False)
         ctx.H, ctx.scale = H, scale
         ctx.save_for_backward(qw, qr, k, v, kr, kv_len, bd, o, lse)
         return o
@@ -1778,8 +1777,7 @@ class _FlashRelAttention(torch.autograd.Function):
 def rel_attention(qw, qr, k, v, kr, kv_len, n_head, scale, drop_p=0.0):
     """kr [2T, C] or [B, 2T, C]; drop_p: dropout on the attention probabilities (training only)."""
     if use_flash and flash_supported(qw.shape[-1] // n_head):
-        _FlashAttention.last_planes = None
-        return _attach_attn_planes(_FlashRelAttention.apply(qw, qr, k, v, kr, kv_len, int(n_head), float(scale), float(drop_p)))
+        return _apply(_FlashRelAttention, qw, qr, k, v, kr, kv_len, int(n_head), float(scale), float(drop_p))
     if drop_p > 0.0 or kr.dim() == 3:
         raise NotImplementedError("XLNet dropout needs the fused attention kernels (head dim <= 160, multiple of 4)")
     return _RelAttention.apply(qw, qr, k, v, kr, kv_len, int(n_head), float(scale))
@@ -1801,7 +1799,6 @@ def _unit_bound(device):
 class _ChannelAttn(torch.autograd.Function):
     """ChannelAttention core (blocks.py:426-434) on a fused qkv [B,T,3C]:
     A_h = softmax_rows(scale * k_h^T v_h)  [hd,hd];  out_h[t,:] = q_h[t,:] A_h^T."""
-    last_amax = (None, 0)
 
     @staticmethod
     def forward(ctx, qkv, H, scale, bwd_precision=None):
@@ -1821,7 +1818,7 @@ class _ChannelAttn(torch.autograd.Function):
         out = torch.empty(B, T, Cn, dtype=torch.float32, device=qkv.device)
         gemm(qkv, A, out, T, hd, hd, 1, 1, C3, hd, Cn, batch=(B, H), sA=sQ, sB=(H * hd * hd, hd * hd),
              sC=(T * Cn, hd), want_amax=True, a_amax=qa, b_amax=one)             # q A^T (its output goes straight into proj)
-        _ChannelAttn.last_amax = _amax_of(out)          # picked up by `channel_attention` (attributes set here do not survive apply)
+        _leave(_ChannelAttn, 0, amax=_amax_of(out))
         ctx.H, ctx.scale = H, scale
         ctx.save_for_backward(qkv, A)
         return out
@@ -1857,11 +1854,7 @@ class _ChannelAttn(torch.autograd.Function):
 
 
 def channel_attention(qkv, n_head, scale, bwd_precision=None):
-    _ChannelAttn.last_amax = (None, 0)
-    out = _ChannelAttn.apply(qkv, int(n_head), float(scale), bwd_precision)
-    parts, n = _ChannelAttn.last_amax
-    _ChannelAttn.last_amax = (None, 0)
-    return _tag_amax(out, parts, n) if parts is not None else out
+    return _apply(_ChannelAttn, qkv, int(n_head), float(scale), bwd_precision)
 
 
 # ---------------------------------------------------------------------------------------- labels + losses
@@ -2356,7 +2349,6 @@ def _ptr3(ts):
 
 
 class _QkvPre(torch.autograd.Function):
-    last_amax = (None, 0)
     """h = LN1(x); y_j = LN_j(dwconv3_stride(h; w_j) * mask), j = q, k, v   (blocks.py:561-563, 363-369) in one launch
     (vilco_qkv_pre_fwd); backward = vilco_qkv_pre_bwd (conv outputs recomputed from h) + LN1's ordinary backward."""
 
@@ -2381,7 +2373,9 @@ class _QkvPre(torch.autograd.Function):
                                          stats1[1].data_ptr(), _ptr3(means), _ptr3(rstds),
                                          _ptr3([parts[0], parts[1], parts[2]]) if parts is not None else None, B, T, Cn,
                                          int(stride), float(eps1), float(eps), _stream()))
-        _QkvPre.last_amax = (parts, npart)
+        if parts is not None:
+            for j in range(3):
+                _leave(_QkvPre, j, amax=(parts[j], npart))
         ctx.stride, ctx.eps1, ctx.want_h = int(stride), float(eps1), bool(want_h)
         ctx.save_for_backward(x, g1, b1, wq, wk, wv, gq, gk, gv, lens, stats1, stats, h)
         outs = (ys[0], ys[1], ys[2], h) if want_h else (ys[0], ys[1], ys[2])
@@ -2438,16 +2432,9 @@ def qkv_pre(x, ln1, convs, norms, lens, stride, want_h, skip=False):
     (g1, b1, eps1), (wq, wk, wv), ((gq, bq), (gk, bk), (gv, bv), eps) = ln1, convs, norms
     x = x.contiguous()
     fold = bool(skip and fold_skip_grads and x.requires_grad)
-    outs = _QkvPre.apply(x, g1, b1, wq, wk, wv, gq, bq, gk, bk, gv, bv, lens, int(stride), float(eps1),
-                         float(eps), bool(want_h), fold)
-    if skip and not fold:
-        outs = tuple(outs) + (x,)
-    parts, n = _QkvPre.last_amax
-    _QkvPre.last_amax = (None, 0)
-    if parts is not None:
-        for j in range(3):
-            _tag_amax(outs[j], parts[j], n)
-    return outs
+    outs = _apply(_QkvPre, x, g1, b1, wq, wk, wv, gq, bq, gk, bk, gv, bv, lens, int(stride), float(eps1),
+                  float(eps), bool(want_h), fold)
+    return tuple(outs) + (x,) if skip and not fold else outs
 
 
 # ---------------------------------------------------------------------------------------- narration SSL (csrc/ssl.hip)
