@@ -79,7 +79,10 @@ __global__ __launch_bounds__(LN_THREADS) void ln_fwd_kernel(
         s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
       }
     }
-    const float mu = wave_sum(s) * invC;
+    // a division, not sum * (1 / C): whenever the fp32 sum of a constant row is exact (C * v representable, as for v = 3) the
+    // mean is v itself, xhat 0 and y == beta.  fl(1 / C) is off by up to half an ulp, which at C = 1792 made the mean of such a
+    // row 3.0000002 and rstd = 1 / sqrt(eps) turned that into 3e-5 of y.  (var keeps * invC: var = 0 is exact either way.)
+    const float mu = wave_sum(s) / (float)C;
     float q = 0.f;
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
@@ -419,6 +422,9 @@ extern "C" int vilco_layernorm_bwd(const vilco_ln_bwd_desc* d, void* stream) {
   if ((dgamma == nullptr) != (dbeta == nullptr)) return VILCO_ERR_BADARG;
   if (rows == 0) return VILCO_OK;
   if ((C % 4) != 0 || C > 4096) return VILCO_ERR_UNSUPPORTED;
+  if (!vilco_aligned(dy, 16) || !vilco_aligned(x, 16) || !vilco_aligned(dx, 16) || !vilco_aligned(dres, 16) ||
+      !vilco_aligned(gamma, 16) || (relu && !vilco_aligned(y, 16)))
+    return VILCO_ERR_BADARG;          // the rows are read and written as float4, like the forward's
   if (!workspace || workspace_bytes < vilco_layernorm_bwd_workspace(rows, C)) return VILCO_ERR_WORKSPACE;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const int nv = (C + 255) / 256;
