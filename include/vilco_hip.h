@@ -952,6 +952,56 @@ int vilco_ssl_nce_bwd(const float* gloss, const float* mask, const float* xn, co
 int vilco_ssl_ring_update(const float* rows, const float* mask, int32_t B, int32_t D, float* bank, int32_t M,
                           int32_t* ring, void* stream);
 
+/* ------------------------------------------------------------------------------------------ */
+/* L2P prompt pool (MQ/libs/cl_methods/prompt.py:47-117): match, batch vote and prepend (csrc/prompt.hip).          */
+/*   row key   xk[b] = mean_l x[b][l] | max_l | max + 2 mean | cls[b]   (key_mode; padding rows count)                 */
+/*   normalise xn[b] = xk[b] rsqrt(max(sum xk^2, 1e-12)), pn[p] likewise from key[p];  sim[b][p] = <xn[b], pn[p]>      */
+/*   select    idx_in given: idx = idx_in (entries outside [0, P) raise the status word and are clamped).             */
+/*             idx_in NULL: per row the k prompts of largest sim by COUNTING RANK (before = larger sim, or equal sim   */
+/*             and smaller index; NaN is out of contract); vote != 0: the k ids with the most picks over all B k       */
+/*             picks, again by counting rank (larger count, equal counts by smaller id), the same list for every row.  */
+/*   outputs   prompted[b] = prompt[idx[b][0]], ..., prompt[idx[b][k-1]] (len rows each), then x[b]  -- bit copies;    */
+/*             reduce_sim = (sum_b (sum_j sim[b][idx[b][j]])) / B, j then b in order;  selkey[b][j] = pn[idx[b][j]].    */
+/* fwd: two launches (select: one workgroup per row; gather-and-prepend: row copies, idx read from device memory).    */
+/* bwd: at most two launches.  g_prompted [B][k len + L][C], g_reduce_sim device float[1].  d_prompt[p] = the sum of  */
+/* g_prompted[b][j len .. (j+1) len) over the (b, j) with idx[b][j] == p in (b, j) order (exact zeros when none);      */
+/* d_key through reduce_sim and the normalisation; d_x = g_prompted[:, k len:] + the reduce_sim path through the row   */
+/* key (max: to the FIRST position attaining it; key_mode 3 has none).  Each of d_prompt / d_key / d_x may be NULL.    */
+/* No float atomics: the same bits on every call.  `workspace` (vilco_prompt_workspace bytes, 256-byte aligned) is     */
+/* written by fwd and read by bwd: keep it between the two.                                                            */
+/* BADARG before any device work: !(1 <= k <= P <= 64), len < 1, B < 1, L < 1, C < 1, key_mode outside 0..3, key_mode  */
+/* 3 without cls, null operands.                                                                                       */
+/* ------------------------------------------------------------------------------------------ */
+enum { VILCO_PROMPT_MEAN = 0, VILCO_PROMPT_MAX = 1, VILCO_PROMPT_MEAN_MAX = 2, VILCO_PROMPT_CLS = 3 };
+typedef struct vilco_prompt_desc {
+  const float* x;           /* [B][L][C] */
+  const float* prompt;      /* [P][len][C] */
+  const float* key;         /* [P][C] */
+  const float* cls;         /* [B][C], key_mode 3 only */
+  const int64_t* idx_in;    /* [B][k] or NULL: select on the device */
+  int32_t B, L, C, P, len, k;
+  int32_t key_mode;         /* VILCO_PROMPT_* */
+  int32_t vote;             /* batchwise_prompt; only read when idx_in is NULL */
+  /* outputs of fwd (inputs of bwd: idx, xn, pn) */
+  int64_t* idx;             /* [B][k] */
+  float* sim;               /* [B][P] */
+  float* pn;                /* [P][C] */
+  float* xn;                /* [B][C] */
+  float* selkey;            /* [B][k][C] */
+  float* prompted;          /* [B][k len + L][C] */
+  float* reduce_sim;        /* [1] */
+  void* workspace;
+  size_t workspace_bytes;
+} vilco_prompt_desc;
+size_t vilco_prompt_workspace(const vilco_prompt_desc* d);
+int vilco_prompt_fwd(const vilco_prompt_desc* d, void* stream);
+int vilco_prompt_bwd(const vilco_prompt_desc* d, const float* g_prompted, const float* g_reduce_sim, float* d_prompt,
+                     float* d_key, float* d_x, void* stream);
+/* The library's device status word: kernels that validate device-resident arguments (vilco_prompt_fwd: idx_in) OR a    */
+/* bit into it instead of faulting or making the host read.  _take synchronises the device, returns the word and clears */
+/* it (tests, end-of-epoch checks); bit 0 = a prompt index outside [0, P).                                               */
+int vilco_status_word_take(int32_t* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -129,6 +129,14 @@ class BicCorrectDesc(C.Structure):
                 ("ldx", i32), ("ldy", i32), ("n_layers", i32)]
 
 
+class PromptDesc(C.Structure):
+    _cname_ = "vilco_prompt_desc"
+    _fields_ = [("x", c_fp), ("prompt", c_fp), ("key", c_fp), ("cls", c_fp), ("idx_in", c_fp),
+                ("B", i32), ("L", i32), ("C", i32), ("P", i32), ("len", i32), ("k", i32), ("key_mode", i32), ("vote", i32),
+                ("idx", c_fp), ("sim", c_fp), ("pn", c_fp), ("xn", c_fp), ("selkey", c_fp), ("prompted", c_fp),
+                ("reduce_sim", c_fp), ("workspace", c_fp), ("workspace_bytes", sz)]
+
+
 # name -> (restype, argtypes); must list every symbol include/vilco_hip.h declares
 SIGNATURES = {
     "vilco_status_str": (C.c_char_p, [C.c_int]),
@@ -254,6 +262,10 @@ SIGNATURES = {
     "vilco_ssl_nce_fwd": (C.c_int, [c_fp, c_fp, c_fp, i32, i32, c_fp, i32, c_fp, f32, c_fp, c_fp, c_fp, c_fp, c_fp, sz, c_fp]),
     "vilco_ssl_nce_bwd": (C.c_int, [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, i32, i32, i32, f32, c_fp, c_fp, c_fp, sz, c_fp]),
     "vilco_ssl_ring_update": (C.c_int, [c_fp, c_fp, i32, i32, c_fp, i32, c_fp, c_fp]),
+    "vilco_prompt_workspace": (sz, [C.POINTER(PromptDesc)]),
+    "vilco_prompt_fwd": (C.c_int, [C.POINTER(PromptDesc), c_fp]),
+    "vilco_prompt_bwd": (C.c_int, [C.POINTER(PromptDesc), c_fp, c_fp, c_fp, c_fp, c_fp, c_fp]),
+    "vilco_status_word_take": (C.c_int, [C.POINTER(i32)]),
 }
 
 _lib = None

@@ -101,6 +101,7 @@ __device__ __forceinline__ uint32_t vilco_step_seed(uint32_t seed, const uint32_
   return seed + __builtin_nontemporal_load(word) * 0x9E3779B1u;
 }
 const uint32_t* vilco_seed_word_dev();     // sync.hip: device address of the step word
+int32_t* vilco_status_word_dev();          // status.hip: device address of the status word (null: no device)
 
 static inline uint32_t vilco_drop_threshold_host(float p) {     // host side: the kernels receive the threshold
   if (p <= 0.f) return 0u;

@@ -20,6 +20,29 @@ extern "C" size_t vilco_abi_sizeof(const char* struct_name) {
   ABI_SIZE(vilco_gemm_desc) ABI_SIZE(vilco_pack_item) ABI_SIZE(vilco_attn_amax_in) ABI_SIZE(vilco_loss_desc)
   ABI_SIZE(vilco_ln_fwd_desc) ABI_SIZE(vilco_ln_bwd_desc) ABI_SIZE(vilco_attn_desc) ABI_SIZE(vilco_scale_add_bwd_desc)
   ABI_SIZE(vilco_act_bwd_desc) ABI_SIZE(vilco_optim_desc) ABI_SIZE(vilco_distill_desc) ABI_SIZE(vilco_bic_correct_desc)
+  ABI_SIZE(vilco_prompt_desc)
 #undef ABI_SIZE
   return 0;
+}
+
+// The device status word: kernels that validate device-resident arguments OR a bit into it (an integer atomic) instead of
+// faulting or making the host read; vilco_status_word_take reads and clears it.
+__device__ int32_t vilco_status_word_storage[16];      // word 0; its own 64-byte line
+
+int32_t* vilco_status_word_dev() {
+  static int32_t* p = [] {
+    void* q = nullptr;
+    if (hipGetSymbolAddress(&q, HIP_SYMBOL(vilco_status_word_storage)) != hipSuccess) q = nullptr;
+    return reinterpret_cast<int32_t*>(q);
+  }();
+  return p;
+}
+
+// current value, then cleared (synchronises the device: tests / end-of-epoch checks only)
+extern "C" int vilco_status_word_take(int32_t* out) {
+  if (!out) return VILCO_ERR_BADARG;
+  if (hipDeviceSynchronize() != hipSuccess) return VILCO_ERR_LAUNCH;
+  if (hipMemcpyFromSymbol(out, HIP_SYMBOL(vilco_status_word_storage), sizeof(int32_t)) != hipSuccess) return VILCO_ERR_LAUNCH;
+  const int32_t zero = 0;
+  return hipMemcpyToSymbol(HIP_SYMBOL(vilco_status_word_storage), &zero, sizeof(int32_t)) == hipSuccess ? VILCO_OK : VILCO_ERR_LAUNCH;
 }

@@ -639,7 +639,7 @@ class PtTransformer(nn.Module):
 
     def capturable(self, inp, task_id=-1, prev_out_cls_logits=None):
         """can forward_prepared(inp, None, task_id) + backward run without touching the host?  (the fused label / loss
-        kernels, a fixed prompt window, narration SSL only on its fused path -- the unfused one reads the mask sum and
+        kernels, a prompt pool on ops.prompt_pool (or, with VILCO_FUSED_PROMPT=0, a fixed window), narration SSL only on its fused path -- the unfused one reads the mask sum and
         keeps the ring pointer on the host).  Distillation: an iCaRL step with n_known > 0 is capturable when its targets
         are resident on the device and travel in `inp.dist_tgt` (distill_target: the whole term is then ops.cl_distill
         over a buffer a replay refreshes); NumPy targets are uploaded per step and a batch without a cached clip has no
@@ -667,7 +667,9 @@ class PtTransformer(nn.Module):
         elif prev_out_cls_logits:
             return False
         if hasattr(self, 'prompt') and not (0 <= task_id and (task_id + 1) * self.prompt.top_k <= self.prompt.pool_size):
-            return False
+            # a task past the pool selects its prompts by similarity: only ops.prompt_pool does that without reading the host
+            if not (ops.fused_prompt and task_id >= 0):
+                return False
         return True
 
     def forward_prepared(self, inp, video_list=None, task_id=-1, ensemble=False, is_training=True,
@@ -690,10 +692,11 @@ class PtTransformer(nn.Module):
             if is_training:
                 start, end = task_id * self.prompt.top_k, (task_id + 1) * self.prompt.top_k
                 if end <= self.prompt.pool_size:
-                    prompt_mask = torch.arange(start, end, device=text_tm.device).unsqueeze(0).expand(text_tm.shape[0], -1)
+                    # one device tensor per (window, B), kept: nothing is built per step and a captured step addresses it
+                    prompt_mask = ops.prompt_window(start, self.prompt.top_k, text_tm.shape[0], text_tm.device)
             res = self.prompt(text_tm, prompt_mask=prompt_mask, cls_features=None)
             self.total_prompt_len = res['total_prompt_len']
-            text_tm = res['prompted_embedding'].contiguous()
+            text_tm = res['prompted_embedding']                     # written contiguous by the op (and by torch.cat)
             reduce_sim = res['reduce_sim']
 
         # training with fixed loss weights: labels + losses are ONE fused kernel pair (ops.mq_loss) that also applies the

@@ -59,7 +59,8 @@ def arithmetic_key():
             #  the remaining switches that change which kernels / roundings a step records, and the library's own
             # configuration generation (vilco_gemm_force / vilco_gemm_set_skinny)
             bool(fold_skip_grads), bool(xl_ds_planes), bool(xl_scores_kernel), bool(linear_group_enabled), bool(use_flash),
-            bool(_reuse_packs), bool(_weight_cache), str(range_check), int(_lib.load().vilco_gemm_config_gen()), bool(pack_group_enabled), bool(conv_dz_planes), bool(ln_bwd_amax))
+            bool(_reuse_packs), bool(_weight_cache), str(range_check), int(_lib.load().vilco_gemm_config_gen()), bool(pack_group_enabled), bool(conv_dz_planes), bool(ln_bwd_amax),
+            bool(fused_prompt))
 
 
 def get_precision():
@@ -2149,6 +2150,124 @@ def bic_correct(logits, splits, layers, inplace=False):
             params.append(p)
     tab = _bic_table(ends, params, logits.device)
     return _BicCorrect.apply(logits, tab, bool(inplace), *params)
+
+
+# ---------------------------------------------------------------------------------------- L2P prompt pool
+# VILCO_FUSED_PROMPT=0: cl_methods.Prompt keeps its tensor-op body on the device too (A/B runs).  Part of arithmetic_key():
+# a captured step replays the path it recorded.
+fused_prompt = os.environ.get("VILCO_FUSED_PROMPT", "1") != "0"
+PROMPT_KEY_MODES = {'mean': 0, 'max': 1, 'mean_max': 2, 'cls': 3}
+_prompt_windows = {}
+
+
+def prompt_window(start, k, B, device):
+    """the fixed per-task window [start, start + k) for every row of the batch as a device int64 [B, k], made once per
+    (start, k, B, device) and kept: a captured step addresses it"""
+    key = (int(start), int(k), int(B), str(device))
+    w = _prompt_windows.get(key)
+    if w is None:
+        w = _prompt_windows[key] = torch.arange(int(start), int(start) + int(k), device=device).unsqueeze(0).repeat(int(B), 1)
+    return w
+
+
+def status_word_take():
+    """the library's device status word, read and cleared (synchronises the device).  Bit 0: a prompt index outside the pool."""
+    v = C.c_int32(0)
+    _lib.check(_lib.load().vilco_status_word_take(C.byref(v)))
+    return v.value
+
+
+def _prompt_desc(x, prompt, key, idx_in, cls, cfg):
+    k, mode, vote = cfg
+    d = _lib.PromptDesc()
+    d.x, d.prompt, d.key, d.cls, d.idx_in = x.data_ptr(), prompt.data_ptr(), key.data_ptr(), _p(cls), _p(idx_in)
+    d.B, d.L, d.C = x.shape
+    d.P, d.len = prompt.shape[0], prompt.shape[1]
+    d.k, d.key_mode, d.vote = int(k), int(mode), int(bool(vote))
+    return d
+
+
+class _PromptPool(torch.autograd.Function):
+    """vilco_prompt_fwd / _bwd: two launches forward, at most two backward, no host read, no data-dependent allocation"""
+
+    @staticmethod
+    def forward(ctx, x, prompt, key, idx_in, cls, cfg):
+        _chk(x, prompt, key, cls)
+        lib = _lib.load()
+        dev, (B, L, Cn), k = x.device, x.shape, int(cfg[0])
+        P, length = prompt.shape[0], prompt.shape[1]
+        d = _prompt_desc(x, prompt, key, idx_in, cls, cfg)
+        f32 = dict(dtype=torch.float32, device=dev)
+        kk, ll = max(k, 0), max(length, 0)               # a bad k / len is the launcher's to refuse
+        idx = torch.empty(B, kk, dtype=torch.int64, device=dev)
+        sim, pn, xn = torch.empty(B, P, **f32), torch.empty(P, Cn, **f32), torch.empty(B, Cn, **f32)
+        selkey, prompted = torch.empty(B, kk, Cn, **f32), torch.empty(B, kk * ll + L, Cn, **f32)
+        rs = torch.empty((), **f32)
+        nws = lib.vilco_prompt_workspace(C.byref(d))
+        ws = torch.empty(max(int(nws), 4), dtype=torch.uint8, device=dev)      # written forward, read backward: kept on ctx
+        d.idx, d.sim, d.pn, d.xn, d.selkey = idx.data_ptr(), sim.data_ptr(), pn.data_ptr(), xn.data_ptr(), selkey.data_ptr()
+        d.prompted, d.reduce_sim, d.workspace, d.workspace_bytes = prompted.data_ptr(), rs.data_ptr(), ws.data_ptr(), nws
+        _lib.check(lib.vilco_prompt_fwd(C.byref(d), _stream()))
+        ctx.desc, ctx.keep = d, (x, prompt, key, idx_in, cls, ws)      # the backward reads these through the descriptor
+        ctx.save_for_backward(idx, pn, xn)
+        ctx.mark_non_differentiable(idx, sim, pn, xn, selkey)
+        return prompted, rs, idx, sim, pn, xn, selkey
+
+    @staticmethod
+    def backward(ctx, g_prompted, g_rs, *unused):
+        idx, pn, xn = ctx.saved_tensors
+        x, prompt, key = ctx.keep[:3]
+        d = ctx.desc
+        d.idx, d.pn, d.xn = idx.data_ptr(), pn.data_ptr(), xn.data_ptr()
+        dev = x.device
+        g_prompted = (torch.zeros(x.shape[0], d.k * d.len + d.L, d.C, dtype=torch.float32, device=dev) if g_prompted is None
+                      else g_prompted.contiguous().float())
+        g_rs = torch.zeros((), dtype=torch.float32, device=dev) if g_rs is None else g_rs.contiguous().float()
+        want_x, want_p, want_k = ctx.needs_input_grad[:3]
+        dx = torch.empty_like(x) if want_x else None
+        dp = torch.empty_like(prompt) if want_p else None
+        dk = torch.empty_like(key) if want_k else None
+        _lib.check(_lib.load().vilco_prompt_bwd(C.byref(d), g_prompted.data_ptr(), g_rs.data_ptr(), _p(dp), _p(dk), _p(dx),
+                                                _stream()))
+        return dx, dp, dk, None, None, None
+
+
+def prompt_pool(x, prompt, key, idx=None, top_k=None, batchwise=False, embedding_key='mean', cls_features=None):
+    """The L2P prompt pool as one operator (include/vilco_hip.h: vilco_prompt_desc; reference MQ/libs/cl_methods/prompt.py:47-117).
+    x [B, L, C], prompt [P, len, C], key [P, C]: fp32 on the device.  idx [B, k] int64 on the device = the fixed window; None:
+    the k = top_k prompts of largest cosine similarity are chosen on the device by counting rank (larger similarity first,
+    equal similarities by smaller index), with `batchwise` the k most-picked ids of the batch (larger count first, equal
+    counts by smaller id) for every row.  -> (prompted [B, k len + L, C], reduce_sim (0-dim), idx [B, k] int64, sim [B, P],
+    pn [P, C], xn [B, C], selected_key [B, k, C]).
+    Gradients reach prompt, key and x (each only if it requires one) from prompted and reduce_sim.  The other five outputs
+    are marked non-differentiable -- nothing in the project or the reference differentiates them -- and cls_features gets
+    no gradient.  An idx entry outside [0, P) sets bit 0 of the status word (status_word_take) and is clamped."""
+    for t in (x, prompt, key):
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise RuntimeError("vilco_amd ops run on the HIP device only (got a %s tensor); there is no CPU fallback"
+                               % (t.device if torch.is_tensor(t) else type(t).__name__))
+    if embedding_key not in PROMPT_KEY_MODES:
+        raise NotImplementedError("Not supported way of calculating embedding keys!")
+    if x.dim() != 3 or prompt.dim() != 3 or key.dim() != 2 or prompt.shape[2] != x.shape[2] or key.shape != (prompt.shape[0], x.shape[2]):
+        raise ValueError("prompt_pool: x [B, L, C], prompt [P, len, C], key [P, C]; got %s %s %s" %
+                         (tuple(x.shape), tuple(prompt.shape), tuple(key.shape)))
+    mode = PROMPT_KEY_MODES[embedding_key]
+    if mode == 3 and cls_features is None:
+        mode = 1                                             # the reference: the maximum stands in
+    cls = None
+    if mode == 3:
+        if cls_features.shape != (x.shape[0], x.shape[2]) or cls_features.device != x.device:
+            raise ValueError("prompt_pool: cls_features must be [B, C] on the device of x")
+        cls = cls_features.detach().contiguous()
+    if idx is not None:
+        if idx.dim() != 2 or idx.shape[0] != x.shape[0] or idx.dtype != torch.int64 or idx.device != x.device:
+            raise ValueError("prompt_pool: idx must be int64 [B, k] on the device of x")
+        idx, k = idx.contiguous(), idx.shape[1]
+    else:
+        if top_k is None:
+            raise ValueError("prompt_pool: top_k is needed when no idx is given")
+        k = int(top_k)
+    return _PromptPool.apply(x.contiguous(), prompt.contiguous(), key.contiguous(), idx, cls, (k, mode, bool(batchwise)))
 
 
 # ---------------------------------------------------------------------------------------- inference decode
