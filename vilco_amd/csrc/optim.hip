@@ -60,8 +60,10 @@ __global__ __launch_bounds__(OPT_THREADS) void clip_coef_kernel(const float* __r
 struct Hyper {
   float lr[8], wd[8];
   float beta1, beta2, eps;
+  float log_beta1, log_beta2;              // log(beta), taken in double on the host: 1 - beta^t = -expm1f(t log beta)
   float momentum;                          // SGD
-  const float* tstep;                      // [n] per-tensor step count (after this update), torch keeps it per param
+  const float* tstep;                      // [n] per-tensor step count (after this update), torch keeps it per param;
+                                           // SGD only asks whether it is <= 1 (the momentum buffer starts as the gradient)
   const float* lr_dev;                     // optional [ngroups] learning rates in device memory (override lr[]): a captured
                                            // step replays its kernel arguments, the schedule's value must come from memory
 };
@@ -91,8 +93,10 @@ __global__ __launch_bounds__(OPT_THREADS) void adamw_kernel(MultiArgs a, Hyper h
   const float lr = h.lr_dev ? h.lr_dev[gi] : h.lr[gi], wd = h.wd[gi];
   const float c = coef ? coef[1] : 1.f;
   const float stp = h.tstep[t];
-  const float step_size = lr / (1.f - powf(h.beta1, stp));      // bias corrections 1 - beta^step
-  const float rs2 = sqrtf(1.f - powf(h.beta2, stp));
+  // bias corrections 1 - beta^step: as 1.f - powf(beta, step) the subtraction cancels for small step counts (beta2 = 0.999:
+  // ~100 roundings at steps 2..5), and half of that reaches the update through the square root
+  const float step_size = lr / -expm1f(stp * h.log_beta1);
+  const float rs2 = sqrtf(-expm1f(stp * h.log_beta2));
   float mx = 0.f;
   for (long i = threadIdx.x; i < cnt; i += OPT_THREADS) {
     const float gr = g[i] * c;
@@ -137,6 +141,8 @@ __global__ __launch_bounds__(OPT_THREADS) void sgd_kernel(MultiArgs a, Hyper h, 
 
 // EWC / MAS penalty (MQ/libs/cl_methods/EWC.py:6-22, MAS.py:5-21) over a chunk table of (parameter, importance,
 // consolidated value) triples: partial[chunk] = sum F (opt - p)^2 ; grad += -2 lambda F (opt - p).
+// The added term is formed in double and rounded once (the kernels are bound by their five streams, not by arithmetic), so an
+// element's gradient carries one rounding per add and one for the term: independent of the order atomics arrive in.
 // ptrs = [4][n]: param, grad, importance, optpar; numel[t] = optpar's element count (a prefix of the parameter when the
 // class head has grown since the task was consolidated).
 __global__ __launch_bounds__(OPT_THREADS) void cl_penalty_kernel(MultiArgs a, float lambda, float* __restrict__ partial) {
@@ -151,10 +157,10 @@ __global__ __launch_bounds__(OPT_THREADS) void cl_penalty_kernel(MultiArgs a, fl
   if (cnt > a.chunk) cnt = a.chunk;
   float s = 0.f;
   for (long i = threadIdx.x; i < cnt; i += OPT_THREADS) {
-    const float d = o[i] - p[i];
-    const float fd = f[i] * d;
-    s += fd * d;
-    g[i] -= 2.f * lambda * fd;      // every parameter occurs once: plain read-modify-write
+    const double d = (double)o[i] - (double)p[i];
+    const double fd = (double)f[i] * d;
+    s += (float)(fd * d);
+    g[i] = (float)((double)g[i] - 2.0 * (double)lambda * fd);      // every parameter occurs once: plain read-modify-write
   }
   s = wave_sum(s);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
@@ -176,10 +182,10 @@ __global__ __launch_bounds__(OPT_THREADS) void cl_penalty_atomic_kernel(MultiArg
   if (cnt > a.chunk) cnt = a.chunk;
   float s = 0.f;
   for (long i = threadIdx.x; i < cnt; i += OPT_THREADS) {
-    const float d = o[i] - p[i];
-    const float fd = f[i] * d;
-    s += fd * d;
-    atomicAdd(&g[i], -2.f * lambda * fd);
+    const double d = (double)o[i] - (double)p[i];
+    const double fd = (double)f[i] * d;
+    s += (float)(fd * d);
+    atomicAdd(&g[i], (float)(-2.0 * (double)lambda * fd));
   }
   s = wave_sum(s);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
@@ -335,6 +341,7 @@ extern "C" int vilco_optim_step(const vilco_optim_desc* d, void* stream) {
   Hyper h;
   for (int i = 0; i < 8; ++i) { h.lr[i] = i < ngroups ? lr[i] : 0.f; h.wd[i] = i < ngroups ? wd[i] : 0.f; }
   h.beta1 = d->beta1; h.beta2 = d->beta2; h.eps = d->eps;
+  h.log_beta1 = (float)log((double)d->beta1); h.log_beta2 = (float)log((double)d->beta2);
   h.momentum = d->momentum;
   h.tstep = tensor_step;
   h.lr_dev = lr_dev;

@@ -76,7 +76,10 @@ class FusedOptimizer(optim.Optimizer):
 
     def __init__(self, params, lr, kind="AdamW", momentum=0.9, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01):
         assert kind in ("AdamW", "SGD")
-        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, momentum=momentum))
+        defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, momentum=momentum)
+        if kind == "SGD":
+            defaults.update(dampening=0.0, nesterov=False)      # what torch.optim.SGD.step reads from a loaded group
+        super().__init__(params, defaults)
         self.kind = kind
         self._plans = None              # list over passes, valid for self._plans_key
         self._plans_key = None
@@ -112,7 +115,10 @@ class FusedOptimizer(optim.Optimizer):
         base = [float(self.state[p]['step']) for p, _ in items]
         # step count handed to the kernel = count AFTER this pass's increment: a parameter listed m times goes
         # s -> s+1 (pass 0) -> s+2 (pass 1) ... within one iteration and by m from iteration to iteration
-        tstep0 = [b + (k + 1) - m for b, m in zip(base, inc)]
+        # SGD: the kernel only asks "first step?", and torch.optim.SGD collects every occurrence's (missing) buffer before it
+        # updates any, so all occurrences of a fresh parameter start the buffer from the gradient: pass k sees pass 0's count
+        kk = k if self.kind == "AdamW" else 0
+        tstep0 = [b + (kk + 1) - m for b, m in zip(base, inc)]
         uniform = all(m == 1.0 for m in inc)
         return dict(items=items, first=first, amax=amax,
                     amax_views=[amax[first[i]:first[i + 1]] for i in range(len(numel))],
@@ -143,14 +149,20 @@ class FusedOptimizer(optim.Optimizer):
 
     def load_state_dict(self, state_dict):
         self._plans, self._plans_key = None, None
-        return super().load_state_dict(state_dict)
+        out = super().load_state_dict(state_dict)
+        for g in self.param_groups:      # a torch.optim checkpoint's groups replace ours: AdamW's carry no momentum, SGD's no betas
+            for k, v in self.defaults.items():
+                g.setdefault(k, v)
+        return out
 
     def _ensure_state(self, items):
         for p, _ in items:
             if not (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous() and p.grad.is_contiguous()):
                 raise RuntimeError("FusedOptimizer needs contiguous fp32 parameters on the HIP device")
             st = self.state[p]
-            if len(st) == 0:
+            if self.kind == "SGD" and st.get('momentum_buffer') is not None and 'step' not in st:
+                st['step'] = torch.tensor(1.0)      # a torch.optim.SGD checkpoint: no count, but the buffer is live -- not `first`
+            if len(st) == 0 or (self.kind == "SGD" and st.get('momentum_buffer') is None):
                 st['step'] = torch.tensor(0.0)
                 if self.kind == "AdamW":
                     st['exp_avg'] = torch.zeros_like(p)
