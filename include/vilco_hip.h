@@ -538,8 +538,31 @@ typedef struct vilco_optim_desc {
   /* train_utils.py:351) and the per-tensor step counts `tensor_step` are memory the host (or a captured increment) rewrites        */
   /* between replays.                                                                                                               */
   const float* lr_dev;
+  /* optional (NULL: off): Synaptic Intelligence's path integral taken inside the update.  si_ptrs = device int64 [n]: the address of   */
+  /* each tensor's omega (fp32, the parameter's element count, walked with the same chunk table), or 0 for a tensor that is not        */
+  /* regularised.  Per element omega = fmaf(-gr, p_new - p_old, omega): gr = grad * clip coefficient (before SGD adds wd * p),          */
+  /* p_new - p_old the fp32 difference of the stored values.  p and the optimizer state get the bits they get with NULL.  omega is     */
+  /* memory a captured launch points at: it must outlive the graph, like the table.                                                    */
+  const int64_t* si_ptrs;
 } vilco_optim_desc;
 int vilco_optim_step(const vilco_optim_desc* d, void* stream);
+/* Synaptic Intelligence (Zenke et al. 2017), end of a task: ONE launch over all regularised tensors turns the path integral into  */
+/* importance, in place:                                                                                                          */
+/*   importance[i] = (i < numel_old[t] ? importance[i] : 0) + max(omega[i], 0) / ((p[i] - theta_start[i])^2 + xi)                   */
+/*   optpar[i] = p[i];  omega[i] = 0;  theta_start[i] = p[i]                                   for i < numel[t]                    */
+/* (quotient and sum in double, rounded once).  All five tensors of an entry hold numel[t] fp32 elements; importance beyond        */
+/* numel_old[t] is not read (fresh memory; the new rows of a class head that has grown).  n <= 0, a null table, xi <= 0:           */
+/* VILCO_ERR_BADARG.  nchunks == 0 launches nothing.                                                                              */
+typedef struct vilco_si_desc {
+  const int64_t* ptrs;         /* device [5][n]: param, omega, theta_start, importance, optpar */
+  const int64_t* numel;        /* device [n]: elements of the parameter */
+  const int64_t* numel_old;    /* device [n]: leading elements of importance that held a value before, 0 .. numel[t] */
+  const int32_t* chunk_tensor; /* device [nchunks] */
+  const int64_t* chunk_off;    /* device [nchunks] */
+  int32_t n, nchunks, chunk;
+  float xi;                    /* > 0 (Zenke: 0.1) */
+} vilco_si_desc;
+int vilco_si_consolidate(const vilco_si_desc* d, void* stream);
 /* dst[0..n) = vals[0..n): n <= 16 HOST floats carried as kernel arguments (stream-ordered, no staging buffer) -- how the */
 /* host hands this iteration's learning rates to a captured optimizer step.                                              */
 int vilco_store_f32(float* dst, const float* vals, int32_t n, void* stream);

@@ -113,7 +113,13 @@ class OptimDesc(C.Structure):
     _fields_ = [("kind", i32), ("ptrs", c_fp), ("numel", c_fp), ("chunk_tensor", c_fp), ("chunk_off", c_fp), ("group", c_fp),
                 ("n", i32), ("nchunks", i32), ("chunk", i32), ("lr", c_fp), ("wd", c_fp), ("ngroups", i32),
                 ("beta1", f32), ("beta2", f32), ("eps", f32), ("momentum", f32), ("tensor_step", c_fp), ("norm_coef", c_fp),
-                ("chunk_amax", c_fp), ("lr_dev", c_fp)]
+                ("chunk_amax", c_fp), ("lr_dev", c_fp), ("si_ptrs", c_fp)]
+
+
+class SiDesc(C.Structure):
+    _cname_ = "vilco_si_desc"
+    _fields_ = [("ptrs", c_fp), ("numel", c_fp), ("numel_old", c_fp), ("chunk_tensor", c_fp), ("chunk_off", c_fp),
+                ("n", i32), ("nchunks", i32), ("chunk", i32), ("xi", f32)]
 
 
 class DistillDesc(C.Structure):
@@ -202,6 +208,7 @@ SIGNATURES = {
     "vilco_permute3": (C.c_int, [c_fp, c_fp, i32, i32, i32, i64, i64, i64, i64, c_fp]),
     "vilco_grad_norm": (C.c_int, [c_fp, c_fp, c_fp, c_fp, i32, i32, i32, f32, c_fp, c_fp, c_fp]),
     "vilco_optim_step": (C.c_int, [C.POINTER(OptimDesc), c_fp]),
+    "vilco_si_consolidate": (C.c_int, [C.POINTER(SiDesc), c_fp]),
     "vilco_store_f32": (C.c_int, [c_fp, C.POINTER(f32), i32, c_fp]),
     "vilco_qkv_pre_supported": (C.c_int, [i32]),
     "vilco_qkv_pre_amax_parts": (C.c_int, [i32, i32, i32]),

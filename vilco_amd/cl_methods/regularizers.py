@@ -13,7 +13,12 @@ reference's autograd puts it too).
 The consolidation pass (`on_task_update`) reproduces the reference by default: the LAST batch's gradient, one more
 dictionary per task.  `importance='mean'` estimates the importance over the whole task and `merge='online'` keeps one
 dictionary for the whole stream; both do their arithmetic in vilco_cl_accumulate (csrc/optim.hip), one multi-tensor
-launch per batch / per merge."""
+launch per batch / per merge.
+
+Synaptic Intelligence (kind='si', bottom of the file) shares the penalty and MAS's 'importance' key; its importance is a
+path integral the optimizer's update kernel takes at every step, consolidated by one launch at the end of a task."""
+import ctypes
+
 import torch
 
 from .. import _lib, ops
@@ -22,6 +27,10 @@ CHUNK = 16384
 
 
 def _entries(model, kind):
+    """(parameter, importance, optpar) of every consolidated (task, name) pair; kind 'ewc' reads reg_params['fisher'],
+    'mas' and 'si' read reg_params['importance']"""
+    if kind not in ('ewc', 'mas', 'si'):
+        raise ValueError("kind must be 'ewc', 'mas' or 'si', got %r" % (kind,))
     reg = getattr(model, 'reg_params', None) or {}
     key = 'fisher' if kind == 'ewc' else 'importance'
     if key not in reg or 'optpar' not in reg:
@@ -203,3 +212,103 @@ def on_task_mas_update(loader_task, device, optimizer, model):
 
 def get_mas_regularized_loss(loss, model, reg_lambda):
     return get_regularized_loss(loss, model, reg_lambda, kind='mas')
+
+
+# ------------------------------------------------------------------------------------------------ Synaptic Intelligence
+# (Zenke, Poole, Ganguli 2017; the reference has no SI).  Per regularised parameter: `omega`, the path integral of the task so
+# far, advanced by the optimizer's update kernel at every step (FusedOptimizer.attach_si -> vilco_optim_desc.si_ptrs):
+#     omega <- omega - gr * (p_new - p_old),   gr = the clipped gradient the update consumes (penalty gradient included)
+# and `theta_start`, the parameter at the start of the task.  At the end of a task ONE launch (vilco_si_consolidate) makes
+#     Omega <- Omega_old + max(omega, 0) / ((theta - theta_start)^2 + xi),  theta* <- theta,  omega <- 0,  theta_start <- theta
+# Omega / theta* live in model.reg_params under MAS's keys ('importance' / 'optpar', ONE dictionary for the stream), so
+# `_entries(model, 'si')`, the penalty kernel, checkpoints and head growth (optpar a prefix of a grown head) work as for MAS.
+SI_XI = 0.1          # Zenke's default; cl_cfg['si_xi'] overrides it
+
+
+def si_xi(cl_cfg):
+    return float(cl_cfg.get('si_xi', SI_XI))
+
+
+def _si_params(model):
+    """the parameters SI regularises: what EWC / MAS regularise (`_entries`: no 'scale' in the name) among the trained ones"""
+    return [(name, p) for name, p in model.named_parameters() if p.requires_grad and 'scale' not in name]
+
+
+def si_begin_task(model, optimizer):
+    """Start of a task (after the class head has grown and the task's optimizer exists): a zeroed `omega` and a snapshot
+    `theta_start` for every regularised parameter, kept in model.si_state = {name: {'omega', 'theta_start'}}, and the omegas
+    attached to the optimizer, whose update kernel advances them from now on -- eagerly or replayed (attaching drops the
+    optimizer's cached plans, and a GraphedStep captured over them recaptures).  si_state is per task and is not
+    checkpointed.
+    Data parallel: nothing is exchanged.  Every rank steps with the averaged gradient and makes the same update, so omega,
+    theta_start and the consolidated importance are equal on all ranks by construction."""
+    state = {}
+    for name, p in _si_params(model):
+        if not (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous()):
+            raise RuntimeError("Synaptic Intelligence needs contiguous fp32 parameters on the HIP device (%s)" % name)
+        state[name] = {'omega': torch.zeros_like(p), 'theta_start': p.detach().clone()}
+    model.si_state = state
+    optimizer.attach_si({p: state[name]['omega'] for name, p in _si_params(model)})
+    return state
+
+
+def on_task_si_update(model, optimizer=None, xi=SI_XI):
+    """End of a task: one vilco_si_consolidate launch over all regularised tensors folds the task's path integral into the
+    importance (formula above), anchors theta* at the CURRENT parameters, zeroes omega and moves theta_start, all in place;
+    model.reg_params then holds one 'importance' / 'optpar' dictionary.  An importance that is already there (an earlier
+    task, a checkpoint) is Omega_old on its flat prefix: the rows a class head gained since start from zero, as in
+    `_merge_online`; a name SI does not track this task is carried unchanged.
+    Ordering (train_cl.run_episodes): SI consolidates from the state at the END of training -- the state its path integral
+    led to -- before the task's best checkpoint is reloaded, and needs no pass over the data.  `optimizer` is not stepped;
+    it keeps accumulating into the zeroed omegas if training goes on."""
+    if not xi > 0:
+        raise ValueError("si_xi must be positive, got %r" % (xi,))
+    state = getattr(model, 'si_state', None)
+    if not state:
+        raise RuntimeError("on_task_si_update without si_begin_task: the model carries no si_state")
+    reg = model.reg_params
+    if not ('importance' in reg and 'optpar' in reg):
+        reg['importance'], reg['optpar'] = [], []
+    if len(reg['importance']) > 1:
+        raise ValueError("Synaptic Intelligence keeps ONE importance dictionary; reg_params holds %d" % len(reg['importance']))
+    old_imp = reg['importance'][0] if reg['importance'] else {}
+    old_opt = reg['optpar'][0] if reg['optpar'] else {}
+    imp_d, opt_d, rows, numel, numel_old = {}, {}, [], [], []
+    for name, p in model.named_parameters():
+        st = state.get(name)
+        if st is None:
+            if name in old_imp:
+                imp_d[name], opt_d[name] = old_imp[name], old_opt[name]
+            continue
+        if st['omega'].numel() != p.numel() or not p.is_contiguous():
+            raise RuntimeError("si_state of %s does not fit the parameter: call si_begin_task after the head has grown" % name)
+        old = old_imp.get(name)
+        n_old = 0 if old is None else old.numel()
+        if old is not None and old.shape == p.shape and old.is_contiguous() and old.device == p.device:
+            imp, opt = old, old_opt[name]                  # updated in place
+        else:
+            imp, opt = torch.empty_like(p), torch.empty_like(p)          # what lies behind n_old is written, not read
+            if old is not None:
+                assert n_old <= p.numel() and old.shape[1:] == p.shape[1:], name
+                imp.view(-1)[:n_old].copy_(old.reshape(-1))
+        imp_d[name], opt_d[name] = imp, opt
+        rows.append((p.data_ptr(), st['omega'].data_ptr(), st['theta_start'].data_ptr(), imp.data_ptr(), opt.data_ptr()))
+        numel.append(p.numel())
+        numel_old.append(n_old)
+    if rows:
+        dev = next(iter(imp_d.values())).device
+        ct, co = [], []
+        for i, n in enumerate(numel):
+            for off in range(0, n, CHUNK):
+                ct.append(i)
+                co.append(off)
+        ptrs = torch.tensor([list(col) for col in zip(*rows)], dtype=torch.int64).to(dev)
+        t_numel = torch.tensor(numel, dtype=torch.int64).to(dev)
+        t_old = torch.tensor(numel_old, dtype=torch.int64).to(dev)
+        t_ct = torch.tensor(ct or [0], dtype=torch.int32).to(dev)
+        t_co = torch.tensor(co or [0], dtype=torch.int64).to(dev)
+        d = _lib.SiDesc(ptrs=ptrs.data_ptr(), numel=t_numel.data_ptr(), numel_old=t_old.data_ptr(), chunk_tensor=t_ct.data_ptr(),
+                        chunk_off=t_co.data_ptr(), n=len(rows), nchunks=len(ct), chunk=CHUNK, xi=float(xi))
+        _lib.check(_lib.load().vilco_si_consolidate(ctypes.byref(d), torch.cuda.current_stream().cuda_stream))
+    reg['importance'], reg['optpar'] = [imp_d], [opt_d]
+    return reg

@@ -79,8 +79,15 @@ __device__ __forceinline__ void emit_chunk_amax(float mx, float* __restrict__ ch
   if (threadIdx.x == 0) chunk_amax[blockIdx.x] = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
 }
 
+// SI (Synaptic Intelligence, Zenke et al. 2017): the update also advances the path integral of every regularised
+// tensor, omega <- fmaf(-gr, p_new - p_old, omega), gr = the clipped gradient the update consumes, p_new - p_old the fp32
+// difference of the stored values (so it contains the weight decay).  si_ptrs [n] = address of each tensor's omega (the
+// parameter's element count, walked with the same chunk table), 0 = not regularised.  Old value, gradient and new value are in
+// registers here: the cost is one more read-modify-write stream, no launch, no atomics (every element has one owner thread).
+// SI = false never reads si_ptrs and is the kernel as it was.
+template <bool SI>
 __global__ __launch_bounds__(OPT_THREADS) void adamw_kernel(MultiArgs a, Hyper h, const float* __restrict__ coef,
-                                                            float* __restrict__ chunk_amax) {
+                                                            float* __restrict__ chunk_amax, const long* __restrict__ si_ptrs) {
   const int t = a.chunk_tensor[blockIdx.x];
   const long off = a.chunk_off[blockIdx.x];
   float* p = reinterpret_cast<float*>(a.ptrs[t]) + off;
@@ -97,24 +104,46 @@ __global__ __launch_bounds__(OPT_THREADS) void adamw_kernel(MultiArgs a, Hyper h
   // ~100 roundings at steps 2..5), and half of that reaches the update through the square root
   const float step_size = lr / -expm1f(stp * h.log_beta1);
   const float rs2 = sqrtf(-expm1f(stp * h.log_beta2));
+  float* om = nullptr;
+  if constexpr (SI) {
+    const long oa = si_ptrs[t];
+    if (oa) om = reinterpret_cast<float*>(oa) + off;
+  }
   float mx = 0.f;
   for (long i = threadIdx.x; i < cnt; i += OPT_THREADS) {
-    const float gr = g[i] * c;
-    float pv = p[i] * (1.f - lr * wd);
-    const float mv = h.beta1 * m[i] + (1.f - h.beta1) * gr;
-    const float vv = h.beta2 * v[i] + (1.f - h.beta2) * gr * gr;
-    m[i] = mv;
-    v[i] = vv;
-    pv -= step_size * (mv / (sqrtf(vv) / rs2 + h.eps));
-    p[i] = pv;
-    mx = fmaxf(mx, fabsf(pv));
+    const float keep = 1.f - lr * wd;
+    {
+      // every product and sum of the element's update is rounded on its own: that is how this loop has always been compiled
+      // (packed multiplies, no fused multiply-add), and the pragma holds both instantiations to it -- the path integral's extra
+      // uses of gr and pv must not change a bit of p, m or v
+#pragma clang fp contract(off)
+      const float gr = g[i] * c;
+      const float p0 = p[i];
+      float ov = 0.f;
+      if constexpr (SI) {
+        if (om) ov = om[i];          // issued with the other loads, not behind the stores
+      }
+      float pv = p0 * keep;
+      const float mv = h.beta1 * m[i] + (1.f - h.beta1) * gr;
+      const float vv = h.beta2 * v[i] + (1.f - h.beta2) * gr * gr;
+      m[i] = mv;
+      v[i] = vv;
+      pv -= step_size * (mv / (sqrtf(vv) / rs2 + h.eps));
+      p[i] = pv;
+      if constexpr (SI) {
+        if (om) om[i] = __fmaf_rn(-gr, pv - p0, ov);
+      }
+      mx = fmaxf(mx, fabsf(pv));
+    }
   }
   if (chunk_amax) emit_chunk_amax(mx, chunk_amax);
 }
 
 // torch.optim.SGD with momentum (no dampening / nesterov): g += wd*p ; buf = first ? g : mom*buf + g ; p -= lr*buf
+// SI: as in adamw_kernel; gr is the clipped gradient BEFORE wd * p is added to it
+template <bool SI>
 __global__ __launch_bounds__(OPT_THREADS) void sgd_kernel(MultiArgs a, Hyper h, const float* __restrict__ coef,
-                                                          float* __restrict__ chunk_amax) {
+                                                          float* __restrict__ chunk_amax, const long* __restrict__ si_ptrs) {
   const int t = a.chunk_tensor[blockIdx.x];
   const long off = a.chunk_off[blockIdx.x];
   float* p = reinterpret_cast<float*>(a.ptrs[t]) + off;
@@ -126,14 +155,30 @@ __global__ __launch_bounds__(OPT_THREADS) void sgd_kernel(MultiArgs a, Hyper h, 
   const float lr = h.lr_dev ? h.lr_dev[gi] : h.lr[gi], wd = h.wd[gi];
   const float c = coef ? coef[1] : 1.f;
   const bool first = h.tstep[t] <= 1.f;          // momentum buffer starts as the first gradient
+  float* om = nullptr;
+  if constexpr (SI) {
+    const long oa = si_ptrs[t];
+    if (oa) om = reinterpret_cast<float*>(oa) + off;
+  }
   float mx = 0.f;
   for (long i = threadIdx.x; i < cnt; i += OPT_THREADS) {
+    // the roundings this loop has always been compiled to, spelled out so that both instantiations keep them whatever else uses
+    // gc and pv: c g and wd p rounded on their own and added; momentum buf + d and p - lr buf fused
+#pragma clang fp contract(off)
     const float pv0 = p[i];
-    float gr = g[i] * c + wd * pv0;
-    const float b = first ? gr : h.momentum * m[i] + gr;
+    const float gc = g[i] * c;
+    float ov = 0.f;
+    if constexpr (SI) {
+      if (om) ov = om[i];
+    }
+    float gr = gc + wd * pv0;
+    const float b = first ? gr : __fmaf_rn(h.momentum, m[i], gr);
     m[i] = b;
-    const float pv = pv0 - lr * b;
+    const float pv = __fmaf_rn(-lr, b, pv0);
     p[i] = pv;
+    if constexpr (SI) {
+      if (om) om[i] = __fmaf_rn(-gc, pv - pv0, ov);
+    }
     mx = fmaxf(mx, fabsf(pv));
   }
   if (chunk_amax) emit_chunk_amax(mx, chunk_amax);
@@ -249,6 +294,34 @@ __global__ __launch_bounds__(OPT_THREADS) void cl_accumulate_kernel(MultiArgs a,
   cl_acc_scalar<OP>(src, acc, head + 4 * nvec, cnt, alpha, beta, rd_src, rd_acc);
 }
 
+// End of a task under Synaptic Intelligence: the path integral becomes importance, in place, ONE launch over all tensors.
+//   Omega = Omega_old + max(omega, 0) / ((p - theta_start)^2 + xi) ; optpar = p ; omega = 0 ; theta_start = p
+// ptrs = [5][n]: param, omega, theta_start, importance, optpar, each of numel[t] elements; importance held a value in its first
+// numel_old[t] elements only (0: none yet; a prefix: the class head has grown), what lies behind them is not read.
+// The quotient and the sum are formed in double and rounded once.  One owner thread per element, five streams, no atomics.
+__global__ __launch_bounds__(OPT_THREADS) void si_consolidate_kernel(MultiArgs a, const long* __restrict__ numel_old, float xi) {
+  const int t = a.chunk_tensor[blockIdx.x];
+  const long off = a.chunk_off[blockIdx.x];
+  const float* p = reinterpret_cast<const float*>(a.ptrs[t]) + off;
+  float* om = reinterpret_cast<float*>(a.ptrs[(long)a.n + t]) + off;
+  float* ts = reinterpret_cast<float*>(a.ptrs[2L * a.n + t]) + off;
+  float* f = reinterpret_cast<float*>(a.ptrs[3L * a.n + t]) + off;
+  float* o = reinterpret_cast<float*>(a.ptrs[4L * a.n + t]) + off;
+  long cnt = a.numel[t] - off;
+  if (cnt > a.chunk) cnt = a.chunk;
+  if (off < 0 || cnt <= 0) return;
+  const long old = numel_old[t] - off;           // elements of this chunk that carry an earlier importance
+  for (long i = threadIdx.x; i < cnt; i += OPT_THREADS) {
+    const float pv = p[i];
+    const double d = (double)pv - (double)ts[i];
+    const double q = (double)fmaxf(om[i], 0.f) / (d * d + (double)xi);
+    f[i] = (float)(i < old ? (double)f[i] + q : q);
+    o[i] = pv;
+    om[i] = 0.f;
+    ts[i] = pv;
+  }
+}
+
 __global__ __launch_bounds__(OPT_THREADS) void scaled_sum_kernel(const float* __restrict__ partial, int n, float scale,
                                                                  float* __restrict__ out) {
   __shared__ double red[OPT_THREADS];
@@ -348,7 +421,23 @@ extern "C" int vilco_optim_step(const vilco_optim_desc* d, void* stream) {
   MultiArgs a{reinterpret_cast<const long*>(ptrs), reinterpret_cast<const long*>(numel), chunk_tensor,
               reinterpret_cast<const long*>(chunk_off), group, n, chunk};
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (kind == 0) hipLaunchKernelGGL(adamw_kernel, dim3(nchunks), dim3(OPT_THREADS), 0, s, a, h, norm_coef, chunk_amax);
-  else hipLaunchKernelGGL(sgd_kernel, dim3(nchunks), dim3(OPT_THREADS), 0, s, a, h, norm_coef, chunk_amax);
+  const long* si = reinterpret_cast<const long*>(d->si_ptrs);
+  const dim3 grid(nchunks), block(OPT_THREADS);
+  if (kind == 0 && si) hipLaunchKernelGGL(adamw_kernel<true>, grid, block, 0, s, a, h, norm_coef, chunk_amax, si);
+  else if (kind == 0) hipLaunchKernelGGL(adamw_kernel<false>, grid, block, 0, s, a, h, norm_coef, chunk_amax, si);
+  else if (si) hipLaunchKernelGGL(sgd_kernel<true>, grid, block, 0, s, a, h, norm_coef, chunk_amax, si);
+  else hipLaunchKernelGGL(sgd_kernel<false>, grid, block, 0, s, a, h, norm_coef, chunk_amax, si);
+  return vilco_launch_status();
+}
+
+extern "C" int vilco_si_consolidate(const vilco_si_desc* d, void* stream) {
+  if (!d) return VILCO_ERR_BADARG;
+  if (!d->ptrs || !d->numel || !d->numel_old || !d->chunk_tensor || !d->chunk_off) return VILCO_ERR_BADARG;
+  if (d->n <= 0 || d->nchunks < 0 || d->chunk <= 0 || !(d->xi > 0.f)) return VILCO_ERR_BADARG;
+  if (d->nchunks == 0) return VILCO_OK;
+  MultiArgs a{reinterpret_cast<const long*>(d->ptrs), reinterpret_cast<const long*>(d->numel), d->chunk_tensor,
+              reinterpret_cast<const long*>(d->chunk_off), nullptr, d->n, d->chunk};
+  hipLaunchKernelGGL(si_consolidate_kernel, dim3(d->nchunks), dim3(OPT_THREADS), 0, reinterpret_cast<hipStream_t>(stream), a,
+                     reinterpret_cast<const long*>(d->numel_old), d->xi);
   return vilco_launch_status();
 }

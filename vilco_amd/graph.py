@@ -20,10 +20,12 @@ buffer of the distillation targets of the batch's first cached clip), the dropou
 the stochastic-depth factors (torch's graph-safe Philox draw, captured), BiC's alpha / beta (the correction kernel reads them
 through a table of the layers' addresses: stage 2 writes them after the capture), the loss-normaliser EMA, the optimizer's step
 counts and learning rates (vilco_optim_desc.lr_dev), the narration memory bank and its ring word (csrc/ssl.hip: the update
-advances the word on the device by the number of narrated clips, which differs from batch to batch).
+advances the word on the device by the number of narrated clips, which differs from batch to batch), and -- under Synaptic
+Intelligence -- the path integrals `omega`, which the captured update advances on every replay through its table of their
+addresses (vilco_optim_desc.si_ptrs; table and omegas are kept alive by the optimizer).
 
 What is captured is what ran: graphs are keyed by the input shapes, task id, the identity / requires_grad of every
-parameter and BiC's split table with the addresses of its layers, and dropped when parameters were written from outside (load_state_dict, an eager optimizer step) -- cached
+parameter and BiC's split table with the addresses of its layers, and dropped when parameters were written from outside (load_state_dict, an eager optimizer step) or Synaptic Intelligence was attached / re-attached to the optimizer (a new task's omegas) -- cached
 operand planes and max|w| partials would be stale otherwise.  Steps the device half cannot run alone (distillation
 against host-side NumPy targets or in a batch without a cached clip, a BiC model whose split table the correction kernel
 does not take, narration SSL with its fused path switched off by VILCO_FUSED_SSL=0) fall back to the eager path.
@@ -232,7 +234,10 @@ class GraphedStep:
         if self.optimizer is None:
             return ent['wgen'] == ops._weight_gen[0]      # weights written through raw pointers since the capture: the
                                                           # captured forward reads operand planes packed before it
-        return ent['plans'] is self.optimizer._plans      # (a captured update re-packs its weights inside graph 1)
+        # (a captured update re-packs its weights inside graph 1.)  The captured update launch holds the plan's tables, the
+        # Synaptic-Intelligence table among them (or its absence): FusedOptimizer.attach_si drops the plans and advances si_gen,
+        # so a graph captured without SI is never replayed with it, nor with another task's omegas, nor the other way round
+        return ent['plans'] is self.optimizer._plans and ent['si_gen'] == self.optimizer.si_gen
 
     # ------------------------------------------------------------------ capture
     def _capture(self, ent, inp, task_id):
@@ -353,7 +358,7 @@ class GraphedStep:
                 opt.step(clip_grad_l2norm=self.clip, lr_dev=self._lr_dev)
             for pl in opt._plans:            # the capture counted an update that did not run
                 pl['count'] -= 1
-            ent.update(opt_graph=g2, plans=opt._plans)
+            ent.update(opt_graph=g2, plans=opt._plans, si_gen=opt.si_gen)
         # the parameters the captured step reads: those that got a gradient, and frozen ones (the adapters' EMA copies are
         # neither: they are written in place after every iteration and only read at inference)
         ent['tracked'] = [p for p, g in zip(self.params, ent['grads']) if g is not None or not p.requires_grad]

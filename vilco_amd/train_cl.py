@@ -11,6 +11,7 @@ reference driver MQ/train_cl.py:206-389 (+ load_best_checkpoint :31-40), written
       reload the task's best checkpoint, final validation           (:363-365)
       if another task follows: augment_classification(num_next_classes), EWC / MAS consolidation, NEW optimizer
           and scheduler                                             (:373-389)
+      [cl_cfg.name 'si' (ours): si_begin_task before the epochs, consolidation right after them, before the reload]
 
 What is ours rather than the reference's: the stream is any iterable with QILSetTask's contract
 (`(data, loader, num_next_classes)` per task, a `.memory` attribute; utils/cl_stream.py has an in-memory one --
@@ -109,6 +110,26 @@ def make_mq_validate(cfg, val_stream, evaluator, retrieval_eval=None, idx_classe
     return validate
 
 
+def _si_check(cfg, start_epoch):
+    """cl_cfg.name == 'si'?  A resume inside a task is refused: the path integral of the epochs already trained is per-task
+    state (model.si_state) that checkpoints do not carry."""
+    use_si = cfg['cl_cfg']['name'] == 'si'
+    if use_si:
+        regularizers.si_xi(cfg['cl_cfg'])
+        if start_epoch > 0:
+            raise ValueError("cl_cfg.name 'si' cannot resume inside a task (start_epoch = %d): the path integral of the epochs "
+                             "already trained is not checkpointed; resume at a task boundary" % start_epoch)
+    return use_si
+
+
+def _si_consolidate(cfg, model, optimizer):
+    """Synaptic Intelligence's consolidation, called where the task's training ends: from the state the path integral led
+    to, BEFORE the best checkpoint is reloaded, without a pass over the data (EWC / MAS consolidate after the reload, over
+    the task's loader).  The caller installs the returned dictionary after the reload, which restores the checkpoint's."""
+    reg = regularizers.on_task_si_update(model, optimizer, xi=regularizers.si_xi(cfg['cl_cfg']))
+    return {k: list(v) for k, v in reg.items()}
+
+
 def run_episodes(cfg, model, train_stream, validate=None, ckpt_folder=None, gpu_id=0, start_task=0, start_epoch=0,
                  combine_train=False, reducer=None, logger=None, print_freq=20, on_step_history=None, use_graph=False,
                  keep_history=True):
@@ -121,6 +142,7 @@ def run_episodes(cfg, model, train_stream, validate=None, ckpt_folder=None, gpu_
     Returns (model, optimizer, scheduler, log) with log = list of per-task dicts."""
     is_main = int(os.environ.get("LOCAL_RANK", "0")) == 0
     imp_opts = regularizers.importance_options(cfg['cl_cfg'])      # a bad value fails here, not after the first task
+    use_si = _si_check(cfg, start_epoch)
     optimizer = make_optimizer(model, cfg['opt'])
 
     def make_graph(opt):
@@ -146,6 +168,8 @@ def run_episodes(cfg, model, train_stream, validate=None, ckpt_folder=None, gpu_
         best, best_epoch = -10000.0, -1
         prev_logits = cache_prev_logits(model, loader, j) if model.type_sampling == 'icarl' else {}
         ck_name = 'best_task_{:03d}_performance.pth.tar'.format(j)
+        if use_si:
+            regularizers.si_begin_task(model, optimizer)      # the head has grown, this task's optimizer exists
         for epoch in range(start_epoch, max_epochs):
             sampler = getattr(loader, 'sampler', None)
             if sampler is not None and hasattr(sampler, 'set_epoch'):
@@ -174,6 +198,7 @@ def run_episodes(cfg, model, train_stream, validate=None, ckpt_folder=None, gpu_
             _barrier(reducer)          # the other ranks do not run ahead into the next epoch's collectives while rank 0
                                        # validates and writes the checkpoint
         entry['best_metric'], entry['best_epoch'] = best, best_epoch
+        si_reg = _si_consolidate(cfg, model, optimizer) if use_si and num_next is not None else None
 
         # replay memory for the next task (train_cl.py:343-361)
         n_cls = model.cls_head.cls_head.conv.out_channels
@@ -202,6 +227,8 @@ def run_episodes(cfg, model, train_stream, validate=None, ckpt_folder=None, gpu_
             elif cfg['cl_cfg']['name'] == 'mas':
                 model.reg_params = regularizers.on_task_update(loader, gpu_id, optimizer, model, kind='mas', group=getattr(reducer, 'group', None), data_parallel=reducer is not None,
                                                                **imp_opts)
+            elif use_si:
+                model.reg_params = si_reg      # (the reload above put the checkpoint's older dictionary back)
             optimizer = make_optimizer(model, cfg['opt'])
             scheduler = make_scheduler(optimizer, cfg['opt'], iters_per_epoch)
             if reducer is not None:
@@ -380,6 +407,7 @@ def run_episodes_nlq(cfg, model, train_stream, val_stream, evaluator, ckpt_folde
     from .utils import train_utils_nlq as tu
     is_main = int(os.environ.get("LOCAL_RANK", "0")) == 0
     imp_opts = regularizers.importance_options(cfg['cl_cfg'])
+    use_si = _si_check(cfg, start_epoch)
     hb = cfg['opt']["backbone_lr_weight"] != 1
 
     def new_optimizer():
@@ -420,6 +448,8 @@ def run_episodes_nlq(cfg, model, train_stream, val_stream, evaluator, ckpt_folde
         tracker.new_task(entry['init_R1'])
         prev_logits = cache_prev_logits(model, loader, j, as_numpy=True) if model.type_sampling == 'icarl' else {}
         ck_name = 'Best_task_{:02d}.pth.tar'.format(j)
+        if use_si:
+            regularizers.si_begin_task(model, optimizer)      # a new optimizer per task: attached again
         for epoch in range(start_epoch, max_epochs):
             sampler = getattr(loader, 'sampler', None)
             if sampler is not None and hasattr(sampler, 'set_epoch'):
@@ -451,6 +481,7 @@ def run_episodes_nlq(cfg, model, train_stream, val_stream, evaluator, ckpt_folde
             if validated or is_best:
                 _barrier(reducer)
         entry['best_R1'], entry['best_epoch'] = tracker.best, tracker.best_epoch
+        si_reg = _si_consolidate(cfg, model, optimizer) if use_si and num_next is not None else None
         if memory_size != 0:
             model.add_samples_to_mem(val_stream, data, 'ALL' if memory_size == 'ALL' else memory_size // 13)
         train_stream.memory = model.memory
@@ -469,6 +500,8 @@ def run_episodes_nlq(cfg, model, train_stream, val_stream, evaluator, ckpt_folde
                 model.reg_params = regularizers.on_task_update(loader, gpu_id, optimizer, model, kind=cfg['cl_cfg']['name'],
                                                                group=getattr(reducer, 'group', None), data_parallel=reducer is not None,
                                                                **imp_opts)
+            elif use_si:
+                model.reg_params = si_reg
             optimizer = new_optimizer()
             scheduler = tu.make_scheduler(optimizer, cfg['opt'], iters_per_epoch)
             graph = make_graph(optimizer)

@@ -84,7 +84,23 @@ class FusedOptimizer(optim.Optimizer):
         self._plans = None              # list over passes, valid for self._plans_key
         self._plans_key = None
         self.last_grad_norm = None      # device tensor [norm, clip coef] of the last step
+        self._si = None                 # {id(param): (param, omega)} while Synaptic Intelligence is attached
+        self.si_gen = 0                 # advanced by every attach_si(): a captured step holds the table of ONE attachment
 
+    def attach_si(self, omegas):
+        """Synaptic Intelligence (cl_methods/regularizers.py): from now on every update also advances the path integral
+        omega <- omega - gr * (p_new - p_old) of the parameters in `omegas` ({param: fp32 tensor of the parameter's shape}),
+        inside the update kernel (vilco_optim_desc.si_ptrs).  None detaches.  The [n] address table is built with the step
+        plan, in its order, one per pass (a parameter listed k times adds the path of each of its k updates); cached plans
+        are dropped, and with them whatever was captured over them.  The optimizer keeps the omegas alive; state_dict()
+        does not hold them."""
+        if omegas is not None:
+            for q, om in omegas.items():
+                if not (om.is_cuda and om.dtype == torch.float32 and om.is_contiguous() and om.numel() == q.numel()):
+                    raise RuntimeError("attach_si: omega must be a contiguous fp32 device tensor with the parameter's element count")
+        self._flush_steps()
+        self._si = None if omegas is None else {id(q): (q, om) for q, om in omegas.items()}
+        self.si_gen += 1
     def _passes(self):
         """[(param, group index)] lists; a parameter listed k times (the adapter aliases of train_utils.py:108-113)
         is stepped k times per iteration like torch.optim would: k-th occurrences go to pass k."""
@@ -120,7 +136,11 @@ class FusedOptimizer(optim.Optimizer):
         kk = k if self.kind == "AdamW" else 0
         tstep0 = [b + (kk + 1) - m for b, m in zip(base, inc)]
         uniform = all(m == 1.0 for m in inc)
-        return dict(items=items, first=first, amax=amax,
+        si = None
+        if self._si is not None:        # address of every tensor's omega in plan order, 0 = not regularised
+            si = torch.tensor([self._si[id(p)][1].data_ptr() if id(p) in self._si else 0 for p, _ in items],
+                              dtype=torch.int64, device=dev)
+        return dict(items=items, first=first, amax=amax, si=si,
                     amax_views=[amax[first[i]:first[i + 1]] for i in range(len(numel))],
                     numel=torch.tensor(numel, dtype=torch.int64, device=dev),
                     chunk_tensor=torch.tensor(ct, dtype=torch.int32, device=dev),
@@ -251,7 +271,8 @@ class FusedOptimizer(optim.Optimizer):
                                momentum=g0['momentum'], tensor_step=plan['tstep'].data_ptr(),
                                norm_coef=None if coef is None or clip_grad_l2norm <= 0 else coef.data_ptr(),
                                chunk_amax=plan['amax'].data_ptr() if OPT_AMAX else None,
-                               lr_dev=None if lr_dev is None else lr_dev.data_ptr())
+                               lr_dev=None if lr_dev is None else lr_dev.data_ptr(),
+                               si_ptrs=None if plan['si'] is None else plan['si'].data_ptr())
             _lib.check(lib.vilco_optim_step(C.byref(d), stream))
             first = plan['first']
             for i, (p, _) in enumerate(items):
@@ -354,7 +375,7 @@ def train_one_epoch(train_loader, model, optimizer, scheduler, curr_epoch, n_gpu
                     prev_out_cls_logits_dict=None, current_task_id=0, reducer=None, graph=None, keep_history=True):
     """One epoch of the continual-learning training loop (train_utils.py:278-423), same arguments.  Per iteration:
     zero_grad, forward with `task_id` and the cached iCaRL/BiC logits of the batch's videos, backward of
-    final_loss (+ the EWC / MAS penalty of cl_name, applied as one multi-tensor kernel that adds its gradient to
+    final_loss (+ the EWC / MAS / SI penalty of cl_name, applied as one multi-tensor kernel that adds its gradient to
     p.grad), [gradient all-reduce], fused clip + optimizer step, scheduler step, adapter EMA (`post_train_step`).
     Nothing in the loop reads a device value unless a log line is due (every `print_freq` iterations).
     graph: a vilco_amd.graph.GraphedStep built over (model, optimizer, clip_grad_l2norm[, reducer]) -- iterations whose
@@ -376,7 +397,7 @@ def train_one_epoch(train_loader, model, optimizer, scheduler, curr_epoch, n_gpu
         # loss + lambda * sum_i sum_p F_i (theta*_i - theta)^2 (EWC.py:6-22 / MAS.py:5-21): value added to the
         # reported loss, gradient added straight into p.grad.  The penalty is the same on every rank, so adding it
         # after the gradient average equals averaging it.
-        last_pen[0] = regularizers.apply_penalty(model, reg_lambda, kind=cl_name) if cl_name in ('ewc', 'mas') else None
+        last_pen[0] = regularizers.apply_penalty(model, reg_lambda, kind=cl_name) if cl_name in ('ewc', 'mas', 'si') else None
 
     for iter_idx, video_list in enumerate(train_loader, 0):
         prev = []

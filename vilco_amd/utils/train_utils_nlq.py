@@ -133,7 +133,7 @@ def train_one_epoch(train_loader, model, optimizer, scheduler, curr_epoch, model
                     tb_writer=None, print_freq=20, cl_name=None, reg_lambda=0.0, prev_out_cls_logits_dict=None,
                     current_task_id=0, reducer=None, graph=None, keep_history=True, logger=None):
     """the reference's signature (:376-390); the iteration itself is the MQ one (same sequence: zero_grad, forward with
-    task_id, [EWC / MAS penalty], backward, clip, optimizer and scheduler step, adapter EMA)"""
+    task_id, [EWC / MAS / SI penalty], backward, clip, optimizer and scheduler step, adapter EMA)"""
     if not hasattr(model, 'use_adapt'):
         model.use_adapt = getattr(model, 'use_adapter', False)
     return mq.train_one_epoch(train_loader, model, optimizer, scheduler, curr_epoch, 1, model_ema=model_ema,
