@@ -503,26 +503,39 @@ int vilco_permute3(const float* in, float* out, int32_t d0, int32_t d1, int32_t 
                    int64_t s0, int64_t s1, int64_t s2, void* stream);
 
 /* ------------------------------------------------------------------------------------------ */
+/* The chunk table every multi-tensor kernel walks (csrc/optim.hip), one block per chunk.                     */
+/* A ROW is one stream of the operator: ptrs[k * n + t] is the address of tensor t's fp32 data in row k, so   */
+/* entry t is the tuple (ptrs[0][t], ptrs[1][t], ...); each entry point names its rows and needs `rows` to be */
+/* at least as many as it reads.  numel[t] = elements of entry t to walk, the same in every row: the whole    */
+/* tensor, or a PREFIX of it when the class head has grown since the shorter row was made.  The work is cut   */
+/* into nchunks chunks of at most `chunk` elements: chunk c covers elements chunk_off[c] .. of entry          */
+/* chunk_tensor[c].  The chunks of one entry are consecutive and ascending, so per-chunk outputs (partial     */
+/* sums, chunk_amax) of entry t are one contiguous run.  A chunk that lies outside its entry does nothing.    */
+/* A null table, n < 0, nchunks < 0, chunk <= 0 or too few rows: VILCO_ERR_BADARG.                            */
+/* ------------------------------------------------------------------------------------------ */
+typedef struct vilco_chunk_table {
+  const int64_t* ptrs;         /* device [rows][n] */
+  const int64_t* numel;        /* device [n] */
+  const int32_t* chunk_tensor; /* device [nchunks] */
+  const int64_t* chunk_off;    /* device [nchunks] */
+  int32_t rows, n, nchunks, chunk;
+} vilco_chunk_table;
+
+/* ------------------------------------------------------------------------------------------ */
 /* Step glue of train_one_epoch (MQ/libs/utils/train_utils.py:343-351): clip_grad_norm_ + optimizer.step()  */
-/* as multi-tensor kernels.  ptrs = device int64 [4][n] (param, grad, state1, state2 pointers of the n      */
-/* gradient-bearing fp32 tensors), numel [n]; the work is cut into nchunks chunks of `chunk` elements        */
-/* (chunk_tensor / chunk_off).  norm_coef (device float[2]) = {total L2 norm, min(1, max_norm/(norm+1e-6))}; */
+/* as multi-tensor kernels over the n gradient-bearing fp32 tensors.                                         */
+/* vilco_grad_norm reads row 1 (grad) of a table of >= 2 rows -- the optimizer's own table serves.           */
+/* norm_coef (device float[2]) = {total L2 norm, min(1, max_norm/(norm+1e-6))};                              */
 /* pass it to vilco_optim_step to scale gradients without a host sync, or null.                              */
 /* kind 0 = torch.optim.AdamW (decoupled decay; tensor_step = device float[n], each tensor's step count      */
 /* after this update, for the bias corrections), 1 = SGD with momentum.                                      */
 /* lr / wd are HOST arrays indexed by parameter group (group[n] on the device).                              */
 /* ------------------------------------------------------------------------------------------ */
-int vilco_grad_norm(const int64_t* ptrs, const int64_t* numel, const int32_t* chunk_tensor,
-                    const int64_t* chunk_off, int32_t n, int32_t nchunks, int32_t chunk, float max_norm,
-                    float* partial, float* norm_coef, void* stream);
+int vilco_grad_norm(const vilco_chunk_table* table, float max_norm, float* partial, float* norm_coef, void* stream);
 typedef struct vilco_optim_desc {
+  vilco_chunk_table table;     /* rows: param, grad, exp_avg or momentum buffer, exp_avg_sq (AdamW reads 4, SGD 3) */
   int32_t kind;                /* 0 = AdamW, 1 = SGD with momentum */
-  const int64_t* ptrs;         /* device [4][n] */
-  const int64_t* numel;        /* device [n] */
-  const int32_t* chunk_tensor; /* device [nchunks] */
-  const int64_t* chunk_off;    /* device [nchunks] */
   const int32_t* group;        /* device [n]: parameter group of every tensor */
-  int32_t n, nchunks, chunk;
   const float* lr;             /* HOST [ngroups] */
   const float* wd;             /* HOST [ngroups] */
   int32_t ngroups;             /* 1..8 */
@@ -554,12 +567,8 @@ int vilco_optim_step(const vilco_optim_desc* d, void* stream);
 /* numel_old[t] is not read (fresh memory; the new rows of a class head that has grown).  n <= 0, a null table, xi <= 0:           */
 /* VILCO_ERR_BADARG.  nchunks == 0 launches nothing.                                                                              */
 typedef struct vilco_si_desc {
-  const int64_t* ptrs;         /* device [5][n]: param, omega, theta_start, importance, optpar */
-  const int64_t* numel;        /* device [n]: elements of the parameter */
+  vilco_chunk_table table;     /* rows: param, omega, theta_start, importance, optpar; numel[t] = elements of the parameter */
   const int64_t* numel_old;    /* device [n]: leading elements of importance that held a value before, 0 .. numel[t] */
-  const int32_t* chunk_tensor; /* device [nchunks] */
-  const int64_t* chunk_off;    /* device [nchunks] */
-  int32_t n, nchunks, chunk;
   float xi;                    /* > 0 (Zenke: 0.1) */
 } vilco_si_desc;
 int vilco_si_consolidate(const vilco_si_desc* d, void* stream);
@@ -698,25 +707,22 @@ int vilco_bic_correct_bwd(const vilco_bic_correct_desc* d, const float* x_fwd, i
 /* Continual-learning regularisers of MQ/libs/cl_methods/EWC.py:6-22 (get_regularized_loss) and MAS.py:5-21   */
 /* (get_mas_regularized_loss), called per iteration from train_utils.py:337-344, as ONE multi-tensor launch:    */
 /*   out[0] = lambda * sum_t sum_{i < numel[t]} F_t[i] (opt_t[i] - p_t[i])^2,   grad_t[i] -= 2 lambda F (opt - p) */
-/* ptrs = device int64 [4][n]: parameter, its gradient (accumulated into), importance F (Fisher / |grad|),      */
-/* consolidated value opt; numel[t] = elements of opt_t (a PREFIX of the parameter when the class head has grown */
-/* since the task, EWC.py:19-21).  Same chunk table as the optimizer.  shared_params != 0: some parameter occurs */
-/* in more than one entry (several consolidated tasks) -> gradient accumulated with atomics.                    */
+/* table rows (>= 4): parameter, its gradient (accumulated into), importance F (Fisher / |grad|), consolidated */
+/* value opt; numel[t] = elements of opt_t (a prefix of the parameter when the class head has grown since the   */
+/* task, EWC.py:19-21).  shared_params != 0: some parameter occurs in more than one entry (several consolidated */
+/* tasks) -> gradient accumulated with atomics.                                                                 */
 /* ------------------------------------------------------------------------------------------ */
-int vilco_cl_penalty(const int64_t* ptrs, const int64_t* numel, const int32_t* chunk_tensor,
-                     const int64_t* chunk_off, int32_t n, int32_t nchunks, int32_t chunk, float lambda,
-                     int32_t shared_params, float* partial, float* out, void* stream);
+int vilco_cl_penalty(const vilco_chunk_table* table, float lambda, int32_t shared_params, float* partial, float* out,
+                     void* stream);
 /* Importance accumulation of the consolidation passes MQ/libs/cl_methods/EWC.py:24-56 (on_task_update) and MAS.py:23-57        */
 /* (on_task_mas_update), which keep the last batch's squared / absolute gradient; summing over the batches, and merging the   */
 /* tasks (the commented-out consolidate_reg_params of MAS.py), is ONE multi-tensor launch over the same chunk table:           */
 /*   acc_t[i] = beta * acc_t[i] + alpha * f(src_t[i])   for i < numel[t];   op 0: f(x) = x, 1: x * x, 2: |x|                  */
-/* ptrs = device int64 [2][n]: src, acc.  numel[t] may be shorter than either allocation: elements past it are not touched.    */
+/* table rows (>= 2): src, acc.  numel[t] may be shorter than either allocation: elements past it are not touched.            */
 /* beta == 0: acc is not read (fresh memory needs no memset, NaNs in it do not propagate); alpha == 0: src is not read.        */
 /* Every element has one owner thread: no atomics, no workspace, the same bits on every call.  16-byte accesses wherever src  */
 /* and acc are misaligned by the same amount, 4-byte accesses otherwise.  nchunks == 0 launches nothing.                       */
-int vilco_cl_accumulate(const int64_t* ptrs, const int64_t* numel, const int32_t* chunk_tensor,
-                        const int64_t* chunk_off, int32_t n, int32_t nchunks, int32_t chunk, int32_t op, float alpha,
-                        float beta, void* stream);
+int vilco_cl_accumulate(const vilco_chunk_table* table, int32_t op, float alpha, float beta, void* stream);
 
 /* Deferred finishing (csrc/defer.hip).  The second stage of every two-stage column reduction (LayerNorm d-gamma / d-beta,  */
 /* bias and scale gradients, depthwise-tap gradients: reference autograd sums under blocks.py:152-166, 106-130, 628-641)  */

@@ -15,6 +15,45 @@ import numpy as np
 import torch
 
 
+CHUNK = 16384          # elements per chunk of the multi-tensor kernels, stated here on its own: not read from the library
+
+
+def chunk_lists(numels, chunk=CHUNK):
+    """(chunk_tensor, chunk_off, first) of a vilco_chunk_table as host lists: tensor i is cut into chunks of `chunk` elements at
+    offsets 0, chunk, ...; first[i] .. first[i + 1] are its chunks (first has len(numels) + 1 entries).  The tests' own
+    statement of the walking convention: vilco_amd.ops.ChunkPlan is held against it, and is not used to build it."""
+    ct, co, first = [], [], []
+    for i, n in enumerate(numels):
+        first.append(len(ct))
+        for off in range(0, n, chunk):
+            ct.append(i)
+            co.append(off)
+    first.append(len(ct))
+    return ct, co, first
+
+
+class Table:
+    """a vilco_chunk_table on the device, built by hand: `ptr_rows` = the address rows [rows][n], `numels` = elements per entry;
+    empty lists are padded to one element so that no address is null.  `struct()` is the ctypes mirror of it."""
+
+    def __init__(self, dev, ptr_rows, numels):
+        self.numels, self.n, self.nrows, self.dev = list(numels), len(numels), len(ptr_rows), dev
+        ct, co, self.first = chunk_lists(self.numels)
+        self.nchunks = len(ct)
+        self.ptrs = torch.tensor(ptr_rows if self.n else [[0]] * self.nrows, dtype=torch.int64).to(dev)
+        self.numel = torch.tensor(self.numels or [0], dtype=torch.int64).to(dev)
+        self.ct = torch.tensor(ct or [0], dtype=torch.int32).to(dev)
+        self.co = torch.tensor(co or [0], dtype=torch.int64).to(dev)
+        self.partial = torch.full((max(self.nchunks, 1),), float('nan'), device=dev)
+
+    def struct(self, **kw):
+        from vilco_amd import _lib
+        f = dict(ptrs=self.ptrs.data_ptr(), numel=self.numel.data_ptr(), chunk_tensor=self.ct.data_ptr(), chunk_off=self.co.data_ptr(),
+                 rows=self.nrows, n=self.n, nchunks=self.nchunks, chunk=CHUNK)
+        f.update(kw)
+        return _lib.ChunkTable(**f)
+
+
 def f32(x):
     """the double that a C `float` argument carries"""
     return float(np.float32(x))

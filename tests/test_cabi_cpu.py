@@ -3,6 +3,7 @@ validation paths that need no GPU; the config surface equals the reference DEFAU
 import ctypes
 import os
 import re
+import sys
 
 import pytest
 
@@ -144,8 +145,8 @@ def test_optional_parts_of_the_descriptors_validate_on_the_host():
     assert lib.vilco_attn_fwd(ctypes.byref(d), None) == -2
     # at most 8 parameter groups travel as kernel arguments
     lr = (ctypes.c_float * 9)()
-    d = _lib.OptimDesc(ptrs=x, numel=x, chunk_tensor=x, chunk_off=x, group=x, n=1, nchunks=1, chunk=1024, lr=ctypes.addressof(lr),
-                       wd=ctypes.addressof(lr), ngroups=9, tensor_step=x)
+    tb = _lib.ChunkTable(ptrs=x, numel=x, chunk_tensor=x, chunk_off=x, rows=4, n=1, nchunks=1, chunk=1024)
+    d = _lib.OptimDesc(table=tb, group=x, lr=ctypes.addressof(lr), wd=ctypes.addressof(lr), ngroups=9, tensor_step=x)
     assert lib.vilco_optim_step(ctypes.byref(d), None) == -1
     # LayerNorm backward: dgamma and dbeta come together or not at all
     d = _lib.LnBwdDesc(dy=x, x=x, mean=x, rstd=x, dx=x, dgamma=x, rows=64, C=64, workspace=x, workspace_bytes=1 << 40)
@@ -160,3 +161,48 @@ def test_struct_mirrors_have_the_size_the_compiler_gave_the_c_structs():
     for c in mirrors:
         assert ctypes.sizeof(c) == lib.vilco_abi_sizeof(c._cname_.encode()) > 0, c.__name__
     assert lib.vilco_abi_sizeof(b"vilco_no_such_struct") == 0
+
+
+def test_chunk_table_entry_points_validate_on_the_host():
+    """vilco_grad_norm and vilco_cl_penalty (the other three users of a vilco_chunk_table: test_importance_cpu.py,
+    test_si_cpu.py): a null table, null rows of it, bad counts and one row too few are refused before anything is launched"""
+    from vilco_amd import _lib
+    lib = _lib.load()
+    x = 4096
+    ok = dict(ptrs=x, numel=x, chunk_tensor=x, chunk_off=x, n=1, nchunks=1, chunk=1024)
+    calls = {"grad_norm": (2, lambda t: lib.vilco_grad_norm(t, 0.5, x, x, None)),
+             "cl_penalty": (4, lambda t: lib.vilco_cl_penalty(t, 0.37, 0, x, x, None))}
+    for name, (rows, call) in calls.items():
+        assert call(None) == -1, name
+        for bad in (dict(ptrs=None), dict(numel=None), dict(chunk_tensor=None), dict(chunk_off=None), dict(n=-1), dict(nchunks=-1),
+                    dict(chunk=0), dict(rows=rows - 1)):
+            assert call(ctypes.byref(_lib.ChunkTable(**dict(dict(ok, rows=rows), **bad)))) == -1, (name, bad)
+    tb = ctypes.byref(_lib.ChunkTable(rows=4, **ok))
+    assert lib.vilco_grad_norm(tb, 0.5, None, x, None) == -1 and lib.vilco_grad_norm(tb, 0.5, x, None, None) == -1
+    assert lib.vilco_cl_penalty(tb, 0.37, 0, None, x, None) == -1 and lib.vilco_cl_penalty(tb, 0.37, 0, x, None, None) == -1
+    assert ctypes.sizeof(_lib.ChunkTable) == lib.vilco_abi_sizeof(b"vilco_chunk_table") == 48
+    assert _lib.OptimDesc._fields_[0] == ("table", _lib.ChunkTable) and _lib.SiDesc._fields_[0] == ("table", _lib.ChunkTable)
+
+
+def test_chunk_plan_is_the_table_the_tests_build_by_hand():
+    """ops.ChunkPlan against tests/optim_restatement.py's own loop, at the chunk edges and for no tensors at all"""
+    import torch
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import optim_restatement as R
+    from vilco_amd import ops
+    from vilco_amd.cl_methods import regularizers
+    from vilco_amd.utils import train_utils
+    assert ops.CHUNK == R.CHUNK and ops.CL_CHUNK is ops.CHUNK and train_utils.CHUNK is ops.CHUNK and regularizers.CHUNK is ops.CHUNK
+    C = R.CHUNK
+    for numels in ([], [1, 3, 255, 256, 257, C - 1, C, C + 1, 2 * C + 5]):
+        ct, co, first = R.chunk_lists(numels)
+        plan = ops.ChunkPlan(numels, torch.device('cpu'))
+        assert (plan.n, plan.nchunks, plan.chunk, plan.first) == (len(numels), len(ct), C, first)
+        assert plan.numel.dtype == torch.int64 and plan.chunk_tensor.dtype == torch.int32 and plan.chunk_off.dtype == torch.int64
+        assert plan.numel.tolist() == (numels or [0]) and plan.chunk_tensor.tolist() == (ct or [0]) and plan.chunk_off.tolist() == (co or [0])
+        ptrs = torch.zeros(3, max(len(numels), 1), dtype=torch.int64)
+        t = plan.table(ptrs, 3)
+        assert (t.ptrs, t.numel, t.chunk_tensor, t.chunk_off) == (ptrs.data_ptr(), plan.numel.data_ptr(), plan.chunk_tensor.data_ptr(),
+                                                                   plan.chunk_off.data_ptr())
+        assert (t.rows, t.n, t.nchunks, t.chunk) == (3, len(numels), len(ct), C) and t.chunk_off
+    assert first == [0, 1, 2, 3, 4, 5, 6, 7, 9, 12] and co[-3:] == [0, C, 2 * C] and ct[-3:] == [8, 8, 8]

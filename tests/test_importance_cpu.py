@@ -1,12 +1,14 @@
 """EWC / MAS importance over the whole task and the online merge, without a GPU: the float64 restatement
 (tests/importance_restatement.py) against the reference-recorded consolidation goldens (tests/golden/cl_parts.pt), and the
 host-tensor path of `on_task_update` against the restatement; the argument checks of vilco_cl_accumulate."""
+import ctypes
 import os
 
 import pytest
 import torch
 
 from importance_restatement import GrowToy, RecordingSGD, importance, merge, toy_loader
+import optim_restatement as R
 from parity_util import HERE, cases, rel_err
 
 U = 2.0 ** -24          # one fp32 rounding, relative
@@ -221,13 +223,12 @@ def test_cl_accumulate_rejects_bad_arguments_without_a_gpu():
     from vilco_amd import _lib
     lib = _lib.load()
     x = 4096                                            # dummy addresses: every check precedes the launch
-    ok = dict(ptrs=x, numel=x, ct=x, co=x, n=1, nchunks=1, chunk=16384, op=1)
+    ok = dict(ptrs=x, numel=x, chunk_tensor=x, chunk_off=x, rows=2, n=1, nchunks=1, chunk=R.CHUNK)
 
-    def call(**kw):
-        a = dict(ok, **kw)
-        return lib.vilco_cl_accumulate(a['ptrs'], a['numel'], a['ct'], a['co'], a['n'], a['nchunks'], a['chunk'], a['op'],
-                                       1.0, 0.0, None)
-    for bad in (dict(ptrs=None), dict(numel=None), dict(ct=None), dict(co=None), dict(n=-1), dict(nchunks=-1), dict(chunk=0),
-                dict(chunk=-4), dict(op=-1), dict(op=3)):
+    def call(op=1, **kw):
+        return lib.vilco_cl_accumulate(ctypes.byref(_lib.ChunkTable(**dict(ok, **kw))), op, 1.0, 0.0, None)
+    for bad in (dict(ptrs=None), dict(numel=None), dict(chunk_tensor=None), dict(chunk_off=None), dict(n=-1), dict(nchunks=-1),
+                dict(chunk=0), dict(chunk=-4), dict(op=-1), dict(op=3), dict(rows=1)):
         assert call(**bad) == -1, bad
+    assert lib.vilco_cl_accumulate(None, 1, 1.0, 0.0, None) == -1
     assert call(nchunks=0) == 0 and call(n=0, nchunks=0) == 0          # nothing to do: no launch, OK

@@ -18,7 +18,7 @@ import torch
 import optim_restatement as R
 
 U = 2.0 ** -24
-CHUNK = 16384
+CHUNK = R.CHUNK
 pytestmark = pytest.mark.gpu
 
 SIZES_A = [1, 3, 63, 64, 65, 255, 256, 257, CHUNK - 1, CHUNK, CHUNK + 1, 2 * CHUNK + 5]
@@ -80,25 +80,9 @@ def _slots(dev, sizes, seed, stream, scale=1.0, fn=None):
     return out
 
 
-class Table:
-    """pointer rows [4][n], numel, chunk_tensor, chunk_off on the device, built the way FusedOptimizer._build_plan builds them"""
-
-    def __init__(self, dev, rows, numels):
-        self.rows, self.numels, self.n = rows, list(numels), len(numels)
-        ct, co, self.first = [], [], []
-        for i, n in enumerate(self.numels):
-            self.first.append(len(ct))
-            for off in range(0, n, CHUNK):
-                ct.append(i)
-                co.append(off)
-        self.first.append(len(ct))
-        self.nchunks = len(ct)
-        self.ptrs = torch.tensor([[s.view.data_ptr() for s in r] for r in rows] if self.n else [[0]] * 4, dtype=torch.int64).to(dev)
-        self.numel = torch.tensor(self.numels or [0], dtype=torch.int64).to(dev)
-        self.ct = torch.tensor(ct or [0], dtype=torch.int32).to(dev)
-        self.co = torch.tensor(co or [0], dtype=torch.int64).to(dev)
-        self.partial = torch.full((max(self.nchunks, 1),), float('nan'), device=dev)
-        self.dev = dev
+def Table(dev, rows, numels):
+    """R.Table over slot rows: the addresses are those of the misaligned views"""
+    return R.Table(dev, [[s.view.data_ptr() for s in r] for r in rows], numels)
 
 
 def _stream():
@@ -114,8 +98,7 @@ def _lib():
 def _grad_norm(tb, max_norm):
     L, lib = _lib()
     out = torch.full((2,), float('nan'), device=tb.dev)
-    L.check(lib.vilco_grad_norm(tb.ptrs.data_ptr(), tb.numel.data_ptr(), tb.ct.data_ptr(), tb.co.data_ptr(), tb.n, tb.nchunks,
-                                CHUNK, float(max_norm), tb.partial.data_ptr(), out.data_ptr(), _stream()))
+    L.check(lib.vilco_grad_norm(C.byref(tb.struct()), float(max_norm), tb.partial.data_ptr(), out.data_ptr(), _stream()))
     torch.cuda.synchronize()
     return out.cpu()
 
@@ -214,9 +197,8 @@ class StepCase:
         tb = self.table
         lr, wd = (C.c_float * 9)(*(list(lrs) + [0.0])), (C.c_float * 9)(*(WDS + [0.0]))
         kind = (0 if self.kind == "AdamW" else 1) if kind is None else kind
-        d = L.OptimDesc(kind=kind, ptrs=tb.ptrs.data_ptr(), numel=tb.numel.data_ptr(), chunk_tensor=tb.ct.data_ptr(),
-                        chunk_off=tb.co.data_ptr(), group=self.tgroup.data_ptr(), n=tb.n, nchunks=tb.nchunks, chunk=CHUNK,
-                        lr=C.addressof(lr), wd=C.addressof(wd), ngroups=ngroups, beta1=BETA1, beta2=BETA2, eps=EPS, momentum=MOM,
+        d = L.OptimDesc(table=tb.struct(), kind=kind, group=self.tgroup.data_ptr(), lr=C.addressof(lr), wd=C.addressof(wd),
+                        ngroups=ngroups, beta1=BETA1, beta2=BETA2, eps=EPS, momentum=MOM,
                         tensor_step=self.tstep.data_ptr(), norm_coef=None if coef is None else coef.data_ptr(),
                         chunk_amax=self.amax.data_ptr(), lr_dev=None if lr_dev is None else lr_dev.data_ptr())
         try:
@@ -363,8 +345,8 @@ class PenaltyCase:
         L, lib = _lib()
         tb = self.table
         out = torch.full((1,), float('nan'), device=self.dev)
-        L.check(lib.vilco_cl_penalty(tb.ptrs.data_ptr(), tb.numel.data_ptr(), tb.ct.data_ptr(), tb.co.data_ptr(), tb.n, tb.nchunks,
-                                     CHUNK, float(lam), int(shared), tb.partial.data_ptr(), out.data_ptr(), _stream()))
+        L.check(lib.vilco_cl_penalty(C.byref(tb.struct()), float(lam), int(shared), tb.partial.data_ptr(), out.data_ptr(),
+                                     _stream()))
         torch.cuda.synchronize()
         return float(out[0])
 

@@ -119,14 +119,20 @@ def test_resume_inside_a_task_is_refused():
 FAKE = 4096          # a non-null address: every check below fails before anything is dereferenced or launched
 
 
+def _table(rows, kw):
+    """a vilco_chunk_table of one tensor and one chunk over FAKE addresses; takes its fields out of `kw`"""
+    from vilco_amd import _lib
+    d = dict(ptrs=FAKE, numel=FAKE, chunk_tensor=FAKE, chunk_off=FAKE, rows=rows, n=1, nchunks=1, chunk=S.R.CHUNK)
+    d.update({k: kw.pop(k) for k in list(kw) if k in d})
+    return _lib.ChunkTable(**d)
+
+
 def test_si_consolidate_rejects_bad_arguments_without_a_gpu():
     from vilco_amd import _lib
     lib = _lib.load()
 
     def desc(**kw):
-        d = dict(ptrs=FAKE, numel=FAKE, numel_old=FAKE, chunk_tensor=FAKE, chunk_off=FAKE, n=1, nchunks=1, chunk=16384, xi=0.1)
-        d.update(kw)
-        return _lib.SiDesc(**d)
+        return _lib.SiDesc(table=_table(5, kw), numel_old=kw.pop('numel_old', FAKE), xi=kw.pop('xi', 0.1), **kw)
     assert lib.vilco_si_consolidate(None, None) == -1
     for table in ('ptrs', 'numel', 'numel_old', 'chunk_tensor', 'chunk_off'):
         assert lib.vilco_si_consolidate(ctypes.byref(desc(**{table: None})), None) == -1, table
@@ -136,6 +142,7 @@ def test_si_consolidate_rejects_bad_arguments_without_a_gpu():
         assert lib.vilco_si_consolidate(ctypes.byref(desc(n=n)), None) == -1, n
     assert lib.vilco_si_consolidate(ctypes.byref(desc(chunk=0)), None) == -1
     assert lib.vilco_si_consolidate(ctypes.byref(desc(nchunks=-1)), None) == -1
+    assert lib.vilco_si_consolidate(ctypes.byref(desc(rows=4)), None) == -1            # reads five rows
     assert lib.vilco_si_consolidate(ctypes.byref(desc(nchunks=0)), None) == 0          # nothing to do, nothing launched
 
 
@@ -145,16 +152,16 @@ def test_optim_step_with_si_rejects_bad_arguments_without_a_gpu():
     lr = (ctypes.c_float * 1)(1e-3)
 
     def desc(**kw):
-        d = dict(kind=0, ptrs=FAKE, numel=FAKE, chunk_tensor=FAKE, chunk_off=FAKE, group=FAKE, n=1, nchunks=1, chunk=16384,
-                 lr=ctypes.addressof(lr), wd=ctypes.addressof(lr), ngroups=1, beta1=0.9, beta2=0.999, eps=1e-8, momentum=0.9,
-                 tensor_step=FAKE, si_ptrs=FAKE)
+        d = dict(table=_table(4, kw), kind=0, group=FAKE, lr=ctypes.addressof(lr), wd=ctypes.addressof(lr), ngroups=1, beta1=0.9,
+                 beta2=0.999, eps=1e-8, momentum=0.9, tensor_step=FAKE, si_ptrs=FAKE)
         d.update(kw)
         return _lib.OptimDesc(**d)
     assert lib.vilco_optim_step(None, None) == -1
     for bad in (dict(ptrs=None), dict(numel=None), dict(group=None), dict(tensor_step=None), dict(n=-1), dict(chunk=0),
-                dict(kind=2), dict(ngroups=0)):
+                dict(kind=2), dict(ngroups=0), dict(rows=3), dict(kind=1, rows=2)):       # AdamW reads four rows, SGD three
         assert lib.vilco_optim_step(ctypes.byref(desc(**bad)), None) == -1, bad
     assert lib.vilco_optim_step(ctypes.byref(desc(nchunks=0)), None) == 0
+    assert lib.vilco_optim_step(ctypes.byref(desc(kind=1, rows=3, nchunks=0)), None) == 0
     assert ctypes.sizeof(_lib.OptimDesc) == lib.vilco_abi_sizeof(b"vilco_optim_desc")
     assert ctypes.sizeof(_lib.SiDesc) == lib.vilco_abi_sizeof(b"vilco_si_desc") > 0
     assert _lib.OptimDesc._fields_[-1][0] == "si_ptrs"              # appended: older callers' descriptors stay a prefix

@@ -25,7 +25,7 @@ import si_restatement as S
 
 R = S.R
 U = 2.0 ** -24
-CHUNK = 16384
+CHUNK = R.CHUNK
 pytestmark = pytest.mark.gpu
 
 SIZES = [1, 3, 255, 256, 257, CHUNK - 1, CHUNK, CHUNK + 1, 2 * CHUNK + 5]
@@ -85,15 +85,6 @@ def _slots(dev, seed, stream, scale=1.0, fn=None, sizes=SIZES):
     return out
 
 
-def _chunks(numels, dev):
-    ct, co = [], []
-    for i, n in enumerate(numels):
-        for off in range(0, n, CHUNK):
-            ct.append(i)
-            co.append(off)
-    return torch.tensor(ct, dtype=torch.int32).to(dev), torch.tensor(co, dtype=torch.int64).to(dev), len(ct)
-
-
 def _stream():
     return torch.cuda.current_stream().cuda_stream
 
@@ -121,20 +112,17 @@ class StepCase:
                         self.m[i].view.fill_(float('nan'))       # first step: the buffer is not read
         for s in self.p + self.m + self.v:
             s.snap()
-        self.rows = torch.tensor([[s.view.data_ptr() for s in r] for r in (self.p, self.g, self.m, self.v)], dtype=torch.int64).to(dev)
-        self.numel = torch.tensor(SIZES, dtype=torch.int64).to(dev)
-        self.ct, self.co, self.nchunks = _chunks(SIZES, dev)
+        self.table = R.Table(dev, [[s.view.data_ptr() for s in r] for r in (self.p, self.g, self.m, self.v)], SIZES)
         self.tstep = torch.tensor(self.steps, dtype=torch.float32).to(dev)
         self.tgroup = torch.tensor(self.group, dtype=torch.int32).to(dev)
-        self.amax = torch.zeros(self.nchunks, device=dev)
+        self.amax = torch.zeros(self.table.nchunks, device=dev)
         self.si = torch.tensor([0 if i == NO_OMEGA else s.view.data_ptr() for i, s in enumerate(self.om)], dtype=torch.int64).to(dev)
 
     def run(self, coef, with_si):
         L, lib = _lib()
         lr, wd = (C.c_float * 3)(*LRS), (C.c_float * 3)(*WDS)
-        d = L.OptimDesc(kind=0 if self.kind == "AdamW" else 1, ptrs=self.rows.data_ptr(), numel=self.numel.data_ptr(),
-                        chunk_tensor=self.ct.data_ptr(), chunk_off=self.co.data_ptr(), group=self.tgroup.data_ptr(), n=len(SIZES),
-                        nchunks=self.nchunks, chunk=CHUNK, lr=C.addressof(lr), wd=C.addressof(wd), ngroups=self.ngroups,
+        d = L.OptimDesc(table=self.table.struct(), kind=0 if self.kind == "AdamW" else 1, group=self.tgroup.data_ptr(),
+                        lr=C.addressof(lr), wd=C.addressof(wd), ngroups=self.ngroups,
                         beta1=BETA1, beta2=BETA2, eps=EPS, momentum=MOM, tensor_step=self.tstep.data_ptr(),
                         norm_coef=None if coef is None else coef.data_ptr(), chunk_amax=self.amax.data_ptr(), lr_dev=None,
                         si_ptrs=self.si.data_ptr() if with_si else None)
@@ -201,12 +189,9 @@ def test_step_kernels_take_the_path_integral(dev, kind, ngroups, clip):
 # ------------------------------------------------------------------------------------------------- the consolidation
 def _consolidate(dev, rows, numels, numel_old, xi):
     L, lib = _lib()
-    ptrs = torch.tensor([[s.view.data_ptr() for s in r] for r in rows], dtype=torch.int64).to(dev)
-    t_n = torch.tensor(numels, dtype=torch.int64).to(dev)
+    tb = R.Table(dev, [[s.view.data_ptr() for s in r] for r in rows], numels)
     t_o = torch.tensor(numel_old, dtype=torch.int64).to(dev)
-    ct, co, nchunks = _chunks(numels, dev)
-    d = L.SiDesc(ptrs=ptrs.data_ptr(), numel=t_n.data_ptr(), numel_old=t_o.data_ptr(), chunk_tensor=ct.data_ptr(),
-                 chunk_off=co.data_ptr(), n=len(numels), nchunks=nchunks, chunk=CHUNK, xi=xi)
+    d = L.SiDesc(table=tb.struct(), numel_old=t_o.data_ptr(), xi=xi)
     try:
         L.check(lib.vilco_si_consolidate(C.byref(d), _stream()))
     finally:

@@ -122,6 +122,7 @@ def test_optimizer_leaves_weight_amax_for_the_packs(dev, kind):
     from vilco_amd.utils.train_utils import FusedOptimizer
     torch.manual_seed(3)
     shapes = [(1024, 512), (70,), (96, 40, 3), (3, 5)]
+    from optim_restatement import CHUNK
     ps = [(torch.randn(s) * (10.0 ** i)).to(dev).requires_grad_(True) for i, s in enumerate(shapes)]
     with warnings.catch_warnings():
         warnings.simplefilter("ignore")
@@ -137,7 +138,7 @@ def test_optimizer_leaves_weight_amax_for_the_packs(dev, kind):
                 assert tag is None
                 continue
             parts, n = ops._weight_amax(p)
-            assert n == -(-p.numel() // 16384) and parts.numel() == n
+            assert n == -(-p.numel() // CHUNK) and parts.numel() == n
             assert float(parts.max()) == float(p.detach().abs().max()), (step, tuple(p.shape))
         w = ps[0]
         rows, cols = w.shape

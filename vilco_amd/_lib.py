@@ -108,18 +108,22 @@ class ActBwdDesc(C.Structure):
                 ("row_mask", c_fp)]
 
 
+class ChunkTable(C.Structure):
+    _cname_ = "vilco_chunk_table"
+    _fields_ = [("ptrs", c_fp), ("numel", c_fp), ("chunk_tensor", c_fp), ("chunk_off", c_fp),
+                ("rows", i32), ("n", i32), ("nchunks", i32), ("chunk", i32)]
+
+
 class OptimDesc(C.Structure):
     _cname_ = "vilco_optim_desc"
-    _fields_ = [("kind", i32), ("ptrs", c_fp), ("numel", c_fp), ("chunk_tensor", c_fp), ("chunk_off", c_fp), ("group", c_fp),
-                ("n", i32), ("nchunks", i32), ("chunk", i32), ("lr", c_fp), ("wd", c_fp), ("ngroups", i32),
+    _fields_ = [("table", ChunkTable), ("kind", i32), ("group", c_fp), ("lr", c_fp), ("wd", c_fp), ("ngroups", i32),
                 ("beta1", f32), ("beta2", f32), ("eps", f32), ("momentum", f32), ("tensor_step", c_fp), ("norm_coef", c_fp),
                 ("chunk_amax", c_fp), ("lr_dev", c_fp), ("si_ptrs", c_fp)]
 
 
 class SiDesc(C.Structure):
     _cname_ = "vilco_si_desc"
-    _fields_ = [("ptrs", c_fp), ("numel", c_fp), ("numel_old", c_fp), ("chunk_tensor", c_fp), ("chunk_off", c_fp),
-                ("n", i32), ("nchunks", i32), ("chunk", i32), ("xi", f32)]
+    _fields_ = [("table", ChunkTable), ("numel_old", c_fp), ("xi", f32)]
 
 
 class DistillDesc(C.Structure):
@@ -206,7 +210,7 @@ SIGNATURES = {
     "vilco_add_pe": (C.c_int, [c_fp, c_fp, c_fp, c_fp, i32, i32, i32, c_fp]),
     "vilco_transpose2d": (C.c_int, [c_fp, c_fp, i32, i32, i32, c_fp]),
     "vilco_permute3": (C.c_int, [c_fp, c_fp, i32, i32, i32, i64, i64, i64, i64, c_fp]),
-    "vilco_grad_norm": (C.c_int, [c_fp, c_fp, c_fp, c_fp, i32, i32, i32, f32, c_fp, c_fp, c_fp]),
+    "vilco_grad_norm": (C.c_int, [C.POINTER(ChunkTable), f32, c_fp, c_fp, c_fp]),
     "vilco_optim_step": (C.c_int, [C.POINTER(OptimDesc), c_fp]),
     "vilco_si_consolidate": (C.c_int, [C.POINTER(SiDesc), c_fp]),
     "vilco_store_f32": (C.c_int, [c_fp, C.POINTER(f32), i32, c_fp]),
@@ -226,8 +230,8 @@ SIGNATURES = {
     "vilco_cl_distill_workspace": (sz, [i64]),
     "vilco_cl_distill_fwd": (C.c_int, [C.POINTER(DistillDesc), c_fp, c_fp, sz, c_fp]),
     "vilco_cl_distill_bwd": (C.c_int, [C.POINTER(DistillDesc), c_fp, c_fp, c_fp]),
-    "vilco_cl_penalty": (C.c_int, [c_fp, c_fp, c_fp, c_fp, i32, i32, i32, f32, i32, c_fp, c_fp, c_fp]),
-    "vilco_cl_accumulate": (C.c_int, [c_fp, c_fp, c_fp, c_fp, i32, i32, i32, i32, f32, f32, c_fp]),
+    "vilco_cl_penalty": (C.c_int, [C.POINTER(ChunkTable), f32, i32, c_fp, c_fp, c_fp]),
+    "vilco_cl_accumulate": (C.c_int, [C.POINTER(ChunkTable), i32, f32, f32, c_fp]),
     "vilco_nms_workspace": (sz, [i64, i32]),
     "vilco_nms_1d": (C.c_int, [c_fp, c_fp, c_fp, i32, i64, f32, c_fp, c_fp, c_fp, sz, c_fp]),
     "vilco_softnms_1d": (C.c_int, [c_fp, c_fp, c_fp, i32, i64, f32, f32, f32, i32, i64, c_fp, c_fp, c_fp,

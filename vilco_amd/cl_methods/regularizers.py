@@ -23,7 +23,7 @@ import torch
 
 from .. import _lib, ops
 
-CHUNK = 16384
+CHUNK = ops.CHUNK
 
 
 def _entries(model, kind):
@@ -59,23 +59,15 @@ def apply_penalty(model, reg_lambda, kind='ewc'):
         if not (p.is_contiguous() and p.grad.is_contiguous() and imp.is_contiguous() and opt.is_contiguous()
                 and imp.is_cuda and opt.is_cuda and imp.dtype == torch.float32):
             raise RuntimeError("vilco_cl_penalty needs contiguous fp32 tensors on the HIP device")
-    numel = [opt.numel() for _, _, opt in items]                 # prefix of the (possibly grown) parameter
-    ct, co = [], []
-    for i, n in enumerate(numel):
-        for off in range(0, n, CHUNK):
-            ct.append(i)
-            co.append(off)
     ptrs = torch.tensor([[p.data_ptr() for p, _, _ in items], [p.grad.data_ptr() for p, _, _ in items],
                          [imp.data_ptr() for _, imp, _ in items], [opt.data_ptr() for _, _, opt in items]],
                         dtype=torch.int64).to(dev, non_blocking=True)
-    t_numel = torch.tensor(numel, dtype=torch.int64).to(dev, non_blocking=True)
-    t_ct = torch.tensor(ct, dtype=torch.int32).to(dev, non_blocking=True)
-    t_co = torch.tensor(co, dtype=torch.int64).to(dev, non_blocking=True)
-    partial = torch.empty(max(len(ct), 1), dtype=torch.float32, device=dev)
+    # numel = optpar's: a prefix of the (possibly grown) parameter.  Rebuilt on every call.
+    plan = ops.ChunkPlan([opt.numel() for _, _, opt in items], dev, non_blocking=True)
+    partial = torch.empty(max(plan.nchunks, 1), dtype=torch.float32, device=dev)
     out = torch.empty(1, dtype=torch.float32, device=dev)
-    _lib.check(lib.vilco_cl_penalty(ptrs.data_ptr(), t_numel.data_ptr(), t_ct.data_ptr(), t_co.data_ptr(), len(items),
-                                    len(ct), CHUNK, float(reg_lambda), int(len({id(p) for p, _, _ in items}) < len(items)),
-                                    partial.data_ptr(), out.data_ptr(),
+    _lib.check(lib.vilco_cl_penalty(ctypes.byref(plan.table(ptrs, 4)), float(reg_lambda),
+                                    int(len({id(p) for p, _, _ in items}) < len(items)), partial.data_ptr(), out.data_ptr(),
                                     torch.cuda.current_stream().cuda_stream))
     return out[0]
 
@@ -297,18 +289,10 @@ def on_task_si_update(model, optimizer=None, xi=SI_XI):
         numel_old.append(n_old)
     if rows:
         dev = next(iter(imp_d.values())).device
-        ct, co = [], []
-        for i, n in enumerate(numel):
-            for off in range(0, n, CHUNK):
-                ct.append(i)
-                co.append(off)
         ptrs = torch.tensor([list(col) for col in zip(*rows)], dtype=torch.int64).to(dev)
-        t_numel = torch.tensor(numel, dtype=torch.int64).to(dev)
+        plan = ops.ChunkPlan(numel, dev)
         t_old = torch.tensor(numel_old, dtype=torch.int64).to(dev)
-        t_ct = torch.tensor(ct or [0], dtype=torch.int32).to(dev)
-        t_co = torch.tensor(co or [0], dtype=torch.int64).to(dev)
-        d = _lib.SiDesc(ptrs=ptrs.data_ptr(), numel=t_numel.data_ptr(), numel_old=t_old.data_ptr(), chunk_tensor=t_ct.data_ptr(),
-                        chunk_off=t_co.data_ptr(), n=len(rows), nchunks=len(ct), chunk=CHUNK, xi=float(xi))
+        d = _lib.SiDesc(table=plan.table(ptrs, 5), numel_old=t_old.data_ptr(), xi=float(xi))
         _lib.check(_lib.load().vilco_si_consolidate(ctypes.byref(d), torch.cuda.current_stream().cuda_stream))
     reg['importance'], reg['optpar'] = [imp_d], [opt_d]
     return reg

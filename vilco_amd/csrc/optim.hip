@@ -9,33 +9,47 @@ namespace {
 
 constexpr int OPT_THREADS = 256;
 
+// the device's copy of a vilco_chunk_table (layout: include/vilco_hip.h), made by table_args() below
 struct MultiArgs {
-  const long* ptrs;          // [4][n]: param, grad, exp_avg (m), exp_avg_sq (v) device pointers
+  const long* ptrs;          // [rows][n] device pointers
   const long* numel;         // [n]
   const int* chunk_tensor;   // [nchunks]
   const long* chunk_off;     // [nchunks] element offset inside the tensor
-  const int* group;          // [n] parameter-group index
+  const int* group;          // [n] parameter-group index (the optimizer's; null elsewhere)
   int n, chunk;
 };
 
-__global__ __launch_bounds__(OPT_THREADS) void sqnorm_kernel(MultiArgs a, float* __restrict__ partial) {
-  __shared__ float red[OPT_THREADS / 64];
+// What block blockIdx.x walks: elements off .. off + cnt of tensor t, row<T>(k) = where they start in row k.  A chunk that lies
+// outside its tensor gets cnt = 0 and no early return: a kernel that owes a per-chunk partial still writes it.
+struct ChunkView {
+  const long* col;           // &ptrs[0][t]
+  long n;
+  int t;
+  long off, cnt;
+  template <typename T>
+  __device__ __forceinline__ T* row(int k) const { return reinterpret_cast<T*>(col[k * n]) + off; }
+};
+
+__device__ __forceinline__ ChunkView chunk_view(const MultiArgs& a) {
   const int t = a.chunk_tensor[blockIdx.x];
   const long off = a.chunk_off[blockIdx.x];
-  const float* g = reinterpret_cast<const float*>(a.ptrs[(long)a.n + t]) + off;
   long cnt = a.numel[t] - off;
   if (cnt > a.chunk) cnt = a.chunk;
-  float s = 0.f;
-  for (long i = threadIdx.x; i < cnt; i += OPT_THREADS) s += g[i] * g[i];
+  if (off < 0 || cnt < 0) cnt = 0;
+  return ChunkView{a.ptrs + t, (long)a.n, t, off, cnt};
+}
+
+// *dst = the block's sum of s: wave sums, then (r0 + r1) + (r2 + r3)
+__device__ __forceinline__ void block_sum_to(float s, float* __restrict__ dst) {
+  __shared__ float red[OPT_THREADS / 64];
   s = wave_sum(s);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
   __syncthreads();
-  if (threadIdx.x == 0) partial[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+  if (threadIdx.x == 0) *dst = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
-// out[0] = total L2 norm, out[1] = clip coefficient min(1, max_norm / (norm + 1e-6))   (max_norm <= 0: coef 1)
-__global__ __launch_bounds__(OPT_THREADS) void clip_coef_kernel(const float* __restrict__ partial, int n,
-                                                                float max_norm, float* __restrict__ out) {
+// sum of partial[0..n) in double over ONE block of OPT_THREADS threads: strided per-thread sums, then a halving tree
+__device__ __forceinline__ double partials_sum(const float* __restrict__ partial, int n) {
   __shared__ double red[OPT_THREADS];
   double s = 0.0;
   for (int i = threadIdx.x; i < n; i += OPT_THREADS) s += (double)partial[i];
@@ -45,8 +59,23 @@ __global__ __launch_bounds__(OPT_THREADS) void clip_coef_kernel(const float* __r
     if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
     __syncthreads();
   }
+  return red[0];
+}
+
+__global__ __launch_bounds__(OPT_THREADS) void sqnorm_kernel(MultiArgs a, float* __restrict__ partial) {
+  const ChunkView c = chunk_view(a);
+  const float* g = c.row<const float>(1);
+  float s = 0.f;
+  for (long i = threadIdx.x; i < c.cnt; i += OPT_THREADS) s += g[i] * g[i];
+  block_sum_to(s, partial + blockIdx.x);
+}
+
+// out[0] = total L2 norm, out[1] = clip coefficient min(1, max_norm / (norm + 1e-6))   (max_norm <= 0: coef 1)
+__global__ __launch_bounds__(OPT_THREADS) void clip_coef_kernel(const float* __restrict__ partial, int n,
+                                                                float max_norm, float* __restrict__ out) {
+  const double total = partials_sum(partial, n);
   if (threadIdx.x == 0) {
-    const float norm = (float)sqrt(red[0]);
+    const float norm = (float)sqrt(total);
     out[0] = norm;
     float c = 1.f;
     if (max_norm > 0.f) {
@@ -55,6 +84,13 @@ __global__ __launch_bounds__(OPT_THREADS) void clip_coef_kernel(const float* __r
     }
     out[1] = c;
   }
+}
+
+// out[0] = scale * sum of the partials
+__global__ __launch_bounds__(OPT_THREADS) void scaled_sum_kernel(const float* __restrict__ partial, int n, float scale,
+                                                                 float* __restrict__ out) {
+  const double total = partials_sum(partial, n);
+  if (threadIdx.x == 0) out[0] = (float)(total * (double)scale);
 }
 
 struct Hyper {
@@ -88,14 +124,13 @@ __device__ __forceinline__ void emit_chunk_amax(float mx, float* __restrict__ ch
 template <bool SI>
 __global__ __launch_bounds__(OPT_THREADS) void adamw_kernel(MultiArgs a, Hyper h, const float* __restrict__ coef,
                                                             float* __restrict__ chunk_amax, const long* __restrict__ si_ptrs) {
-  const int t = a.chunk_tensor[blockIdx.x];
-  const long off = a.chunk_off[blockIdx.x];
-  float* p = reinterpret_cast<float*>(a.ptrs[t]) + off;
-  const float* g = reinterpret_cast<const float*>(a.ptrs[(long)a.n + t]) + off;
-  float* m = reinterpret_cast<float*>(a.ptrs[2L * a.n + t]) + off;
-  float* v = reinterpret_cast<float*>(a.ptrs[3L * a.n + t]) + off;
-  long cnt = a.numel[t] - off;
-  if (cnt > a.chunk) cnt = a.chunk;
+  const ChunkView cv = chunk_view(a);
+  const int t = cv.t;
+  const long cnt = cv.cnt;
+  float* p = cv.row<float>(0);
+  const float* g = cv.row<const float>(1);
+  float* m = cv.row<float>(2);
+  float* v = cv.row<float>(3);
   const int gi = a.group[t];
   const float lr = h.lr_dev ? h.lr_dev[gi] : h.lr[gi], wd = h.wd[gi];
   const float c = coef ? coef[1] : 1.f;
@@ -107,7 +142,7 @@ __global__ __launch_bounds__(OPT_THREADS) void adamw_kernel(MultiArgs a, Hyper h
   float* om = nullptr;
   if constexpr (SI) {
     const long oa = si_ptrs[t];
-    if (oa) om = reinterpret_cast<float*>(oa) + off;
+    if (oa) om = reinterpret_cast<float*>(oa) + cv.off;
   }
   float mx = 0.f;
   for (long i = threadIdx.x; i < cnt; i += OPT_THREADS) {
@@ -144,13 +179,12 @@ __global__ __launch_bounds__(OPT_THREADS) void adamw_kernel(MultiArgs a, Hyper h
 template <bool SI>
 __global__ __launch_bounds__(OPT_THREADS) void sgd_kernel(MultiArgs a, Hyper h, const float* __restrict__ coef,
                                                           float* __restrict__ chunk_amax, const long* __restrict__ si_ptrs) {
-  const int t = a.chunk_tensor[blockIdx.x];
-  const long off = a.chunk_off[blockIdx.x];
-  float* p = reinterpret_cast<float*>(a.ptrs[t]) + off;
-  const float* g = reinterpret_cast<const float*>(a.ptrs[(long)a.n + t]) + off;
-  float* m = reinterpret_cast<float*>(a.ptrs[2L * a.n + t]) + off;
-  long cnt = a.numel[t] - off;
-  if (cnt > a.chunk) cnt = a.chunk;
+  const ChunkView cv = chunk_view(a);
+  const int t = cv.t;
+  const long cnt = cv.cnt;
+  float* p = cv.row<float>(0);
+  const float* g = cv.row<const float>(1);
+  float* m = cv.row<float>(2);
   const int gi = a.group[t];
   const float lr = h.lr_dev ? h.lr_dev[gi] : h.lr[gi], wd = h.wd[gi];
   const float c = coef ? coef[1] : 1.f;
@@ -158,7 +192,7 @@ __global__ __launch_bounds__(OPT_THREADS) void sgd_kernel(MultiArgs a, Hyper h, 
   float* om = nullptr;
   if constexpr (SI) {
     const long oa = si_ptrs[t];
-    if (oa) om = reinterpret_cast<float*>(oa) + off;
+    if (oa) om = reinterpret_cast<float*>(oa) + cv.off;
   }
   float mx = 0.f;
   for (long i = threadIdx.x; i < cnt; i += OPT_THREADS) {
@@ -188,59 +222,29 @@ __global__ __launch_bounds__(OPT_THREADS) void sgd_kernel(MultiArgs a, Hyper h, 
 // consolidated value) triples: partial[chunk] = sum F (opt - p)^2 ; grad += -2 lambda F (opt - p).
 // The added term is formed in double and rounded once (the kernels are bound by their five streams, not by arithmetic), so an
 // element's gradient carries one rounding per add and one for the term: independent of the order atomics arrive in.
-// ptrs = [4][n]: param, grad, importance, optpar; numel[t] = optpar's element count (a prefix of the parameter when the
-// class head has grown since the task was consolidated).
+// rows: param, grad, importance, optpar; numel[t] = optpar's element count (a prefix of the parameter when the class head has
+// grown).  ATOMIC: a parameter appears in more than one task's dictionary, so its gradient is accumulated with atomics.
+template <bool ATOMIC>
 __global__ __launch_bounds__(OPT_THREADS) void cl_penalty_kernel(MultiArgs a, float lambda, float* __restrict__ partial) {
-  __shared__ float red[OPT_THREADS / 64];
-  const int t = a.chunk_tensor[blockIdx.x];
-  const long off = a.chunk_off[blockIdx.x];
-  const float* p = reinterpret_cast<const float*>(a.ptrs[t]) + off;
-  float* g = reinterpret_cast<float*>(a.ptrs[(long)a.n + t]) + off;
-  const float* f = reinterpret_cast<const float*>(a.ptrs[2L * a.n + t]) + off;
-  const float* o = reinterpret_cast<const float*>(a.ptrs[3L * a.n + t]) + off;
-  long cnt = a.numel[t] - off;
-  if (cnt > a.chunk) cnt = a.chunk;
+  const ChunkView c = chunk_view(a);
+  const float* p = c.row<const float>(0);
+  float* g = c.row<float>(1);
+  const float* f = c.row<const float>(2);
+  const float* o = c.row<const float>(3);
   float s = 0.f;
-  for (long i = threadIdx.x; i < cnt; i += OPT_THREADS) {
+  for (long i = threadIdx.x; i < c.cnt; i += OPT_THREADS) {
     const double d = (double)o[i] - (double)p[i];
     const double fd = (double)f[i] * d;
     s += (float)(fd * d);
-    g[i] = (float)((double)g[i] - 2.0 * (double)lambda * fd);      // every parameter occurs once: plain read-modify-write
+    if constexpr (ATOMIC) atomicAdd(&g[i], (float)(-2.0 * (double)lambda * fd));
+    else g[i] = (float)((double)g[i] - 2.0 * (double)lambda * fd);      // every parameter occurs once: plain read-modify-write
   }
-  s = wave_sum(s);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) partial[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
-}
-
-// the same, for a parameter that appears in more than one task's dictionary: gradient accumulated with atomics
-__global__ __launch_bounds__(OPT_THREADS) void cl_penalty_atomic_kernel(MultiArgs a, float lambda,
-                                                                        float* __restrict__ partial) {
-  __shared__ float red[OPT_THREADS / 64];
-  const int t = a.chunk_tensor[blockIdx.x];
-  const long off = a.chunk_off[blockIdx.x];
-  const float* p = reinterpret_cast<const float*>(a.ptrs[t]) + off;
-  float* g = reinterpret_cast<float*>(a.ptrs[(long)a.n + t]) + off;
-  const float* f = reinterpret_cast<const float*>(a.ptrs[2L * a.n + t]) + off;
-  const float* o = reinterpret_cast<const float*>(a.ptrs[3L * a.n + t]) + off;
-  long cnt = a.numel[t] - off;
-  if (cnt > a.chunk) cnt = a.chunk;
-  float s = 0.f;
-  for (long i = threadIdx.x; i < cnt; i += OPT_THREADS) {
-    const double d = (double)o[i] - (double)p[i];
-    const double fd = (double)f[i] * d;
-    s += (float)(fd * d);
-    atomicAdd(&g[i], (float)(-2.0 * (double)lambda * fd));
-  }
-  s = wave_sum(s);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) partial[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+  block_sum_to(s, partial + blockIdx.x);
 }
 
 // Importance accumulation of the consolidation pass (MQ/libs/cl_methods/EWC.py:24-56, MAS.py:23-57, summed over the task's
 // batches instead of keeping the last one): acc = beta * acc + alpha * f(src), f = x | x^2 | |x|, over a chunk table of
-// (src, acc) pairs.  ptrs = [2][n]: src, acc; numel[t] = elements to touch (a prefix of acc when the class head has grown).
+// (src, acc) pairs.  rows: src, acc; numel[t] = elements to touch (a prefix of acc when the class head has grown).
 // Pure streaming, one owner thread per element.  beta == 0: acc is not read; alpha == 0: src is not read.
 template <int OP>
 __device__ __forceinline__ float cl_acc_value(float a, float x, float alpha, float beta, bool rd_src, bool rd_acc) {
@@ -261,13 +265,10 @@ __device__ __forceinline__ void cl_acc_scalar(const float* src, float* acc, long
 
 template <int OP>
 __global__ __launch_bounds__(OPT_THREADS) void cl_accumulate_kernel(MultiArgs a, float alpha, float beta) {
-  const int t = a.chunk_tensor[blockIdx.x];
-  const long off = a.chunk_off[blockIdx.x];
-  const float* src = reinterpret_cast<const float*>(a.ptrs[t]) + off;
-  float* acc = reinterpret_cast<float*>(a.ptrs[(long)a.n + t]) + off;
-  long cnt = a.numel[t] - off;
-  if (cnt > a.chunk) cnt = a.chunk;
-  if (off < 0 || cnt <= 0) return;
+  const ChunkView c = chunk_view(a);
+  const long cnt = c.cnt;
+  const float* src = c.row<const float>(0);
+  float* acc = c.row<float>(1);
   const bool rd_src = alpha != 0.f, rd_acc = beta != 0.f;
   // 16-byte accesses over the part where BOTH streams are 16-byte aligned: that needs the same misalignment on both (tensor
   // base pointers are arbitrary); then a scalar head of up to 3 elements, the wide body, a scalar tail.  Otherwise all scalar.
@@ -296,22 +297,18 @@ __global__ __launch_bounds__(OPT_THREADS) void cl_accumulate_kernel(MultiArgs a,
 
 // End of a task under Synaptic Intelligence: the path integral becomes importance, in place, ONE launch over all tensors.
 //   Omega = Omega_old + max(omega, 0) / ((p - theta_start)^2 + xi) ; optpar = p ; omega = 0 ; theta_start = p
-// ptrs = [5][n]: param, omega, theta_start, importance, optpar, each of numel[t] elements; importance held a value in its first
+// rows: param, omega, theta_start, importance, optpar, each of numel[t] elements; importance held a value in its first
 // numel_old[t] elements only (0: none yet; a prefix: the class head has grown), what lies behind them is not read.
 // The quotient and the sum are formed in double and rounded once.  One owner thread per element, five streams, no atomics.
 __global__ __launch_bounds__(OPT_THREADS) void si_consolidate_kernel(MultiArgs a, const long* __restrict__ numel_old, float xi) {
-  const int t = a.chunk_tensor[blockIdx.x];
-  const long off = a.chunk_off[blockIdx.x];
-  const float* p = reinterpret_cast<const float*>(a.ptrs[t]) + off;
-  float* om = reinterpret_cast<float*>(a.ptrs[(long)a.n + t]) + off;
-  float* ts = reinterpret_cast<float*>(a.ptrs[2L * a.n + t]) + off;
-  float* f = reinterpret_cast<float*>(a.ptrs[3L * a.n + t]) + off;
-  float* o = reinterpret_cast<float*>(a.ptrs[4L * a.n + t]) + off;
-  long cnt = a.numel[t] - off;
-  if (cnt > a.chunk) cnt = a.chunk;
-  if (off < 0 || cnt <= 0) return;
-  const long old = numel_old[t] - off;           // elements of this chunk that carry an earlier importance
-  for (long i = threadIdx.x; i < cnt; i += OPT_THREADS) {
+  const ChunkView c = chunk_view(a);
+  const float* p = c.row<const float>(0);
+  float* om = c.row<float>(1);
+  float* ts = c.row<float>(2);
+  float* f = c.row<float>(3);
+  float* o = c.row<float>(4);
+  const long old = numel_old[c.t] - c.off;       // elements of this chunk that carry an earlier importance
+  for (long i = threadIdx.x; i < c.cnt; i += OPT_THREADS) {
     const float pv = p[i];
     const double d = (double)pv - (double)ts[i];
     const double q = (double)fmaxf(om[i], 0.f) / (d * d + (double)xi);
@@ -322,23 +319,18 @@ __global__ __launch_bounds__(OPT_THREADS) void si_consolidate_kernel(MultiArgs a
   }
 }
 
-__global__ __launch_bounds__(OPT_THREADS) void scaled_sum_kernel(const float* __restrict__ partial, int n, float scale,
-                                                                 float* __restrict__ out) {
-  __shared__ double red[OPT_THREADS];
-  double s = 0.0;
-  for (int i = threadIdx.x; i < n; i += OPT_THREADS) s += (double)partial[i];
-  red[threadIdx.x] = s;
-  __syncthreads();
-  for (int o = OPT_THREADS / 2; o > 0; o >>= 1) {
-    if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) out[0] = (float)(red[0] * (double)scale);
-}
-
 struct F16Vals { float v[16]; };
 __global__ void store_f32_kernel(float* __restrict__ dst, F16Vals vals, int n) {
   if ((int)threadIdx.x < n) dst[threadIdx.x] = vals.v[threadIdx.x];
+}
+
+// the MultiArgs of a table whose entry point reads `rows` rows; false: VILCO_ERR_BADARG
+bool table_args(const vilco_chunk_table* t, int rows, const int32_t* group, MultiArgs* a) {
+  if (!t || !t->ptrs || !t->numel || !t->chunk_tensor || !t->chunk_off) return false;
+  if (t->n < 0 || t->nchunks < 0 || t->chunk <= 0 || t->rows < rows) return false;
+  *a = MultiArgs{reinterpret_cast<const long*>(t->ptrs), reinterpret_cast<const long*>(t->numel), t->chunk_tensor,
+                 reinterpret_cast<const long*>(t->chunk_off), group, t->n, t->chunk};
+  return true;
 }
 
 }  // namespace
@@ -354,47 +346,37 @@ extern "C" int vilco_store_f32(float* dst, const float* vals, int32_t n, void* s
   return vilco_launch_status();
 }
 
-extern "C" int vilco_cl_penalty(const int64_t* ptrs, const int64_t* numel, const int32_t* chunk_tensor,
-                                const int64_t* chunk_off, int32_t n, int32_t nchunks, int32_t chunk, float lambda,
-                                int32_t shared_params, float* partial, float* out, void* stream) {
-  if (!ptrs || !numel || !chunk_tensor || !chunk_off || !partial || !out || n < 0 || nchunks < 0 || chunk <= 0)
-    return VILCO_ERR_BADARG;
+extern "C" int vilco_cl_penalty(const vilco_chunk_table* table, float lambda, int32_t shared_params, float* partial, float* out,
+                                void* stream) {
+  MultiArgs a;
+  if (!table_args(table, 4, nullptr, &a) || !partial || !out) return VILCO_ERR_BADARG;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  MultiArgs a{reinterpret_cast<const long*>(ptrs), reinterpret_cast<const long*>(numel), chunk_tensor,
-              reinterpret_cast<const long*>(chunk_off), nullptr, n, chunk};
-  if (nchunks > 0) {
-    if (shared_params)
-      hipLaunchKernelGGL(cl_penalty_atomic_kernel, dim3(nchunks), dim3(OPT_THREADS), 0, s, a, lambda, partial);
-    else
-      hipLaunchKernelGGL(cl_penalty_kernel, dim3(nchunks), dim3(OPT_THREADS), 0, s, a, lambda, partial);
+  const dim3 grid(table->nchunks), block(OPT_THREADS);
+  if (table->nchunks > 0) {
+    if (shared_params) hipLaunchKernelGGL(cl_penalty_kernel<true>, grid, block, 0, s, a, lambda, partial);
+    else hipLaunchKernelGGL(cl_penalty_kernel<false>, grid, block, 0, s, a, lambda, partial);
   }
-  hipLaunchKernelGGL(scaled_sum_kernel, dim3(1), dim3(OPT_THREADS), 0, s, partial, nchunks, lambda, out);
+  hipLaunchKernelGGL(scaled_sum_kernel, dim3(1), block, 0, s, partial, table->nchunks, lambda, out);
   return vilco_launch_status();
 }
 
-extern "C" int vilco_cl_accumulate(const int64_t* ptrs, const int64_t* numel, const int32_t* chunk_tensor,
-                                   const int64_t* chunk_off, int32_t n, int32_t nchunks, int32_t chunk, int32_t op,
-                                   float alpha, float beta, void* stream) {
-  if (!ptrs || !numel || !chunk_tensor || !chunk_off || n < 0 || nchunks < 0 || chunk <= 0 || op < 0 || op > 2)
-    return VILCO_ERR_BADARG;
-  if (nchunks == 0) return VILCO_OK;
+extern "C" int vilco_cl_accumulate(const vilco_chunk_table* table, int32_t op, float alpha, float beta, void* stream) {
+  MultiArgs a;
+  if (!table_args(table, 2, nullptr, &a) || op < 0 || op > 2) return VILCO_ERR_BADARG;
+  if (table->nchunks == 0) return VILCO_OK;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  MultiArgs a{reinterpret_cast<const long*>(ptrs), reinterpret_cast<const long*>(numel), chunk_tensor,
-              reinterpret_cast<const long*>(chunk_off), nullptr, n, chunk};
-  if (op == 0) hipLaunchKernelGGL(cl_accumulate_kernel<0>, dim3(nchunks), dim3(OPT_THREADS), 0, s, a, alpha, beta);
-  else if (op == 1) hipLaunchKernelGGL(cl_accumulate_kernel<1>, dim3(nchunks), dim3(OPT_THREADS), 0, s, a, alpha, beta);
-  else hipLaunchKernelGGL(cl_accumulate_kernel<2>, dim3(nchunks), dim3(OPT_THREADS), 0, s, a, alpha, beta);
+  const dim3 grid(table->nchunks), block(OPT_THREADS);
+  if (op == 0) hipLaunchKernelGGL(cl_accumulate_kernel<0>, grid, block, 0, s, a, alpha, beta);
+  else if (op == 1) hipLaunchKernelGGL(cl_accumulate_kernel<1>, grid, block, 0, s, a, alpha, beta);
+  else hipLaunchKernelGGL(cl_accumulate_kernel<2>, grid, block, 0, s, a, alpha, beta);
   return vilco_launch_status();
 }
 
-extern "C" int vilco_grad_norm(const int64_t* ptrs, const int64_t* numel, const int32_t* chunk_tensor,
-                               const int64_t* chunk_off, int32_t n, int32_t nchunks, int32_t chunk, float max_norm,
-                               float* partial, float* norm_coef, void* stream) {
-  if (!ptrs || !numel || !chunk_tensor || !chunk_off || !partial || !norm_coef || n < 0 || nchunks < 0 || chunk <= 0)
-    return VILCO_ERR_BADARG;
+extern "C" int vilco_grad_norm(const vilco_chunk_table* table, float max_norm, float* partial, float* norm_coef, void* stream) {
+  MultiArgs a;
+  if (!table_args(table, 2, nullptr, &a) || !partial || !norm_coef) return VILCO_ERR_BADARG;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  MultiArgs a{reinterpret_cast<const long*>(ptrs), reinterpret_cast<const long*>(numel), chunk_tensor,
-              reinterpret_cast<const long*>(chunk_off), nullptr, n, chunk};
+  const int nchunks = table->nchunks;
   if (nchunks > 0) hipLaunchKernelGGL(sqnorm_kernel, dim3(nchunks), dim3(OPT_THREADS), 0, s, a, partial);
   hipLaunchKernelGGL(clip_coef_kernel, dim3(1), dim3(OPT_THREADS), 0, s, partial, nchunks, max_norm, norm_coef);
   return vilco_launch_status();
@@ -402,42 +384,34 @@ extern "C" int vilco_grad_norm(const int64_t* ptrs, const int64_t* numel, const 
 
 extern "C" int vilco_optim_step(const vilco_optim_desc* d, void* stream) {
   if (!d) return VILCO_ERR_BADARG;
-  const int64_t *ptrs = d->ptrs, *numel = d->numel, *chunk_off = d->chunk_off;
-  const int32_t *chunk_tensor = d->chunk_tensor, *group = d->group;
-  const int32_t kind = d->kind, n = d->n, nchunks = d->nchunks, chunk = d->chunk, ngroups = d->ngroups;
-  const float *lr = d->lr, *wd = d->wd, *tensor_step = d->tensor_step, *norm_coef = d->norm_coef, *lr_dev = d->lr_dev;
-  float* chunk_amax = d->chunk_amax;
-  if (!ptrs || !numel || !chunk_tensor || !chunk_off || !group || !lr || !wd || n < 0 || nchunks < 0 || chunk <= 0)
-    return VILCO_ERR_BADARG;
-  if (ngroups < 1 || ngroups > 8 || !tensor_step || (kind != 0 && kind != 1)) return VILCO_ERR_BADARG;
-  if (nchunks == 0) return VILCO_OK;
+  const int32_t kind = d->kind, ngroups = d->ngroups;
+  MultiArgs a;
+  if (!table_args(&d->table, kind == 1 ? 3 : 4, d->group, &a) || !d->group || !d->lr || !d->wd) return VILCO_ERR_BADARG;
+  if (ngroups < 1 || ngroups > 8 || !d->tensor_step || (kind != 0 && kind != 1)) return VILCO_ERR_BADARG;
+  if (d->table.nchunks == 0) return VILCO_OK;
   Hyper h;
-  for (int i = 0; i < 8; ++i) { h.lr[i] = i < ngroups ? lr[i] : 0.f; h.wd[i] = i < ngroups ? wd[i] : 0.f; }
+  for (int i = 0; i < 8; ++i) { h.lr[i] = i < ngroups ? d->lr[i] : 0.f; h.wd[i] = i < ngroups ? d->wd[i] : 0.f; }
   h.beta1 = d->beta1; h.beta2 = d->beta2; h.eps = d->eps;
   h.log_beta1 = (float)log((double)d->beta1); h.log_beta2 = (float)log((double)d->beta2);
   h.momentum = d->momentum;
-  h.tstep = tensor_step;
-  h.lr_dev = lr_dev;
-  MultiArgs a{reinterpret_cast<const long*>(ptrs), reinterpret_cast<const long*>(numel), chunk_tensor,
-              reinterpret_cast<const long*>(chunk_off), group, n, chunk};
+  h.tstep = d->tensor_step;
+  h.lr_dev = d->lr_dev;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const long* si = reinterpret_cast<const long*>(d->si_ptrs);
-  const dim3 grid(nchunks), block(OPT_THREADS);
-  if (kind == 0 && si) hipLaunchKernelGGL(adamw_kernel<true>, grid, block, 0, s, a, h, norm_coef, chunk_amax, si);
-  else if (kind == 0) hipLaunchKernelGGL(adamw_kernel<false>, grid, block, 0, s, a, h, norm_coef, chunk_amax, si);
-  else if (si) hipLaunchKernelGGL(sgd_kernel<true>, grid, block, 0, s, a, h, norm_coef, chunk_amax, si);
-  else hipLaunchKernelGGL(sgd_kernel<false>, grid, block, 0, s, a, h, norm_coef, chunk_amax, si);
+  const dim3 grid(d->table.nchunks), block(OPT_THREADS);
+  if (kind == 0 && si) hipLaunchKernelGGL(adamw_kernel<true>, grid, block, 0, s, a, h, d->norm_coef, d->chunk_amax, si);
+  else if (kind == 0) hipLaunchKernelGGL(adamw_kernel<false>, grid, block, 0, s, a, h, d->norm_coef, d->chunk_amax, si);
+  else if (si) hipLaunchKernelGGL(sgd_kernel<true>, grid, block, 0, s, a, h, d->norm_coef, d->chunk_amax, si);
+  else hipLaunchKernelGGL(sgd_kernel<false>, grid, block, 0, s, a, h, d->norm_coef, d->chunk_amax, si);
   return vilco_launch_status();
 }
 
 extern "C" int vilco_si_consolidate(const vilco_si_desc* d, void* stream) {
   if (!d) return VILCO_ERR_BADARG;
-  if (!d->ptrs || !d->numel || !d->numel_old || !d->chunk_tensor || !d->chunk_off) return VILCO_ERR_BADARG;
-  if (d->n <= 0 || d->nchunks < 0 || d->chunk <= 0 || !(d->xi > 0.f)) return VILCO_ERR_BADARG;
-  if (d->nchunks == 0) return VILCO_OK;
-  MultiArgs a{reinterpret_cast<const long*>(d->ptrs), reinterpret_cast<const long*>(d->numel), d->chunk_tensor,
-              reinterpret_cast<const long*>(d->chunk_off), nullptr, d->n, d->chunk};
-  hipLaunchKernelGGL(si_consolidate_kernel, dim3(d->nchunks), dim3(OPT_THREADS), 0, reinterpret_cast<hipStream_t>(stream), a,
+  MultiArgs a;
+  if (!table_args(&d->table, 5, nullptr, &a) || !d->numel_old || d->table.n <= 0 || !(d->xi > 0.f)) return VILCO_ERR_BADARG;
+  if (d->table.nchunks == 0) return VILCO_OK;
+  hipLaunchKernelGGL(si_consolidate_kernel, dim3(d->table.nchunks), dim3(OPT_THREADS), 0, reinterpret_cast<hipStream_t>(stream), a,
                      reinterpret_cast<const long*>(d->numel_old), d->xi);
   return vilco_launch_status();
 }

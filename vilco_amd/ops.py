@@ -2344,24 +2344,39 @@ def herd_select(grams, m):
     return sel
 
 
-# ---------------------------------------------------------------------------------------- EWC / MAS importance accumulation
-CL_CHUNK = 16384
-CL_OP_COPY, CL_OP_SQUARE, CL_OP_ABS = 0, 1, 2
-_cl_table = {}          # the last chunk table, by (numels, device): a consolidation pass asks for the same one every batch
+# ---------------------------------------------------------------------------------------- multi-tensor chunk tables
+CHUNK = 16384           # elements one block of a multi-tensor kernel walks (csrc/optim.hip)
 
 
-def _cl_chunks(numels, device):
-    key = (tuple(numels), device)
-    if key not in _cl_table:
-        ct, co = [], []
+class ChunkPlan:
+    """The host half of a vilco_chunk_table (include/vilco_hip.h) over tensors of `numels` elements: the device tensors `numel`,
+    `chunk_tensor`, `chunk_off` (uploaded in this order; an empty one is padded to one element, so its address is not null),
+    `nchunks`, and the host list `first` -- first[i] .. first[i + 1] are the chunks of tensor i.  `table(ptrs, rows)` adds the
+    [rows, n] pointer tensor of a call."""
+
+    def __init__(self, numels, device, chunk=CHUNK, non_blocking=False):
+        self.n, self.chunk = len(numels), chunk
+        ct, co, self.first = [], [], []
         for i, n in enumerate(numels):
-            for off in range(0, n, CL_CHUNK):
+            self.first.append(len(ct))
+            for off in range(0, n, chunk):
                 ct.append(i)
                 co.append(off)
-        _cl_table.clear()
-        _cl_table[key] = (torch.tensor(numels, dtype=torch.int64).to(device), torch.tensor(ct, dtype=torch.int32).to(device),
-                          torch.tensor(co, dtype=torch.int64).to(device))
-    return _cl_table[key]
+        self.first.append(len(ct))
+        self.nchunks = len(ct)
+        self.numel, self.chunk_tensor, self.chunk_off = (
+            torch.tensor(v or [0], dtype=dt).to(device, non_blocking=non_blocking)
+            for v, dt in ((list(numels), torch.int64), (ct, torch.int32), (co, torch.int64)))
+
+    def table(self, ptrs, rows):
+        return _lib.ChunkTable(ptrs=ptrs.data_ptr(), numel=self.numel.data_ptr(), chunk_tensor=self.chunk_tensor.data_ptr(),
+                               chunk_off=self.chunk_off.data_ptr(), rows=rows, n=self.n, nchunks=self.nchunks, chunk=self.chunk)
+
+
+# ---------------------------------------------------------------------------------------- EWC / MAS importance accumulation
+CL_CHUNK = CHUNK
+CL_OP_COPY, CL_OP_SQUARE, CL_OP_ABS = 0, 1, 2
+_cl_plan = {}           # the last ChunkPlan, by (numels, device): a consolidation pass asks for the same one every batch
 
 
 def cl_accumulate(srcs, accs, op, alpha, beta, numels=None):
@@ -2399,10 +2414,12 @@ def cl_accumulate(srcs, accs, op, alpha, beta, numels=None):
     _chk(*srcs)
     _chk(*accs)
     dev = accs[0].device
-    t_numel, t_ct, t_co = _cl_chunks(numels, dev)
+    key = (tuple(numels), dev)
+    if key not in _cl_plan:
+        _cl_plan.clear()
+        _cl_plan[key] = ChunkPlan(numels, dev)
     ptrs = torch.tensor([[s.data_ptr() for s in srcs], [a.data_ptr() for a in accs]], dtype=torch.int64).to(dev, non_blocking=True)
-    _lib.check(_lib.load().vilco_cl_accumulate(ptrs.data_ptr(), t_numel.data_ptr(), t_ct.data_ptr(), t_co.data_ptr(), len(accs),
-                                               int(t_ct.numel()), CL_CHUNK, int(op), alpha, beta, _stream()))
+    _lib.check(_lib.load().vilco_cl_accumulate(C.byref(_cl_plan[key].table(ptrs, 2)), int(op), alpha, beta, _stream()))
 
 
 # ---------------------------------------------------------------------------------------- BiC stage 2 over cached logits

@@ -18,7 +18,7 @@ from .. import _lib, ops
 from ..modeling.blocks import AffineDropPath, LayerNorm, MaskedConv1D, Scale
 from .lr_schedulers import LinearWarmupCosineAnnealingLR, LinearWarmupMultiStepLR
 
-CHUNK = 16384
+CHUNK = ops.CHUNK
 OPT_AMAX = os.environ.get("VILCO_OPT_AMAX", "1") != "0"      # the update kernels leave max|w| per chunk for the weight packs
 
 
@@ -117,16 +117,7 @@ class FusedOptimizer(optim.Optimizer):
         return passes, seen
 
     def _build_plan(self, k, items, occurrences):
-        numel = [p.numel() for p, _ in items]
-        ct, co, first = [], [], []
-        for i, n in enumerate(numel):
-            first.append(len(ct))
-            for off in range(0, n, CHUNK):
-                ct.append(i)
-                co.append(off)
-        first.append(len(ct))
         dev = items[0][0].device
-        amax = torch.empty(max(len(ct), 1), dtype=torch.float32, device=dev)
         inc = [float(occurrences[id(p)]) for p, _ in items]
         base = [float(self.state[p]['step']) for p, _ in items]
         # step count handed to the kernel = count AFTER this pass's increment: a parameter listed m times goes
@@ -140,13 +131,13 @@ class FusedOptimizer(optim.Optimizer):
         if self._si is not None:        # address of every tensor's omega in plan order, 0 = not regularised
             si = torch.tensor([self._si[id(p)][1].data_ptr() if id(p) in self._si else 0 for p, _ in items],
                               dtype=torch.int64, device=dev)
-        return dict(items=items, first=first, amax=amax, si=si,
-                    amax_views=[amax[first[i]:first[i + 1]] for i in range(len(numel))],
-                    numel=torch.tensor(numel, dtype=torch.int64, device=dev),
-                    chunk_tensor=torch.tensor(ct, dtype=torch.int32, device=dev),
-                    chunk_off=torch.tensor(co, dtype=torch.int64, device=dev),
+        chunks = ops.ChunkPlan([p.numel() for p, _ in items], dev)
+        first = chunks.first
+        amax = torch.empty(max(chunks.nchunks, 1), dtype=torch.float32, device=dev)
+        return dict(items=items, chunks=chunks, first=first, amax=amax, si=si,
+                    amax_views=[amax[first[i]:first[i + 1]] for i in range(len(items))],
                     group=torch.tensor([gi for _, gi in items], dtype=torch.int32, device=dev),
-                    partial=torch.empty(max(len(ct), 1), dtype=torch.float32, device=dev), nchunks=len(ct),
+                    partial=torch.empty(max(chunks.nchunks, 1), dtype=torch.float32, device=dev),
                     tstep=torch.tensor(tstep0, dtype=torch.float32, device=dev),
                     inc=None if uniform else torch.tensor(inc, dtype=torch.float32, device=dev),
                     inc_host=inc, base=base, count=0, tables={})
@@ -249,14 +240,13 @@ class FusedOptimizer(optim.Optimizer):
                          # (train_utils.py:343-347), so a parameter listed twice is stepped twice with the CLIPPED gradient
         for k, (plan, ptrs) in enumerate(zip(self._plans, tables)):
             items = plan['items']
-            n = len(items)
+            table = plan['chunks'].table(ptrs, 4)
             if k == 0:
                 coef = plan.get('coef')
                 if coef is None:
                     coef = plan['coef'] = torch.empty(2, dtype=torch.float32, device=items[0][0].device)
-                _lib.check(lib.vilco_grad_norm(ptrs.data_ptr(), plan['numel'].data_ptr(), plan['chunk_tensor'].data_ptr(),
-                                               plan['chunk_off'].data_ptr(), n, plan['nchunks'], CHUNK,
-                                               float(clip_grad_l2norm), plan['partial'].data_ptr(), coef.data_ptr(), stream))
+                _lib.check(lib.vilco_grad_norm(C.byref(table), float(clip_grad_l2norm), plan['partial'].data_ptr(), coef.data_ptr(),
+                                               stream))
                 self.last_grad_norm = coef
             if plan['inc'] is None:
                 plan['tstep'].add_(1.0)              # torch.optim keeps the step per parameter
@@ -264,10 +254,8 @@ class FusedOptimizer(optim.Optimizer):
                 plan['tstep'].add_(plan['inc'])
             plan['count'] += 1
             # the update also leaves max|p| of every chunk it wrote: the scale of next step's fp16 x2 weight planes
-            d = _lib.OptimDesc(kind=0 if self.kind == "AdamW" else 1, ptrs=ptrs.data_ptr(), numel=plan['numel'].data_ptr(),
-                               chunk_tensor=plan['chunk_tensor'].data_ptr(), chunk_off=plan['chunk_off'].data_ptr(),
-                               group=plan['group'].data_ptr(), n=n, nchunks=plan['nchunks'], chunk=CHUNK, lr=C.addressof(lr),
-                               wd=C.addressof(wd), ngroups=ng, beta1=g0['betas'][0], beta2=g0['betas'][1], eps=g0['eps'],
+            d = _lib.OptimDesc(table=table, kind=0 if self.kind == "AdamW" else 1, group=plan['group'].data_ptr(),
+                               lr=C.addressof(lr), wd=C.addressof(wd), ngroups=ng, beta1=g0['betas'][0], beta2=g0['betas'][1], eps=g0['eps'],
                                momentum=g0['momentum'], tensor_step=plan['tstep'].data_ptr(),
                                norm_coef=None if coef is None or clip_grad_l2norm <= 0 else coef.data_ptr(),
                                chunk_amax=plan['amax'].data_ptr() if OPT_AMAX else None,
