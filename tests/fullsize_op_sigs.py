@@ -15,7 +15,8 @@ EXEMPT = {
     "mq_loss": "tests/test_loss_gpu.py and the loss goldens",
     "optimizer": "tests/test_train_utils.py",
     "pack / pack_many / pack_tap / weight_planes": "the operand planes: tests/test_step_gemm_census_gpu.py decodes every one a GEMM reads",
-    "decode / NMS": "not part of the training step (tests/test_nms_gpu.py)",
+    "decode / NMS": "not part of the training step (tests/test_nms_gpu.py; the decode at its edges and at the recipe's shape: "
+                    "tests/test_decode_edges_gpu.py against tests/decode_restatement.py)",
 }
 
 
