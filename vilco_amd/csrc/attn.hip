@@ -298,6 +298,10 @@ __device__ __forceinline__ float mask_score(float s, int i, int j, int len, int 
 }
 
 // ------------------------------------------------------------------------------------------ forward
+// dynamic LDS (bytes) of attn_fwd_kernel: sK + sVt + sP.  Every kernel's figure stands like this one above its carve-up;
+// launch_attn() takes both the attribute and the launch size from it
+template <int HDP, int NP>
+constexpr size_t fwd_lds() { return (size_t)NP * (64 * HDP + HDP * 64 + 4 * 16 * 64) * sizeof(__bf16); }
 template <int HDP, int NP, bool F16, bool DROP>
 __global__ __launch_bounds__(ATT_THREADS) void attn_fwd_kernel(AttnArgs a) {
   if (a.drop_thresh) a.drop_seed = vilco_step_seed(a.drop_seed, a.seed_word);
@@ -516,6 +520,8 @@ __device__ __forceinline__ void block_amax_out(float m, float* out, float* smem_
 }
 constexpr int RS64 = 80;                 // LDS row stride (elements) of a natural [64 rows][64 d] tile
 constexpr int PL64 = 64 * RS64;          // elements per part
+constexpr int RSBF = 68;                 // XL kernels: floats per staged row of position scores (their bodies restate it)
+constexpr size_t LDS64_TILES = 2 * 2 * PL64 * sizeof(__bf16);      // two [2 parts][64 rows][RS64] tiles: K + V, or Q + dO
 
 __device__ __forceinline__ bf16x8 tr_frag64(const __bf16* p) {     // k rows at p, k rows + 16 at p + 16 rows
   typedef short s16x4 __attribute__((ext_vector_type(4)));
@@ -564,6 +570,8 @@ __device__ __forceinline__ unsigned lds_addr_of(const void* p) {
 
 // XL: XLNet's relative attention (mask mode 3: additive position scores read unshifted from bd[b,h,i,Tq-i+j], the XLNet
 // mask -- keys >= kv_len masked except the diagonal --, dropout on the probabilities): same kernel, three more steps
+// dynamic LDS of attn_fwd64_kernel and attn_bwd_dq64_kernel: sK + sV, XL: + sBias [4 waves][32 q][RSBF]
+constexpr size_t lds_q64(bool xl) { return LDS64_TILES + (xl ? 4 * 32 * RSBF * sizeof(float) : 0); }
 template <bool XL>
 __global__ __launch_bounds__(ATT_THREADS, 2) void attn_fwd64_kernel(AttnArgs a) {
   if (a.drop_thresh) a.drop_seed = vilco_step_seed(a.drop_seed, a.seed_word);
@@ -862,6 +870,7 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void attn_fwd64_kernel(AttnArgs a) 
 // workgroup's band streamed through LDS (next tile's loads under the current tile's MFMAs), S^T = KR QR^T leaves a lane with 4
 // consecutive p of one query: one float4 store per 16-row block.  a.qn = qr planes, a.kn = kr planes ([H] or, a.mode = 1, [B*H]
 // batches of 2T rows), a.o = bd, a.sc = {1/s, s} of qr and kr.
+constexpr size_t LDS_XL_SCORES = 2 * PL64 * sizeof(__bf16);       // dynamic LDS of xl_scores64_kernel: sK
 __global__ __launch_bounds__(ATT_THREADS, 2) void xl_scores64_kernel(AttnArgs a) {
   constexpr int HDP = 64;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -956,6 +965,8 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void xl_scores64_kernel(AttnArgs a)
 }
 
 // ------------------------------------------------------------------------------------------ backward: dQ (+ dBias)
+template <int HDP, int NP>         // dynamic LDS of attn_bwd_dq_kernel: sK + sV + sKt + sS
+constexpr size_t dq_lds() { return (size_t)NP * (3 * 64 * HDP + 4 * 16 * 64) * sizeof(__bf16); }
 template <int HDP, int NP, bool F16, bool DROP>
 __global__ __launch_bounds__(ATT_THREADS) void attn_bwd_dq_kernel(AttnArgs a) {
   if (a.drop_thresh) a.drop_seed = vilco_step_seed(a.drop_seed, a.seed_word);
@@ -1479,6 +1490,8 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void attn_bwd_dq64_kernel(AttnArgs 
 // XL: XLNet's relative attention.  The position scores of a (64-query tile, this workgroup's 64 keys) pair are 64 rows of
 // 256 B in the unshifted matrix; they are fetched by LDS-DMA (16 rows per wave) one tile ahead into a double-buffered
 // [64 q][68] LDS image that all four waves read (lane = key, 16 queries per lane and tile: scalar LDS reads).
+// dynamic LDS of attn_bwd_dkdv64_kernel: sQ + sdO, XL: + sBias [2 stages][64 q][RSBF]
+constexpr size_t lds_dkdv64(bool xl) { return LDS64_TILES + (xl ? 2 * 64 * RSBF * sizeof(float) : 0); }
 template <bool XL>
 __global__ __launch_bounds__(ATT_THREADS, 2) void attn_bwd_dkdv64_kernel(AttnArgs a) {
   if (a.drop_thresh) a.drop_seed = vilco_step_seed(a.drop_seed, a.seed_word);
@@ -1710,6 +1723,9 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void attn_bwd_dkdv64_kernel(AttnArg
 // ------------------------------------------------------------------------------------------ backward: dK, dV
 // one workgroup per (b, h, 64-key tile); inner loop over 32-query tiles.  S = Q K^T orientation: the C layout
 // gives each lane one key (col) and 4 consecutive queries (rows), so P^T / dS^T go to LDS as packed stores.
+// dynamic LDS of attn_bwd_dkdv_kernel: sV + sK (KV_REG: sV only) + sQ + sdO + sQt + sdOt + sPt + sdSt
+template <int HDP, int NP>
+constexpr size_t dkdv_lds() { return (size_t)NP * ((HDP > 128 ? 64 * HDP : 2 * 64 * HDP) + 4 * 32 * HDP + 2 * 64 * 32) * sizeof(__bf16); }
 template <int HDP, int NP, bool F16, bool HASB, bool DROP>
 __global__ __launch_bounds__(ATT_THREADS) void attn_bwd_dkdv_kernel(AttnArgs a) {
   if (a.drop_thresh) a.drop_seed = vilco_step_seed(a.drop_seed, a.seed_word);
@@ -1954,126 +1970,102 @@ __global__ __launch_bounds__(ATT_THREADS) void attn_bwd_dkdv_kernel(AttnArgs a) 
   }
 }
 
-template <int HDP, int NP>
-size_t fwd_lds() { return (size_t)NP * (64 * HDP + HDP * 64 + 4 * 16 * 64) * sizeof(__bf16); }
-template <int HDP, int NP>
-size_t dq_lds() { return (size_t)NP * (3 * 64 * HDP + 4 * 16 * 64) * sizeof(__bf16); }
-template <int HDP, int NP>
-size_t dkdv_lds() {        // HDP > 128: the K tile is staged through the Q / dO region (attn_bwd_dkdv_kernel: KV_REG)
-  return (size_t)NP * ((HDP > 128 ? 64 * HDP : 2 * 64 * HDP) + 4 * 32 * HDP + 2 * 64 * 32) * sizeof(__bf16);
+// ------------------------------------------------------------------------------------------ host: route, launches
+// Which kernels take a call (table: DESIGN.md, "Attention routes").  Every public entry computes this ONCE with attn_route()
+// and hands it down: the launches, the choice of operand planes and the checks of the optional outputs read that one value.
+//   Hd64    the MQ blocks' attention: hd = 64, fp16 x2 planes, prefix key mask or none, no bias / dS, no dropout
+//   Hd64XL  XLNet's relative attention (unshifted position scores as bias, XLNet mask, optional dropout) at hd = 64, Tq = Tk;
+//           its backward kernels exist to produce dS: a backward that wants none is General behind the Hd64XL forward
+enum class Route { General, Hd64, Hd64XL };
+struct RouteKey { int hd, mode, Tq, Tk, precision; bool has_bias, drop, want_ds; };     // want_ds (backward): dbias || ds_planes
+inline bool env_on(const char* name) { const char* e = getenv(name); return !(e && e[0] == '0'); }
+
+Route attn_route(const RouteKey& k, bool bwd) {
+  static const bool fast = env_on("VILCO_ATTN_FAST"), xl = env_on("VILCO_ATTN_XL_FAST");       // read once per process
+  if (!fast || k.precision != 3 || k.hd != 64) return Route::General;
+  if (!k.has_bias && !k.want_ds && (k.mode == 0 || k.mode == 2) && !k.drop) return Route::Hd64;
+  if (xl && k.has_bias && k.mode == 3 && k.Tq == k.Tk && (!bwd || k.want_ds)) return Route::Hd64XL;
+  return Route::General;
 }
 
-template <typename K>
-void set_lds(K kernel, size_t bytes) {
-  hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-  (void)hipGetLastError();
+// Sets the kernel's dynamic-LDS limit on its first use, then launches it with the same figure.  RAISE = false for the four
+// kernels whose figure is a constant below the 64 KB a launch may ask for without the attribute (the non-XL *64 kernels,
+// 40 KB, and xl_scores64_kernel, 20 KB); every other kernel sets it, as its figure grows with HDP x NP or with XL.
+template <auto KERNEL, bool RAISE = true>
+void launch_attn(dim3 grid, size_t lds, hipStream_t s, const AttnArgs& a) {
+  if constexpr (RAISE) {
+    static const bool once = ((void)hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
+                              (void)hipGetLastError(), true);
+    (void)once;
+  }
+  hipLaunchKernelGGL(KERNEL, grid, dim3(ATT_THREADS), lds, s, a);
 }
-
-bool fwd64_enabled();
-// the MQ blocks' attention: hd = 64, fp16 x2 planes, prefix key mask, no bias / dBias, no dropout -> the *64 kernels
-inline bool fast64(const AttnArgs& a, int precision) {
-  return precision == 3 && a.hd == 64 && !a.bias && !a.dbias && (a.mode == 0 || a.mode == 2) && !a.drop_thresh && fwd64_enabled();
-}
-bool xl64_enabled();
-// XLNet's relative attention (unshifted position scores as bias, XLNet mask, optional dropout) at hd = 64: attn_fwd64_kernel<true>
-inline bool fast64_xl_fwd(const AttnArgs& a, int precision) {
-  return precision == 3 && a.hd == 64 && a.bias && a.mode == 3 && a.Tq == a.Tk && fwd64_enabled() && xl64_enabled();
-}
-bool xl64_enabled() { static const bool on = [] { const char* e = getenv("VILCO_ATTN_XL_FAST"); return !(e && e[0] == '0'); }(); return on; }
-bool fwd64_enabled() { static const bool on = [] { const char* e = getenv("VILCO_ATTN_FAST"); return !(e && e[0] == '0'); }(); return on; }
 
 template <int HDP, int NP, bool F16 = false>
-int launch_fwd(const AttnArgs& a, hipStream_t s) {
+void launch_fwd(const AttnArgs& a, Route route, hipStream_t s) {
+  const dim3 grid((a.Tq + 63) / 64, a.H, a.B);
   if constexpr (HDP == 64 && NP == 2 && F16) {
-    if (fast64(a, 3)) {
-      size_t lds = 2 * 2 * PL64 * sizeof(__bf16);
+    const dim3 g64((a.Tq + F64_Q - 1) / F64_Q, a.H, a.B);
+    if (route == Route::Hd64) {
+      size_t lds = lds_q64(false);
 #ifdef VILCO_LAB_ATTN
       if (const char* e = getenv("VILCO_LAB_ATTN_LDS")) {       // lab: pad the LDS request to limit workgroups per CU
         lds = (size_t)atoi(e);
         hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_fwd64_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
       }
 #endif
-      hipLaunchKernelGGL(attn_fwd64_kernel<false>, dim3((a.Tq + F64_Q - 1) / F64_Q, a.H, a.B), dim3(ATT_THREADS), lds, s, a);
-      return vilco_launch_status();
+      return launch_attn<&attn_fwd64_kernel<false>, false>(g64, lds, s, a);
     }
-    if (fast64_xl_fwd(a, 3)) {
-      const size_t lds = 2 * 2 * PL64 * sizeof(__bf16) + 4 * 32 * 68 * sizeof(float);
-      static const bool oncexl = [] { set_lds(&attn_fwd64_kernel<true>, 2 * 2 * PL64 * sizeof(__bf16) + 4 * 32 * 68 * sizeof(float)); return true; }();
-      (void)oncexl;
-      hipLaunchKernelGGL(attn_fwd64_kernel<true>, dim3((a.Tq + F64_Q - 1) / F64_Q, a.H, a.B), dim3(ATT_THREADS), lds, s, a);
-      return vilco_launch_status();
-    }
+    if (route == Route::Hd64XL) return launch_attn<&attn_fwd64_kernel<true>>(g64, lds_q64(true), s, a);
   }
-  static const bool once = [] {
-    set_lds(&attn_fwd_kernel<HDP, NP, F16, false>, fwd_lds<HDP, NP>());
-    set_lds(&attn_fwd_kernel<HDP, NP, F16, true>, fwd_lds<HDP, NP>());
-    return true;
-  }();
-  (void)once;
-  dim3 grid((a.Tq + 63) / 64, a.H, a.B);
-  const size_t lds = fwd_lds<HDP, NP>();
-  if (a.drop_thresh) hipLaunchKernelGGL((attn_fwd_kernel<HDP, NP, F16, true>), grid, dim3(ATT_THREADS), lds, s, a);
-  else hipLaunchKernelGGL((attn_fwd_kernel<HDP, NP, F16, false>), grid, dim3(ATT_THREADS), lds, s, a);
-  return vilco_launch_status();
+  if (a.drop_thresh) launch_attn<&attn_fwd_kernel<HDP, NP, F16, true>>(grid, fwd_lds<HDP, NP>(), s, a);
+  else launch_attn<&attn_fwd_kernel<HDP, NP, F16, false>>(grid, fwd_lds<HDP, NP>(), s, a);
 }
 
 template <int HDP, int NP, bool F16 = false>
-int launch_bwd(const AttnArgs& a, hipStream_t s) {
-  static const bool once = [] {
-    set_lds(&attn_bwd_dq_kernel<HDP, NP, F16, false>, dq_lds<HDP, NP>());
-    set_lds(&attn_bwd_dq_kernel<HDP, NP, F16, true>, dq_lds<HDP, NP>());
-    set_lds(&attn_bwd_dkdv_kernel<HDP, NP, F16, false, false>, dkdv_lds<HDP, NP>());
-    set_lds(&attn_bwd_dkdv_kernel<HDP, NP, F16, true, false>, dkdv_lds<HDP, NP>());
-    set_lds(&attn_bwd_dkdv_kernel<HDP, NP, F16, false, true>, dkdv_lds<HDP, NP>());
-    set_lds(&attn_bwd_dkdv_kernel<HDP, NP, F16, true, true>, dkdv_lds<HDP, NP>());
-    return true;
-  }();
-  (void)once;
-  dim3 gq((a.Tq + 63) / 64, a.H, a.B), gk((a.Tk + 63) / 64, a.H, a.B);
-  const size_t lq = dq_lds<HDP, NP>(), lk = dkdv_lds<HDP, NP>();
-  bool fast = false;
-  if constexpr (HDP == 64 && NP == 2 && F16)
-    fast = fast64(a, 3);
-  if (fast) {
-    if constexpr (HDP == 64 && NP == 2 && F16) {
-      constexpr size_t l64 = 2 * 2 * PL64 * sizeof(__bf16);
-      const dim3 gq64((a.Tq + F64_Q - 1) / F64_Q, a.H, a.B);
-      hipLaunchKernelGGL(attn_bwd_dq64_kernel<false>, gq64, dim3(ATT_THREADS), l64, s, a);
-      hipLaunchKernelGGL(attn_bwd_dkdv64_kernel<false>, gk, dim3(ATT_THREADS), l64, s, a);
-      return vilco_launch_status();
+void launch_bwd(const AttnArgs& a, Route route, hipStream_t s) {
+  const dim3 gq((a.Tq + 63) / 64, a.H, a.B), gk((a.Tk + 63) / 64, a.H, a.B);
+  if constexpr (HDP == 64 && NP == 2 && F16) {
+    const dim3 gq64((a.Tq + F64_Q - 1) / F64_Q, a.H, a.B);
+    if (route == Route::Hd64) {
+      launch_attn<&attn_bwd_dq64_kernel<false>, false>(gq64, lds_q64(false), s, a);
+      return launch_attn<&attn_bwd_dkdv64_kernel<false>, false>(gk, lds_dkdv64(false), s, a);
+    }
+    if (route == Route::Hd64XL) {                     // dQ + dS on the fast-path structure
+      launch_attn<&attn_bwd_dq64_kernel<true>>(gq64, lds_q64(true), s, a);
+      return launch_attn<&attn_bwd_dkdv64_kernel<true>>(gk, lds_dkdv64(true), s, a);
     }
   }
-  bool xl_dq = false;                               // XLNet's relative attention: dQ + dS on the fast-path structure
-  if constexpr (HDP == 64 && NP == 2 && F16) xl_dq = fast64_xl_fwd(a, 3) && (a.dbias != nullptr || a.dsp != nullptr);
-  if (xl_dq) {
-    if constexpr (HDP == 64 && NP == 2 && F16) {
-      constexpr size_t lxl = 2 * 2 * PL64 * sizeof(__bf16) + 4 * 32 * 68 * sizeof(float);
-      static const bool oncexl = [] { set_lds(&attn_bwd_dq64_kernel<true>, 2 * 2 * PL64 * sizeof(__bf16) + 4 * 32 * 68 * sizeof(float)); return true; }();
-      (void)oncexl;
-      hipLaunchKernelGGL(attn_bwd_dq64_kernel<true>, dim3((a.Tq + F64_Q - 1) / F64_Q, a.H, a.B), dim3(ATT_THREADS), lxl, s, a);
-      constexpr size_t lkx = 2 * 2 * PL64 * sizeof(__bf16) + 2 * 64 * 68 * sizeof(float);
-      static const bool oncekx = [] { set_lds(&attn_bwd_dkdv64_kernel<true>, 2 * 2 * PL64 * sizeof(__bf16) + 2 * 64 * 68 * sizeof(float)); return true; }();
-      (void)oncekx;
-      hipLaunchKernelGGL(attn_bwd_dkdv64_kernel<true>, gk, dim3(ATT_THREADS), lkx, s, a);
-      return vilco_launch_status();
-    }
-  } else if (a.drop_thresh) hipLaunchKernelGGL((attn_bwd_dq_kernel<HDP, NP, F16, true>), gq, dim3(ATT_THREADS), lq, s, a);
-  else hipLaunchKernelGGL((attn_bwd_dq_kernel<HDP, NP, F16, false>), gq, dim3(ATT_THREADS), lq, s, a);
+  constexpr size_t lq = dq_lds<HDP, NP>(), lk = dkdv_lds<HDP, NP>();
   const bool dr = a.drop_thresh != 0;
-  if (a.bias && dr) hipLaunchKernelGGL((attn_bwd_dkdv_kernel<HDP, NP, F16, true, true>), gk, dim3(ATT_THREADS), lk, s, a);
-  else if (a.bias) hipLaunchKernelGGL((attn_bwd_dkdv_kernel<HDP, NP, F16, true, false>), gk, dim3(ATT_THREADS), lk, s, a);
-  else if (dr) hipLaunchKernelGGL((attn_bwd_dkdv_kernel<HDP, NP, F16, false, true>), gk, dim3(ATT_THREADS), lk, s, a);
-  else hipLaunchKernelGGL((attn_bwd_dkdv_kernel<HDP, NP, F16, false, false>), gk, dim3(ATT_THREADS), lk, s, a);
-  return vilco_launch_status();
+  if (dr) launch_attn<&attn_bwd_dq_kernel<HDP, NP, F16, true>>(gq, lq, s, a);
+  else launch_attn<&attn_bwd_dq_kernel<HDP, NP, F16, false>>(gq, lq, s, a);
+  if (a.bias && dr) launch_attn<&attn_bwd_dkdv_kernel<HDP, NP, F16, true, true>>(gk, lk, s, a);
+  else if (a.bias) launch_attn<&attn_bwd_dkdv_kernel<HDP, NP, F16, true, false>>(gk, lk, s, a);
+  else if (dr) launch_attn<&attn_bwd_dkdv_kernel<HDP, NP, F16, false, true>>(gk, lk, s, a);
+  else launch_attn<&attn_bwd_dkdv_kernel<HDP, NP, F16, false, false>>(gk, lk, s, a);
 }
 
-template <int HDP>
-int dispatch(const AttnArgs& a, int precision, bool bwd, hipStream_t s) {
-  if (precision == 1) return bwd ? launch_bwd<HDP, 1>(a, s) : launch_fwd<HDP, 1>(a, s);
-  if (precision == 0) return bwd ? launch_bwd<HDP, 2>(a, s) : launch_fwd<HDP, 2>(a, s);
-  if (precision == 3) return bwd ? launch_bwd<HDP, 2, true>(a, s) : launch_fwd<HDP, 2, true>(a, s);
-  if constexpr (HDP <= 64) return bwd ? launch_bwd<HDP, 3>(a, s) : launch_fwd<HDP, 3>(a, s);
-  else return VILCO_ERR_UNSUPPORTED;               // three bf16 planes of a wider tile exceed the LDS (check_common)
+// the one hd -> HDP table (padded head width of the tiles): f(std::integral_constant<int, HDP>)
+template <typename F>
+auto with_hdp(int hd, F&& f) {
+  if (hd <= 32) return f(std::integral_constant<int, 32>{});
+  if (hd <= 64) return f(std::integral_constant<int, 64>{});
+  if (hd <= 128) return f(std::integral_constant<int, 128>{});
+  return f(std::integral_constant<int, 160>{});
+}
+inline int hdp_of(int hd) { return with_hdp(hd, [](auto w) { return (int)decltype(w)::value; }); }
+
+int dispatch(const AttnArgs& a, Route route, int precision, bool bwd, hipStream_t s) {
+  return with_hdp(a.hd, [&](auto w) -> int {
+    constexpr int HDP = decltype(w)::value;
+    if (precision == 1) bwd ? launch_bwd<HDP, 1>(a, route, s) : launch_fwd<HDP, 1>(a, route, s);
+    else if (precision == 0) bwd ? launch_bwd<HDP, 2>(a, route, s) : launch_fwd<HDP, 2>(a, route, s);
+    else if (precision == 3) bwd ? launch_bwd<HDP, 2, true>(a, route, s) : launch_fwd<HDP, 2, true>(a, route, s);
+    else if constexpr (HDP <= 64) bwd ? launch_bwd<HDP, 3>(a, route, s) : launch_fwd<HDP, 3>(a, route, s);
+    else return VILCO_ERR_UNSUPPORTED;             // three bf16 planes of a wider tile exceed the LDS (check_common)
+    return vilco_launch_status();
+  });
 }
 
 int check_common(int B, int H, int Tq, int Tk, int hd, int mode, int precision, int window = 0) {
@@ -2085,7 +2077,6 @@ int check_common(int B, int H, int Tq, int Tk, int hd, int mode, int precision, 
 }
 
 inline long up(long x, long a) { return (x + a - 1) / a * a; }
-inline int hdp_of(int hd) { return hd <= 32 ? 32 : (hd <= 64 ? 64 : (hd <= 128 ? 128 : 160)); }   // padded head width of the tiles
 inline int np_of(int precision) { return precision == 1 ? 1 : ((precision == 0 || precision == 3) ? 2 : 3); }
 constexpr long ATT_SCALE_BYTES = 4 * AMAX_MAX_BLOCKS * 4 + 256;    // fp16 x2: amax partials of q, k, v, dO + AttnScales
 
@@ -2178,6 +2169,82 @@ void flush_packs(PackQueue& pq, ScaleWs& sw, bool f16, int NP, int nbatch, hipSt
   if (pq.nt) dispatch_pack_tr_multi(NP, pq.t, pq.nt, s, nbatch);
 }
 
+// What the operand packs of one call share.  A call site names what differs: the tensor, its T, natural or transposed
+// planes, and its slot (0..3 = q, k, v, dO: the amax partials sw->parts[slot], the {1/s, s} pair at scales + 2 slot).
+// Planes are handed out from `cursor` in call order.
+struct Packer {
+  int B, H, hd, HDP, NP;
+  hipStream_t s;
+  PackQueue* queue;          // nullptr: each pack is launched at once
+  __bf16* cursor;
+  const ScaleWs* sw;
+  float* scales;
+  Planes nat(const float* x, int T, int slot) { return pack(x, spec_nat(B, H, T, HDP), false, T, slot); }
+  Planes tr(const float* x, int T, int slot) { return pack(x, spec_tr(B, H, T, hd), true, T, slot); }
+  Planes pack(const float* x, const PlaneSpec& sp, bool t, int T, int slot) {
+    return pack_operand(x, cursor, sp, t, B, H, T, hd, HDP, NP, s, sw->parts[slot], sw->n[slot], scales + 2 * slot, queue);
+  }
+};
+
+// One attention call between its prologue (attn_begin) and its launches (attn_run)
+struct AttnCall {
+  AttnArgs a = {};
+  Route route = Route::General;
+  hipStream_t s = nullptr;
+  int precision = 0;
+  unsigned char* ws = nullptr;       // 256-byte aligned: the amax / scale region, then the operand planes
+  ScaleWs sw;
+  PackQueue pq;
+  Packer packer() {
+    return {a.B, a.H, a.hd, hdp_of(a.hd), np_of(precision), s, &pq, reinterpret_cast<__bf16*>(ws + ATT_SCALE_BYTES), &sw, sw.out};
+  }
+};
+
+// The prologue of vilco_attn_fwd / vilco_attn_bwd: the descriptor's checks in their documented order, the AttnArgs fields
+// both directions share, the route, the aligned workspace (backward: delta in front of it) and the amax plan.  Launches nothing.
+// Returns ATTN_GO, or the call's return value (VILCO_OK: an empty call).
+constexpr int ATTN_GO = 1;
+int attn_begin(const vilco_attn_desc* d, void* stream, bool bwd, AttnCall& c) {
+  if (!d) return VILCO_ERR_BADARG;
+  const int32_t B = d->B, H = d->H, Tq = d->Tq, Tk = d->Tk, hd = d->hd, precision = d->precision;
+  const int rc = check_common(B, H, Tq, Tk, hd, d->mode, precision, d->window);
+  if (!(d->drop_p >= 0.f) || d->drop_p >= 1.f) return VILCO_ERR_BADARG;
+  if (rc != VILCO_OK) return rc;
+  if (!d->q || !d->k || !d->v || !d->o || !d->lse) return VILCO_ERR_BADARG;
+  if (bwd && (!d->dout || !d->dq || !d->dk || !d->dv)) return VILCO_ERR_BADARG;
+  if (d->mode != 2 && !d->kv_len) return VILCO_ERR_BADARG;
+  if (B == 0 || Tq == 0) return VILCO_OK;
+  if (Tk == 0) return VILCO_ERR_BADARG;
+  const size_t need = bwd ? vilco_attn_bwd_workspace(B, H, Tq, Tk, hd, precision) : vilco_attn_fwd_workspace(B, H, Tq, Tk, hd, precision);
+  if (!d->workspace || d->workspace_bytes < need) return VILCO_ERR_WORKSPACE;
+  AttnArgs& a = c.a;
+  a.q = d->q; a.k = d->k; a.v = d->v; a.bias = d->bias; a.lse = d->lse; a.kv_len = d->kv_len;
+  a.B = B; a.H = H; a.Tq = Tq; a.Tk = Tk; a.hd = hd; a.C = H * hd; a.scale = d->scale; a.mode = d->mode; a.window = d->window;
+  a.drop_thresh = vilco_drop_threshold_host(d->drop_p); a.drop_seed = d->drop_seed; a.drop_inv_keep = 1.f / (1.f - d->drop_p);
+  a.seed_word = vilco_seed_word_dev();
+  c.s = reinterpret_cast<hipStream_t>(stream); c.precision = precision;
+  c.route = attn_route({hd, d->mode, Tq, Tk, precision, d->bias != nullptr, a.drop_thresh != 0, bwd && (d->dbias || d->ds_planes)}, bwd);
+  c.ws = reinterpret_cast<unsigned char*>(up((long)reinterpret_cast<uintptr_t>(d->workspace), 256));
+  if (bwd) {
+    a.delta = reinterpret_cast<float*>(c.ws);
+    c.ws += up((long)B * H * Tq * 4, 256);
+  }
+  if (precision == 3) {
+    const float* const xs[4] = {d->q, d->k, d->v, bwd ? d->dout : nullptr};
+    const int Ts[4] = {Tq, Tk, Tk, bwd ? Tq : 0};
+    c.sw = plan_amax(c.ws, xs, Ts, bwd ? 4 : 3, B, H * hd);
+    use_external_amax(c.sw, d->amax_in, bwd ? 4 : 3);
+    a.sc = reinterpret_cast<const AttnScales*>(c.sw.out);
+  }
+  return ATTN_GO;
+}
+
+// queued packs out, then the route's kernels
+int attn_run(AttnCall& c, bool bwd) {
+  flush_packs(c.pq, c.sw, c.precision == 3, np_of(c.precision), c.a.B * c.a.H, c.s);
+  return dispatch(c.a, c.route, c.precision, bwd, c.s);
+}
+
 }  // namespace
 
 #ifdef VILCO_LAB_ATTN
@@ -2190,27 +2257,20 @@ extern "C" int vilco_attn_supported(int32_t hd) { return hd > 0 && hd <= 160 && 
 
 extern "C" int32_t vilco_attn_amax_parts(int32_t B, int32_t H, int32_t T, int32_t hd, int32_t mode, int32_t precision,
                                          int32_t has_bias, float drop_p, int32_t key_side) {
-  AttnArgs a = {};
-  a.hd = hd; a.mode = mode; a.drop_thresh = vilco_drop_threshold_host(drop_p);
-  if (has_bias) a.bias = reinterpret_cast<const float*>(&a);      // only its nullness is looked at
-  if (has_bias == 2) {           // the dS (dbias) partials of XLNet's relative attention: attn_bwd_dq64_kernel<true>, one per workgroup
-    a.Tq = a.Tk = T;
-    if (B <= 0 || H <= 0 || T <= 0 || key_side || !fast64_xl_fwd(a, precision)) return 0;
-    const long nx = (long)((T + F64_Q - 1) / F64_Q) * H * B;
-    return nx <= 8192 ? (int32_t)nx : 0;
-  }
-  if (B <= 0 || H <= 0 || T <= 0 || !fast64(a, precision)) return 0;
-  const long n = (long)((T + (key_side ? 63 : F64_Q - 1)) / (key_side ? 64 : F64_Q)) * H * B;
+  if (B <= 0 || H <= 0 || T <= 0) return 0;
+  // has_bias = 2: the dS (dbias) partials of XLNet's relative attention, attn_bwd_dq64_kernel<true>, one per workgroup
+  const bool ds = has_bias == 2;
+  const Route r = attn_route({hd, mode, T, T, precision, has_bias != 0, vilco_drop_threshold_host(drop_p) != 0, ds}, ds);
+  if (r != (ds ? Route::Hd64XL : Route::Hd64) || (ds && key_side)) return 0;
+  const int rows = key_side ? 64 : F64_Q;           // rows of T per workgroup of the kernel that writes the partials
+  const long n = (long)((T + rows - 1) / rows) * H * B;
   return n <= 8192 ? (int32_t)n : 0;
 }
 
 // 1 when vilco_attn_fwd can write o's operand planes (vilco_attn_desc.o_planes) for this configuration (the hd = 64 forward kernels)
 extern "C" int32_t vilco_attn_planes_supported(int32_t Tq, int32_t Tk, int32_t hd, int32_t mode, int32_t precision, int32_t has_bias,
                                                float drop_p) {
-  AttnArgs a = {};
-  a.hd = hd; a.mode = mode; a.Tq = Tq; a.Tk = Tk; a.drop_thresh = vilco_drop_threshold_host(drop_p);
-  if (has_bias) a.bias = reinterpret_cast<const float*>(&a);      // only its nullness is looked at
-  return (fast64(a, precision) || fast64_xl_fwd(a, precision)) ? 1 : 0;
+  return attn_route({hd, mode, Tq, Tk, precision, has_bias != 0, vilco_drop_threshold_host(drop_p) != 0, false}, false) != Route::General;
 }
 
 extern "C" size_t vilco_attn_fwd_workspace(int32_t B, int32_t H, int32_t Tq, int32_t Tk, int32_t hd, int32_t precision) {
@@ -2220,61 +2280,28 @@ extern "C" size_t vilco_attn_fwd_workspace(int32_t B, int32_t H, int32_t Tq, int
 }
 
 extern "C" int vilco_attn_fwd(const vilco_attn_desc* d, void* stream) {
-  if (!d) return VILCO_ERR_BADARG;
-  const float *q = d->q, *k = d->k, *v = d->v, *bias = d->bias;
-  const int32_t* kv_len = d->kv_len;
-  const int32_t B = d->B, H = d->H, Tq = d->Tq, Tk = d->Tk, hd = d->hd, mode = d->mode, window = d->window, precision = d->precision;
-  const float scale = d->scale, drop_p = d->drop_p;
-  const uint32_t drop_seed = d->drop_seed;
-  const vilco_attn_amax_in* amax_in = d->amax_in;
-  void* workspace = d->workspace;
-  const size_t workspace_bytes = d->workspace_bytes;
-  float *o = d->o, *lse = d->lse, *o_amax = d->o_amax;
-  void* o_planes = d->o_planes;
-  int rc = check_common(B, H, Tq, Tk, hd, mode, precision, window);
-  if (!(drop_p >= 0.f) || drop_p >= 1.f) return VILCO_ERR_BADARG;
-  if (rc != VILCO_OK) return rc;
-  if (!q || !k || !v || !o || !lse) return VILCO_ERR_BADARG;
-  if (mode != 2 && !kv_len) return VILCO_ERR_BADARG;
-  if (B == 0 || Tq == 0) return VILCO_OK;
-  if (Tk == 0) return VILCO_ERR_BADARG;
-  if (!workspace || workspace_bytes < vilco_attn_fwd_workspace(B, H, Tq, Tk, hd, precision)) return VILCO_ERR_WORKSPACE;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const int HDP = hdp_of(hd), NP = np_of(precision);
-  AttnArgs a = {};
-  a.q = q; a.k = k; a.v = v; a.bias = bias; a.o = o; a.lse = lse; a.kv_len = kv_len;
-  a.B = B; a.H = H; a.Tq = Tq; a.Tk = Tk; a.hd = hd; a.C = H * hd; a.scale = scale; a.mode = mode; a.window = window;
-  a.drop_thresh = vilco_drop_threshold_host(drop_p); a.drop_seed = drop_seed; a.drop_inv_keep = 1.f / (1.f - drop_p); a.seed_word = vilco_seed_word_dev();
-  if (o_amax && !fast64(a, precision)) return VILCO_ERR_UNSUPPORTED;      // see vilco_attn_amax_parts
-  a.am_o = o_amax;
-  if (o_planes) {                  // the hd = 64 forward kernels only (fast64 / fast64_xl_fwd)
-    if (!(fast64(a, precision) || fast64_xl_fwd(a, precision)) || !vilco_aligned(o_planes, 256)) return VILCO_ERR_UNSUPPORTED;
+  AttnCall c;
+  const int rc = attn_begin(d, stream, false, c);
+  if (rc != ATTN_GO) return rc;
+  AttnArgs& a = c.a;
+  const int32_t Tq = d->Tq, Tk = d->Tk;
+  a.o = d->o;
+  if (d->o_amax && c.route != Route::Hd64) return VILCO_ERR_UNSUPPORTED;      // see vilco_attn_amax_parts
+  a.am_o = d->o_amax;
+  if (d->o_planes) {               // the hd = 64 forward kernels only
+    if (c.route == Route::General || !vilco_aligned(d->o_planes, 256)) return VILCO_ERR_UNSUPPORTED;
     VilcoPlaneView pv;
-    if (d->o_planes_bytes < vilco_plane_view(o_planes, (long)B * Tq, H * hd, 0, &pv)) return VILCO_ERR_WORKSPACE;
+    if (d->o_planes_bytes < vilco_plane_view(d->o_planes, (long)a.B * Tq, a.C, 0, &pv)) return VILCO_ERR_WORKSPACE;
     a.op0 = pv.p0; a.o_plane_stride = pv.plane_stride; a.o_inv_scale = pv.inv_scale; a.o_rows32 = pv.rows_out;
     a.o_scale_mul = 1.f;
     for (float ik = a.drop_thresh ? a.drop_inv_keep : 1.f; ik > 1.f; ik *= 0.5f) a.o_scale_mul *= 0.5f;      // 2^-ceil(log2(1 / keep))
   }
-  unsigned char* wsb = reinterpret_cast<unsigned char*>(up((long)reinterpret_cast<uintptr_t>(workspace), 256));
-  ScaleWs sw;
-  if (precision == 3) {
-    const float* const xs[4] = {q, k, v, nullptr};
-    const int Ts[4] = {Tq, Tk, Tk, 0};
-    sw = plan_amax(wsb, xs, Ts, 3, B, H * hd);
-    use_external_amax(sw, amax_in, 3);
-    a.sc = reinterpret_cast<const AttnScales*>(sw.out);
-  }
-  float* so = sw.out;
-  __bf16* w = reinterpret_cast<__bf16*>(wsb + ATT_SCALE_BYTES);
-  PackQueue pq;
-  a.qn = pack_operand(q, w, spec_nat(B, H, Tq, HDP), false, B, H, Tq, hd, HDP, NP, s, sw.parts[0], sw.n[0], so, &pq);
-  a.kn = pack_operand(k, w, spec_nat(B, H, Tk, HDP), false, B, H, Tk, hd, HDP, NP, s, sw.parts[1], sw.n[1], so + 2, &pq);
-  if (fast64(a, precision) || fast64_xl_fwd(a, precision))       // the hd = 64 fast kernels read V from its natural planes (transposing LDS reads)
-    a.vn = pack_operand(v, w, spec_nat(B, H, Tk, HDP), false, B, H, Tk, hd, HDP, NP, s, sw.parts[2], sw.n[2], so + 4, &pq);
-  else
-    a.vt = pack_operand(v, w, spec_tr(B, H, Tk, hd), true, B, H, Tk, hd, HDP, NP, s, sw.parts[2], sw.n[2], so + 4, &pq);
-  flush_packs(pq, sw, precision == 3, NP, B * H, s);
-  return hd <= 32 ? dispatch<32>(a, precision, false, s) : (hd <= 64 ? dispatch<64>(a, precision, false, s) : (hd <= 128 ? dispatch<128>(a, precision, false, s) : dispatch<160>(a, precision, false, s)));
+  Packer pk = c.packer();
+  a.qn = pk.nat(d->q, Tq, 0);
+  a.kn = pk.nat(d->k, Tk, 1);
+  if (c.route != Route::General) a.vn = pk.nat(d->v, Tk, 2);       // the hd = 64 kernels read V from its natural planes (transposing LDS reads)
+  else a.vt = pk.tr(d->v, Tk, 2);
+  return attn_run(c, false);
 }
 
 // XLNet position scores (xl_scores64_kernel): bd[B][H][T][2T] (fp32, only the band of every row is written) from qr [B][T][H*64]
@@ -2307,10 +2334,12 @@ extern "C" int vilco_xl_scores(const float* qr, const float* kr, float* bd, int3
   AttnArgs a = {};
   a.B = B; a.H = H; a.Tq = T; a.Tk = T; a.hd = hd; a.C = H * hd; a.mode = per_clip ? 1 : 0;
   a.o = bd;
-  a.qn = pack_operand(qr, w, spec_nat(B, H, T, 64), false, B, H, T, hd, 64, 2, s, sq.parts[0], sq.n[0], scales, nullptr);
-  a.kn = pack_operand(kr, w, spec_nat(Bk, H, 2 * T, 64), false, Bk, H, 2 * T, hd, 64, 2, s, sk.parts[0], sk.n[0], scales + 2, nullptr);
+  Packer pk{B, H, hd, 64, 2, s, nullptr, w, &sq, scales};
+  a.qn = pk.nat(qr, T, 0);
+  pk.B = Bk; pk.sw = &sk; pk.scales = scales + 2;           // kr: its own batch count, partials and scale pair
+  a.kn = pk.nat(kr, 2 * T, 0);
   a.sc = reinterpret_cast<const AttnScales*>(scales);
-  hipLaunchKernelGGL(xl_scores64_kernel, dim3((T + F64_Q - 1) / F64_Q, H, B), dim3(ATT_THREADS), 2 * PL64 * sizeof(__bf16), s, a);
+  launch_attn<&xl_scores64_kernel, false>(dim3((T + F64_Q - 1) / F64_Q, H, B), LDS_XL_SCORES, s, a);
   return vilco_launch_status();
 }
 
@@ -2328,73 +2357,37 @@ extern "C" size_t vilco_attn_dsplanes_bytes(int32_t B, int32_t H, int32_t T) {
 }
 
 extern "C" int vilco_attn_bwd(const vilco_attn_desc* d, void* stream) {
-  if (!d) return VILCO_ERR_BADARG;
-  const float *q = d->q, *k = d->k, *v = d->v, *bias = d->bias;
-  const int32_t* kv_len = d->kv_len;
-  const int32_t B = d->B, H = d->H, Tq = d->Tq, Tk = d->Tk, hd = d->hd, mode = d->mode, window = d->window, precision = d->precision;
-  const float scale = d->scale, drop_p = d->drop_p;
-  const uint32_t drop_seed = d->drop_seed;
-  const vilco_attn_amax_in* amax_in = d->amax_in;
-  void* workspace = d->workspace;
-  const size_t workspace_bytes = d->workspace_bytes;
-  const float *o = d->o, *lse = d->lse, *dout = d->dout;
-  float *dq = d->dq, *dk = d->dk, *dv = d->dv, *dbias = d->dbias;
-  float *dq_amax = d->dq_amax, *dk_amax = d->dk_amax, *dv_amax = d->dv_amax, *dbias_amax = d->dbias_amax;
-  void* ds_planes = d->ds_planes;
-  const size_t ds_planes_bytes = d->ds_planes_bytes;
-  int rc = check_common(B, H, Tq, Tk, hd, mode, precision, window);
-  if (!(drop_p >= 0.f) || drop_p >= 1.f) return VILCO_ERR_BADARG;
-  if (rc != VILCO_OK) return rc;
-  if (!q || !k || !v || !o || !lse || !dout || !dq || !dk || !dv) return VILCO_ERR_BADARG;
-  if (mode != 2 && !kv_len) return VILCO_ERR_BADARG;
-  if (B == 0 || Tq == 0) return VILCO_OK;
-  if (Tk == 0) return VILCO_ERR_BADARG;
-  if (!workspace || workspace_bytes < vilco_attn_bwd_workspace(B, H, Tq, Tk, hd, precision)) return VILCO_ERR_WORKSPACE;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const int HDP = hdp_of(hd), NP = np_of(precision);
-  unsigned char* wsb = reinterpret_cast<unsigned char*>(up((long)reinterpret_cast<uintptr_t>(workspace), 256));
-  float* delta = reinterpret_cast<float*>(wsb);
-  wsb += up((long)B * H * Tq * 4, 256);
-  AttnArgs a = {};
-  a.q = q; a.k = k; a.v = v; a.bias = bias; a.lse = const_cast<float*>(lse); a.kv_len = kv_len;
-  a.B = B; a.H = H; a.Tq = Tq; a.Tk = Tk; a.hd = hd; a.C = H * hd; a.scale = scale; a.mode = mode; a.window = window;
-  a.drop_thresh = vilco_drop_threshold_host(drop_p); a.drop_seed = drop_seed; a.drop_inv_keep = 1.f / (1.f - drop_p); a.seed_word = vilco_seed_word_dev();
-  a.dout = dout; a.delta = delta; a.o_in = o; a.dq = dq; a.dk = dk; a.dv = dv; a.dbias = dbias;
-  if ((dq_amax || dk_amax || dv_amax) && !fast64(a, precision)) return VILCO_ERR_UNSUPPORTED;      // see vilco_attn_amax_parts
-  a.am_dq = dq_amax; a.am_dk = dk_amax; a.am_dv = dv_amax;
-  if (dbias_amax && !(fast64_xl_fwd(a, precision) && dbias)) return VILCO_ERR_UNSUPPORTED;       // XLNet fast path only (has_bias = 2)
-  a.am_ds = dbias_amax;
-  if (ds_planes) {                 // XLNet fast path only; `dbias` / `dbias_amax` are then not written
-    if (dbias || dbias_amax || !fast64_xl_fwd(a, precision) || (Tk % 64) != 0 || !vilco_aligned(ds_planes, 256)) return VILCO_ERR_UNSUPPORTED;
-    if (ds_planes_bytes < vilco_attn_dsplanes_bytes(B, H, Tq)) return VILCO_ERR_WORKSPACE;
+  AttnCall c;
+  const int rc = attn_begin(d, stream, true, c);
+  if (rc != ATTN_GO) return rc;
+  AttnArgs& a = c.a;
+  const int32_t B = d->B, H = d->H, Tq = d->Tq, Tk = d->Tk;
+  a.dout = d->dout; a.o_in = d->o; a.dq = d->dq; a.dk = d->dk; a.dv = d->dv; a.dbias = d->dbias;
+  if ((d->dq_amax || d->dk_amax || d->dv_amax) && c.route != Route::Hd64) return VILCO_ERR_UNSUPPORTED;      // see vilco_attn_amax_parts
+  a.am_dq = d->dq_amax; a.am_dk = d->dk_amax; a.am_dv = d->dv_amax;
+  if (d->dbias_amax && !(c.route == Route::Hd64XL && d->dbias)) return VILCO_ERR_UNSUPPORTED;       // XLNet fast path only (has_bias = 2)
+  a.am_ds = d->dbias_amax;
+  if (d->ds_planes) {              // XLNet fast path only; `dbias` / `dbias_amax` are then not written
+    if (d->dbias || d->dbias_amax || c.route != Route::Hd64XL || (Tk % 64) != 0 || !vilco_aligned(d->ds_planes, 256)) return VILCO_ERR_UNSUPPORTED;
+    if (d->ds_planes_bytes < vilco_attn_dsplanes_bytes(B, H, Tq)) return VILCO_ERR_WORKSPACE;
     const long r32 = ((long)Tq + 31) / 32 * 32, c32 = ((long)Tq + Tk + 31) / 32 * 32;
-    unsigned char* u = reinterpret_cast<unsigned char*>(ds_planes);
+    unsigned char* u = reinterpret_cast<unsigned char*>(d->ds_planes);
     a.dsp = reinterpret_cast<_Float16*>(u + VILCO_PACK_HDR);
     a.ds_plane_stride = (long)B * H * r32 * c32; a.ds_batch_stride = r32 * c32; a.ds_ld = (int)c32;
     a.ds_inv_scale = reinterpret_cast<float*>(u) + VILCO_AMAX_MAX_BLOCKS;
   }
-  ScaleWs sw;
-  if (precision == 3) {
-    const float* const xs[4] = {q, k, v, dout};
-    const int Ts[4] = {Tq, Tk, Tk, Tq};
-    sw = plan_amax(wsb, xs, Ts, 4, B, H * hd);
-    use_external_amax(sw, amax_in, 4);
-    a.sc = reinterpret_cast<const AttnScales*>(sw.out);
+  // the hd = 64 kernels read every operand from its natural planes only (transposing LDS reads): the general kernels,
+  // and only they, get qt / dot / kt
+  const bool general = c.route == Route::General;
+  Packer pk = c.packer();
+  a.qn = pk.nat(d->q, Tq, 0);
+  a.don = pk.nat(d->dout, Tq, 3);
+  if (general) {
+    a.qt = pk.tr(d->q, Tq, 0);
+    a.dot = pk.tr(d->dout, Tq, 3);
   }
-  float* so = sw.out;
-  __bf16* w = reinterpret_cast<__bf16*>(wsb + ATT_SCALE_BYTES);
-  PackQueue pq;
-  // the hd = 64 fast kernels read every operand from its natural planes only (transposing LDS reads)
-  const bool nat_only = fast64(a, precision) || (fast64_xl_fwd(a, precision) && (a.dbias != nullptr || a.dsp != nullptr));
-  a.qn = pack_operand(q, w, spec_nat(B, H, Tq, HDP), false, B, H, Tq, hd, HDP, NP, s, sw.parts[0], sw.n[0], so, &pq);
-  a.don = pack_operand(dout, w, spec_nat(B, H, Tq, HDP), false, B, H, Tq, hd, HDP, NP, s, sw.parts[3], sw.n[3], so + 6, &pq);
-  if (!nat_only) {
-    a.qt = pack_operand(q, w, spec_tr(B, H, Tq, hd), true, B, H, Tq, hd, HDP, NP, s, sw.parts[0], sw.n[0], so, &pq);
-    a.dot = pack_operand(dout, w, spec_tr(B, H, Tq, hd), true, B, H, Tq, hd, HDP, NP, s, sw.parts[3], sw.n[3], so + 6, &pq);
-  }
-  a.kn = pack_operand(k, w, spec_nat(B, H, Tk, HDP), false, B, H, Tk, hd, HDP, NP, s, sw.parts[1], sw.n[1], so + 2, &pq);
-  a.vn = pack_operand(v, w, spec_nat(B, H, Tk, HDP), false, B, H, Tk, hd, HDP, NP, s, sw.parts[2], sw.n[2], so + 4, &pq);
-  if (!nat_only) a.kt = pack_operand(k, w, spec_tr(B, H, Tk, hd), true, B, H, Tk, hd, HDP, NP, s, sw.parts[1], sw.n[1], so + 2, &pq);
-  flush_packs(pq, sw, precision == 3, NP, B * H, s);
-  return hd <= 32 ? dispatch<32>(a, precision, true, s) : (hd <= 64 ? dispatch<64>(a, precision, true, s) : (hd <= 128 ? dispatch<128>(a, precision, true, s) : dispatch<160>(a, precision, true, s)));
+  a.kn = pk.nat(d->k, Tk, 1);
+  a.vn = pk.nat(d->v, Tk, 2);
+  if (general) a.kt = pk.tr(d->k, Tk, 1);
+  return attn_run(c, true);
 }
