@@ -723,6 +723,19 @@ int vilco_cl_penalty(const vilco_chunk_table* table, float lambda, int32_t share
 /* Every element has one owner thread: no atomics, no workspace, the same bits on every call.  16-byte accesses wherever src  */
 /* and acc are misaligned by the same amount, 4-byte accesses otherwise.  nchunks == 0 launches nothing.                       */
 int vilco_cl_accumulate(const vilco_chunk_table* table, int32_t op, float alpha, float beta, void* stream);
+/* A-GEM gradient projection (Chaudhry, Ranzato, Rohrbach, Elhoseiny: "Efficient Lifelong Learning with A-GEM", ICLR 2019,      */
+/* eq. 11; the reference has no gradient-projection method, so there is no line of it to cite).  g = the step's gradient, r =   */
+/* the gradient of a batch drawn from the replay memory, both taken over all entries of the table as ONE vector:               */
+/*   g.r < 0 and r.r > 0:   g_t[i] <- fmaf(-alpha, r_t[i], g_t[i]),  alpha = (float)(g.r / r.r)        for i < numel[t]          */
+/*   otherwise (no conflict, r = 0, a NaN dot):   alpha = 0 and g is neither read again nor written: it keeps its bits          */
+/* table rows (>= 2): grad (fp32, projected in place), ref (fp32, read only); numel[t] = elements of both.                      */
+/* partial = device float[2 * max(nchunks, 1)] (per-chunk fp32 sums of g r, then of r r: one read of the two streams, the       */
+/* block reduction order of vilco_grad_norm); out = device float[3] = {g.r, r.r, alpha}, the two sums formed in double over     */
+/* the partials and rounded once.  At most three launches (dot, finish, apply); the branch is taken on the device: no host      */
+/* read, no allocation.  Every element has one owner thread: no atomics, the same bits on every call.  16-byte accesses where   */
+/* grad and ref are misaligned by the same amount, 4-byte accesses otherwise.  nchunks == 0: out = {0, 0, 0}.                   */
+/* A null table, rows < 2, a null partial or out: VILCO_ERR_BADARG, before anything is launched.                                */
+int vilco_agem_project(const vilco_chunk_table* table, float* partial, float* out, void* stream);
 
 /* Deferred finishing (csrc/defer.hip).  The second stage of every two-stage column reduction (LayerNorm d-gamma / d-beta,  */
 /* bias and scale gradients, depthwise-tap gradients: reference autograd sums under blocks.py:152-166, 106-130, 628-641)  */

@@ -232,6 +232,7 @@ SIGNATURES = {
     "vilco_cl_distill_bwd": (C.c_int, [C.POINTER(DistillDesc), c_fp, c_fp, c_fp]),
     "vilco_cl_penalty": (C.c_int, [C.POINTER(ChunkTable), f32, i32, c_fp, c_fp, c_fp]),
     "vilco_cl_accumulate": (C.c_int, [C.POINTER(ChunkTable), i32, f32, f32, c_fp]),
+    "vilco_agem_project": (C.c_int, [C.POINTER(ChunkTable), c_fp, c_fp, c_fp]),
     "vilco_nms_workspace": (sz, [i64, i32]),
     "vilco_nms_1d": (C.c_int, [c_fp, c_fp, c_fp, i32, i64, f32, c_fp, c_fp, c_fp, sz, c_fp]),
     "vilco_softnms_1d": (C.c_int, [c_fp, c_fp, c_fp, i32, i64, f32, f32, f32, i32, i64, c_fp, c_fp, c_fp,

@@ -319,6 +319,78 @@ __global__ __launch_bounds__(OPT_THREADS) void si_consolidate_kernel(MultiArgs a
   }
 }
 
+// A-GEM (Chaudhry et al., ICLR 2019, "Efficient Lifelong Learning with A-GEM"): the step's gradient g is projected against the
+// replay memory's gradient r when the two conflict:  g <- g - (g.r / r.r) r  if g.r < 0.  rows: grad (projected in place), ref.
+// Three launches, the branch is taken on the device:
+//   dot     partial[c] = sum over chunk c of g r, partial[nchunks + c] = of r r: ONE read of the two streams, fp32 per-thread sums
+//           in sqnorm_kernel's order, then its wave / block tree (block_sum_to, once per sum with a barrier between: it owns one
+//           shared array).  A chunk with cnt == 0 writes two zeros.
+//   finish  one block: both runs summed in double; out = {g.r, r.r, alpha}, alpha = (float)(g.r / r.r) if g.r < 0 && r.r > 0,
+//           else 0 (a NaN dot fails the comparison: the gradient is left as it is)
+//   apply   alpha == 0: every block returns without a load or a store.  Otherwise g[i] = fmaf(-alpha, r[i], g[i]), one owner
+//           thread per element, in cl_accumulate_kernel's access pattern (16-byte where grad and ref share a misalignment).
+__global__ __launch_bounds__(OPT_THREADS) void agem_dot_kernel(MultiArgs a, float* __restrict__ partial, int nchunks) {
+  const ChunkView c = chunk_view(a);
+  const float* g = c.row<const float>(0);
+  const float* r = c.row<const float>(1);
+  float sd = 0.f, sr = 0.f;
+  for (long i = threadIdx.x; i < c.cnt; i += OPT_THREADS) {
+    const float rv = r[i];
+    sd += g[i] * rv;
+    sr += rv * rv;
+  }
+  block_sum_to(sd, partial + blockIdx.x);
+  __syncthreads();                               // thread 0 has read the shared array of the first sum
+  block_sum_to(sr, partial + nchunks + blockIdx.x);
+}
+
+__global__ __launch_bounds__(OPT_THREADS) void agem_finish_kernel(const float* __restrict__ partial, int nchunks,
+                                                                  float* __restrict__ out) {
+  const double dot = partials_sum(partial, nchunks);
+  __syncthreads();                               // every thread has read red[0] of the first sum
+  const double rr = partials_sum(partial + nchunks, nchunks);
+  if (threadIdx.x == 0) {
+    out[0] = (float)dot;
+    out[1] = (float)rr;
+    out[2] = (dot < 0.0 && rr > 0.0) ? (float)(dot / rr) : 0.f;
+  }
+}
+
+__device__ __forceinline__ void agem_apply_scalar(const float* r, float* g, long lo, long hi, float nalpha) {
+  for (long i = lo + threadIdx.x; i < hi; i += OPT_THREADS) g[i] = __fmaf_rn(nalpha, r[i], g[i]);
+}
+
+__global__ __launch_bounds__(OPT_THREADS) void agem_apply_kernel(MultiArgs a, const float* __restrict__ out) {
+  const float alpha = out[2];
+  if (alpha == 0.f) return;                      // no conflict: grad keeps its bits, no traffic
+  const float nalpha = -alpha;
+  const ChunkView c = chunk_view(a);
+  const long cnt = c.cnt;
+  float* g = c.row<float>(0);
+  const float* r = c.row<const float>(1);
+  // as cl_accumulate_kernel: 16-byte accesses over the part where BOTH streams are 16-byte aligned, scalar head and tail
+  const unsigned mg = (unsigned)(reinterpret_cast<uintptr_t>(g) & 15), mr = (unsigned)(reinterpret_cast<uintptr_t>(r) & 15);
+  long head = cnt, nvec = 0;
+  if (mg == mr && (mg & 3) == 0) {
+    head = ((16 - mg) & 15) >> 2;
+    if (head > cnt) head = cnt;
+    nvec = (cnt - head) >> 2;
+  }
+  agem_apply_scalar(r, g, 0, head, nalpha);
+  const float4* r4 = reinterpret_cast<const float4*>(r + head);
+  float4* g4 = reinterpret_cast<float4*>(g + head);
+  for (long i = threadIdx.x; i < nvec; i += OPT_THREADS) {
+    const float4 x = r4[i];
+    float4 v = g4[i];
+    v.x = __fmaf_rn(nalpha, x.x, v.x);
+    v.y = __fmaf_rn(nalpha, x.y, v.y);
+    v.z = __fmaf_rn(nalpha, x.z, v.z);
+    v.w = __fmaf_rn(nalpha, x.w, v.w);
+    g4[i] = v;
+  }
+  agem_apply_scalar(r, g, head + 4 * nvec, cnt, nalpha);
+}
+
 struct F16Vals { float v[16]; };
 __global__ void store_f32_kernel(float* __restrict__ dst, F16Vals vals, int n) {
   if ((int)threadIdx.x < n) dst[threadIdx.x] = vals.v[threadIdx.x];
@@ -379,6 +451,18 @@ extern "C" int vilco_grad_norm(const vilco_chunk_table* table, float max_norm, f
   const int nchunks = table->nchunks;
   if (nchunks > 0) hipLaunchKernelGGL(sqnorm_kernel, dim3(nchunks), dim3(OPT_THREADS), 0, s, a, partial);
   hipLaunchKernelGGL(clip_coef_kernel, dim3(1), dim3(OPT_THREADS), 0, s, partial, nchunks, max_norm, norm_coef);
+  return vilco_launch_status();
+}
+
+extern "C" int vilco_agem_project(const vilco_chunk_table* table, float* partial, float* out, void* stream) {
+  MultiArgs a;
+  if (!table_args(table, 2, nullptr, &a) || !partial || !out) return VILCO_ERR_BADARG;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const int nchunks = table->nchunks;
+  const dim3 grid(nchunks), block(OPT_THREADS);
+  if (nchunks > 0) hipLaunchKernelGGL(agem_dot_kernel, grid, block, 0, s, a, partial, nchunks);
+  hipLaunchKernelGGL(agem_finish_kernel, dim3(1), block, 0, s, partial, nchunks, out);
+  if (nchunks > 0) hipLaunchKernelGGL(agem_apply_kernel, grid, block, 0, s, a, out);
   return vilco_launch_status();
 }
 

@@ -719,6 +719,14 @@ def _cached(w, tag, build):
     return val
 
 
+def forget_weight_planes(params):
+    """drop the cached planes / images of these parameters, keeping their max|w| tags.  For a forward that is NOT followed by
+    an update (A-GEM's reference pass): the next step would otherwise find the planes valid and, when it is being captured,
+    record no pack -- a replayed graph must pack the weights it reads inside itself (vilco_amd/graph.py)."""
+    for p in params:
+        p.__dict__.pop("_vilco_cache", None)
+
+
 def tag_weight_amax(p, parts, n):
     """max|p| partials of parameter p left by whoever wrote it (FusedOptimizer.step: vilco_optim_desc.chunk_amax); valid until
     p's version counter or the weight generation moves.  Call after weights_changed()."""
@@ -2420,6 +2428,40 @@ def cl_accumulate(srcs, accs, op, alpha, beta, numels=None):
         _cl_plan[key] = ChunkPlan(numels, dev)
     ptrs = torch.tensor([[s.data_ptr() for s in srcs], [a.data_ptr() for a in accs]], dtype=torch.int64).to(dev, non_blocking=True)
     _lib.check(_lib.load().vilco_cl_accumulate(C.byref(_cl_plan[key].table(ptrs, 2)), int(op), alpha, beta, _stream()))
+
+
+# ---------------------------------------------------------------------------------------- A-GEM gradient projection
+_agem_plan = {}         # the last (ChunkPlan, partials), by (numels, device): a task asks for the same one every iteration
+
+
+def agem_project(grads, refs, device=None):
+    """vilco_agem_project (Chaudhry et al., ICLR 2019): with g = all of `grads` and r = all of `refs` taken as one vector each,
+    grads[t] -= (g.r / r.r) * refs[t] in place when g.r < 0 and r.r > 0; otherwise nothing is written.  Three launches, the
+    branch is taken on the device.  grads / refs: lists of contiguous fp32 device tensors with pairwise equal numel.
+    -> out, a device tensor [3] = {g.r, r.r, alpha} (alpha = 0: no projection), not synchronised.  Empty lists give zeros
+    (on `device`, default the current one)."""
+    grads, refs = list(grads), list(refs)
+    if len(grads) != len(refs):
+        raise RuntimeError("agem_project: %d gradients for %d reference gradients" % (len(grads), len(refs)))
+    _chk(*grads)
+    _chk(*refs)
+    numels = tuple(g.numel() for g in grads)
+    if any(r.numel() != n for r, n in zip(refs, numels)):
+        raise RuntimeError("agem_project: a gradient and its reference gradient differ in their element count")
+    dev = grads[0].device if grads else torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+    if any(t.device != dev for t in grads + refs):
+        raise RuntimeError("agem_project: all tensors must live on one device")
+    key = (numels, dev)
+    if key not in _agem_plan:
+        _agem_plan.clear()
+        plan = ChunkPlan(numels, dev)
+        _agem_plan[key] = (plan, torch.empty(2 * max(plan.nchunks, 1), dtype=torch.float32, device=dev))
+    plan, partial = _agem_plan[key]
+    ptrs = torch.tensor([[g.data_ptr() for g in grads], [r.data_ptr() for r in refs]] if grads else [[0], [0]],
+                        dtype=torch.int64).to(dev, non_blocking=True)
+    out = torch.empty(3, dtype=torch.float32, device=dev)
+    _lib.check(_lib.load().vilco_agem_project(C.byref(plan.table(ptrs, 2)), partial.data_ptr(), out.data_ptr(), _stream()))
+    return out
 
 
 # ---------------------------------------------------------------------------------------- BiC stage 2 over cached logits

@@ -12,6 +12,7 @@ reference driver MQ/train_cl.py:206-389 (+ load_best_checkpoint :31-40), written
       if another task follows: augment_classification(num_next_classes), EWC / MAS consolidation, NEW optimizer
           and scheduler                                             (:373-389)
       [cl_cfg.name 'si' (ours): si_begin_task before the epochs, consolidation right after them, before the reload]
+      [cl_cfg.name 'agem' (ours): once the memory holds clips, a reference gradient per iteration and the projection]
 
 What is ours rather than the reference's: the stream is any iterable with QILSetTask's contract
 (`(data, loader, num_next_classes)` per task, a `.memory` attribute; utils/cl_stream.py has an in-memory one --
@@ -139,10 +140,20 @@ def run_episodes(cfg, model, train_stream, validate=None, ckpt_folder=None, gpu_
     collectives): inside the epoch loop only the main rank calls it (train_cl.py:283), the others wait at a barrier.
     use_graph: replay the iterations as hipGraphs (vilco_amd/graph.py; a fresh GraphedStep per optimizer, i.e. per task).
     keep_history: keep every iteration's loss dict (device scalars) in the log; off for long runs.
+    cl_cfg.name 'agem' (ours; cl_methods/agem.py): from the first task that finds `train_stream.memory` non-empty, every
+    iteration takes a reference gradient on a batch of cl_cfg['agem_batch'] (default: the loader's batch size) memory clips
+    -- drawn by a MemorySampler seeded with cl_cfg['agem_seed'] (default: the stream's seed) -- and projects the task
+    batch's gradient against it before the clip and the update; before that, training is plain.  A fresh AGEM per task;
+    with keep_history the task's log entry gets 'agem' = [out, ...], one device tensor {g.r, r.r, alpha} per iteration.
+    A-GEM proper wants a stream built with train_enable=False, whose task loader does not mix the memory in; with
+    train_enable=True the method is replay plus projection.  With use_graph the task batch's step replays as usual and
+    the reference pass stays eager between the replays.  Not with a reducer (ValueError).
     Returns (model, optimizer, scheduler, log) with log = list of per-task dicts."""
+    from .cl_methods import agem as agem_mod
     is_main = int(os.environ.get("LOCAL_RANK", "0")) == 0
     imp_opts = regularizers.importance_options(cfg['cl_cfg'])      # a bad value fails here, not after the first task
     use_si = _si_check(cfg, start_epoch)
+    use_agem = agem_mod.check_supported(cfg['cl_cfg']['name'], reducer)
     optimizer = make_optimizer(model, cfg['opt'])
 
     def make_graph(opt):
@@ -170,6 +181,13 @@ def run_episodes(cfg, model, train_stream, validate=None, ckpt_folder=None, gpu_
         ck_name = 'best_task_{:03d}_performance.pth.tar'.format(j)
         if use_si:
             regularizers.si_begin_task(model, optimizer)      # the head has grown, this task's optimizer exists
+        agem = None
+        if use_agem and train_stream.memory:
+            mem_sampler = agem_mod.MemorySampler(train_stream.memory, cfg['cl_cfg'].get('agem_batch', loader.batch_size),
+                                             cfg['cl_cfg'].get('agem_seed', getattr(train_stream, 'seed', 0)))
+            agem = agem_mod.AGEM(model, mem_sampler, trace=[] if keep_history else None)
+            if keep_history:
+                entry['agem'] = agem.trace
         for epoch in range(start_epoch, max_epochs):
             sampler = getattr(loader, 'sampler', None)
             if sampler is not None and hasattr(sampler, 'set_epoch'):
@@ -180,7 +198,7 @@ def run_episodes(cfg, model, train_stream, validate=None, ckpt_folder=None, gpu_
                                    clip_grad_l2norm=cfg['train_cfg']['clip_grad_l2norm'], print_freq=print_freq,
                                    logger=logger, cl_name=cfg['cl_cfg']['name'], reg_lambda=cfg['cl_cfg']['reg_lambda'],
                                    prev_out_cls_logits_dict=prev_logits, current_task_id=j, reducer=reducer, graph=graph,
-                                   keep_history=keep_history or on_step_history is not None)
+                                   keep_history=keep_history or on_step_history is not None, agem=agem)
             if keep_history:
                 entry['history'].append(hist)
             if on_step_history is not None:
@@ -259,9 +277,12 @@ def run_episodes_bic(cfg, model, train_stream, validate=None, ckpt_folder=None, 
     (:622).  use_graph: replay the stage-1 iterations as hipGraphs, as in `run_episodes` (a fresh GraphedStep per optimizer,
     i.e. per task; from the second task on the captured step holds the bias correction, ops.bic_correct, which reads alpha /
     beta from the layers' memory).  Single process (the reference's stage 2 is not data parallel either).  Returns (model, optimizer, scheduler,
-    log); a task's log entry has 'bic' = {'alpha', 'beta', 'before', 'after', 'losses'} after a stage 2."""
+    log); a task's log entry has 'bic' = {'alpha', 'beta', 'before', 'after', 'losses'} after a stage 2.
+    cl_cfg.name 'agem' is refused (ValueError): only `run_episodes` projects gradients."""
+    from .cl_methods import agem as agem_mod
     from .cl_methods.bic import BiCCache, fit_bias_layer, newest_split
     from .utils.cl_stream import DistributedBatchLoader
+    agem_mod.check_supported(cfg['cl_cfg']['name'], driver='run_episodes_bic')
     optimizer = make_optimizer(model, cfg['opt'])
 
     def make_graph(opt):
@@ -403,8 +424,11 @@ def run_episodes_nlq(cfg, model, train_stream, val_stream, evaluator, ckpt_folde
     val_stream: `get_valSet_by_taskNum(n)` -> [(loader with batch size 1, #templates), ...] (cl_benchmark.py:60-74);
     evaluator: `.dataset`, `.evaluate(records, verbose) -> (performance[[R@1, ...]], str)` (libs/utils/metrics.py
     ReferringRecall; outside the hot path).  on_validate(kind, task, epoch, r1) is called after every validation.
+    cl_cfg.name 'agem' is refused (ValueError): only `run_episodes` projects gradients.
     Returns (model, optimizer, scheduler, log)."""
+    from .cl_methods import agem as agem_mod
     from .utils import train_utils_nlq as tu
+    agem_mod.check_supported(cfg['cl_cfg']['name'], driver='run_episodes_nlq')
     is_main = int(os.environ.get("LOCAL_RANK", "0")) == 0
     imp_opts = regularizers.importance_options(cfg['cl_cfg'])
     use_si = _si_check(cfg, start_epoch)

@@ -360,7 +360,8 @@ class AverageMeter(object):
 
 def train_one_epoch(train_loader, model, optimizer, scheduler, curr_epoch, n_gpu=1, model_ema=None,
                     clip_grad_l2norm=-1, tb_writer=None, print_freq=20, logger=None, cl_name=None, reg_lambda=0.0,
-                    prev_out_cls_logits_dict=None, current_task_id=0, reducer=None, graph=None, keep_history=True):
+                    prev_out_cls_logits_dict=None, current_task_id=0, reducer=None, graph=None, keep_history=True,
+                    agem=None):
     """One epoch of the continual-learning training loop (train_utils.py:278-423), same arguments.  Per iteration:
     zero_grad, forward with `task_id` and the cached iCaRL/BiC logits of the batch's videos, backward of
     final_loss (+ the EWC / MAS / SI penalty of cl_name, applied as one multi-tensor kernel that adds its gradient to
@@ -369,6 +370,9 @@ def train_one_epoch(train_loader, model, optimizer, scheduler, curr_epoch, n_gpu
     graph: a vilco_amd.graph.GraphedStep built over (model, optimizer, clip_grad_l2norm[, reducer]) -- iterations whose
     device half can run alone are then replayed as hipGraphs instead of launched kernel by kernel; the others (and the
     first iterations of every new batch shape) take the eager path inside it.
+    agem: a cl_methods.agem.AGEM -- every iteration first takes the reference gradient of a batch from the replay memory
+    (`agem.reference_pass`, eager also when the task batch's step is replayed), and `agem.project()` runs where the penalty
+    runs: after backward (and after the reducer would have finished), before the clip and the update.
     Returns the list of per-iteration loss dicts (device scalars; empty with keep_history=False), which the reference
     does not -- harmless."""
     from ..cl_methods import regularizers
@@ -387,6 +391,11 @@ def train_one_epoch(train_loader, model, optimizer, scheduler, curr_epoch, n_gpu
         # after the gradient average equals averaging it.
         last_pen[0] = regularizers.apply_penalty(model, reg_lambda, kind=cl_name) if cl_name in ('ewc', 'mas', 'si') else None
 
+    def project_and_penalty():
+        agem.project()          # the task batch's gradient against the memory batch's, on the pointers p.grad holds now
+        penalty()
+    between = penalty if agem is None else project_and_penalty
+
     for iter_idx, video_list in enumerate(train_loader, 0):
         prev = []
         for v in video_list:
@@ -394,8 +403,10 @@ def train_one_epoch(train_loader, model, optimizer, scheduler, curr_epoch, n_gpu
                 prev.append(prev_out_cls_logits_dict[v['video_id']])
         if prev and model.cl_name == 'bic':
             prev = prev[-1]        # train_bic_one_epoch (train_utils.py:493): BiC's term walks ONE clip's per-level list
+        if agem is not None:
+            agem.reference_pass(current_task_id)
         if graph is not None:
-            graph.between = penalty
+            graph.between = between
             losses = graph(video_list, task_id=current_task_id, prev_out_cls_logits=prev)
         else:
             optimizer.zero_grad(set_to_none=True)
@@ -405,7 +416,7 @@ def train_one_epoch(train_loader, model, optimizer, scheduler, curr_epoch, n_gpu
             losses['final_loss'].backward()
             if reducer is not None:
                 reducer.finish()
-            penalty()
+            between()
             optimizer.step(clip_grad_l2norm=clip_grad_l2norm)
         if last_pen[0] is not None:
             losses['final_loss'] = losses['final_loss'].detach() + last_pen[0]
