@@ -1,5 +1,5 @@
 #!/bin/bash
-# Device-code identity of two builds of csrc/attn.hip:  tools/attn_device_diff.sh OLD/attn.o NEW/attn.o
+# Device-code identity of two builds of one csrc/*.hip file (attn.hip, gemm.hip, ...):  tools/device_diff.sh OLD/x.o NEW/x.o
 # Extracts the gfx950 code object of each, compares the bytes and, kernel by kernel (symbols sorted by name, so an order
 # change in the object does not count), the disassembly.  Exit 0: every kernel's instructions are identical.
 set -euo pipefail

@@ -16,7 +16,10 @@
 // precision 0 = NP 2 bf16 ("split"), 1 = NP 1 (plain bf16), 2 = NP 3 bf16 ("split3": numerically an fp32 GEMM),
 // 3 = two fp16 parts of the per-tensor scaled operands ("f16x2": 22 bits, 3 MFMAs; pack.h; the default).
 // Reference arithmetic replaced: see include/vilco_hip.h (vilco_gemm).
+#include <algorithm>
+#include <climits>
 #include <cstdlib>
+#include <type_traits>
 #include <utility>
 #include <vector>
 #include "common.h"
@@ -268,6 +271,14 @@ __device__ __forceinline__ void gemm_epilogue(const GArgs& g, f32x4 (&acc)[MI][4
   }
 }
 
+// dynamic LDS of gemm_pp_kernel: two stages of NP parts of (A tile | B tile) -- k-major tiles in [32][rows + 16] rows -- or the
+// epilogue's staged rows where those take more
+template <int BM, int NP, bool AKM, bool BKM>
+constexpr size_t pp_lds() {
+  constexpr size_t a_el = AKM ? 32 * ((BM == 192 ? 256 : BM) + 16) : BM * 32, b_el = BKM ? 32 * (BN + 16) : BN * 32;
+  constexpr size_t pipe = (size_t)2 * NP * (a_el + b_el) * sizeof(__bf16), epi = (size_t)8 * 16 * (BM / 64) * EPI_LD * 4;
+  return pipe > epi ? pipe : epi;
+}
 // K2 (r03): the single-part products (precision 4: weight gradients with long contractions) keep the TWO-slot layout of
 // the two-part kernels but fill the slots with part 0 of two CONSECUTIVE K-steps: a barrier interval then covers 64
 // elements of K -- 2 MFMAs per fragment pair, the same fragment reads and staging traffic as a two-part step.  With one
@@ -835,6 +846,9 @@ __device__ __forceinline__ void gemm_gl_body(const GArgs& g, const int z) {
   STAMPX(3);
 }
 
+// dynamic LDS of gemm_gl_body (the plain and the grouped kernel): two stages x two slots x (A + B) x 128 B
+template <int BM>
+constexpr size_t gl_lds() { return (size_t)4 * (BM + BN) * 128; }
 template <int BM, bool AKM, bool BKM>
 __global__ __launch_bounds__(512) void gemm_gl_kernel(GArgs g) {
   gemm_gl_body<BM, AKM, BKM>(g, (int)blockIdx.z);
@@ -866,6 +880,8 @@ __global__ __launch_bounds__(512) void gemm_gl_group_kernel(GArgsN gg) {
 // epilogue, which is the tiled kernels' own (store_out4: bias, activation, pre-activation, row masks, dropout, residual, beta,
 // max|C|).  Both operands k-contiguous (NT), precision 3 (two fp16 parts, three MFMAs per fragment pair), unbatched.
 constexpr int SK_LD = 68;                                       // floats per row of a wave's partial tile in LDS (EPI_LD's reasons)
+template <int BMS>
+constexpr size_t skinny_lds() { return (size_t)8 * BMS * SK_LD * 4; }      // [8 waves][BMS][SK_LD] floats
 template <int BMS>
 __global__ __launch_bounds__(512) void gemm_skinny_kernel(GArgs g) {
   constexpr int MB = BMS / 16;
@@ -1029,248 +1045,282 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(GArgs g, int nz) {
 
 // ------------------------------------------------------------------------------------------ host side
 inline long align_up(long x, long a) { return (x + a - 1) / a * a; }
-inline bool use_km() {
-  static int v = -1;
-  if (v < 0) { const char* e = getenv("VILCO_GEMM_KM"); v = e ? atoi(e) : 1; }
-  return v != 0;
-}
 constexpr long SCALE_BYTES = 2 * AMAX_MAX_BLOCKS * 4 + 256;   // fp16 x2 format: amax partials of A and B, then {1/sA, sA, 1/sB, sB}
 constexpr long PACK_HDR = VILCO_PACK_HDR;                      // vilco_pack buffers: amax partials, {1/s, s}, then the planes
 
-inline bool k2_enabled() {
-  static const bool on = [] { const char* e = getenv("VILCO_GEMM_K2"); return !(e && e[0] == '0'); }();
-  return on;
+// ---- process-wide switches: read from the environment once per process (the plan is made up to three times per launch)
+inline bool env_flag(const char* name, bool dflt) { const char* e = getenv(name); return e ? e[0] != '0' : dflt; }
+inline int env_int(const char* name, int dflt, int min) {      // values below `min` fall back to the default
+  const char* e = getenv(name); const int x = e ? atoi(e) : dflt; return x >= min ? x : dflt;
 }
-struct Tune { int bm, ks; };
-inline Tune& tune() {       // env read once per process (the plan is made twice per launch); vilco_gemm_force changes it
-  static Tune t = [] {
-    const char* b = getenv("VILCO_GEMM_BM"); const char* k = getenv("VILCO_GEMM_KS");
-    return Tune{b ? atoi(b) : 0, k ? atoi(k) : 0};
-  }();
-  return t;
-}
-
-struct Plan {
-  int NP, Kp, BM, ksplit, kchunk;
-  bool a_tr, b_tr;
-  bool a_km, b_km;                // operand consumed k-major from natural-layout planes (ping-pong kernel only)
-  int a_tap, b_tap;               // pack tap mode
-  int a_out_rows, b_out_rows;     // plane rows written by the kc pack
-  long a_plane, b_plane;          // elements per part (all batches)
-  long a_batch, b_batch;          // elements per batch inside a part
-  int a_nbo, a_nbi, b_nbo, b_nbi;
-  long a_bytes, b_bytes, part_bytes;
-  long split_stride;
-  bool tapkm;                     // k=3 conv weight gradient as a k-major x k-major product over zero-padded token rows (make_plan)
-  bool k2;                        // precision 4: a barrier interval of the kernel covers two K-steps (64 elements of K)
-  bool gl;                        // gemm_gl_kernel (LDS-DMA staging, 64-element chunks): the fp16 x2 products
-  bool skinny;                    // gemm_skinny_kernel (few rows, NT, precision 3): BM = its rows per workgroup (16 | 32)
+struct Config {
+  const bool km = env_int("VILCO_GEMM_KM", 1, INT_MIN) != 0;   // k-major consumption (a number: whatever atoi reads as 0 is off)
+  const bool k2 = env_flag("VILCO_GEMM_K2", true);
+  const bool sub192 = env_flag("VILCO_GEMM_SUB192", true);
+  const bool dw_tall = env_flag("VILCO_GEMM_DW_TALL", true);
+  const bool tapkm = env_flag("VILCO_CONV_DW_KM", true);
+  const bool group = env_flag("VILCO_GEMM_GROUP", true);
+  const int skinny_max_rows = env_int("VILCO_GEMM_SKINNY_M", 640, 1);
+  // largest M that takes 16-row workgroups (more workgroups, more re-reads of B).  Inside the planned range (K <= 768, N <= 1024) 16 rows
+  // are never slower (profiles/r06_skinny_bm16.txt: 154 x 1024 x 768 9.8 us against 11.4 at 32 rows, 512 x 512 x 512 7.6 against 8.6).
+  const int skinny_bm16_rows = env_int("VILCO_GEMM_SKINNY_BM16", 640, 0);
+  const int skinny_max_k = env_int("VILCO_GEMM_SKINNY_K", 768, 1);
+  // the three that vilco_gemm_set_skinny / vilco_gemm_force change
+  bool skinny = env_flag("VILCO_GEMM_SKINNY", true);
+  int force_bm = env_int("VILCO_GEMM_BM", 0, INT_MIN), force_ks = env_int("VILCO_GEMM_KS", 0, INT_MIN);
 };
-
-inline bool& skinny_enabled() {
-  static bool on = [] { const char* e = getenv("VILCO_GEMM_SKINNY"); return !(e && e[0] == '0'); }();
-  return on;
-}
-inline int skinny_max_rows() {
-  static const int v = [] { const char* e = getenv("VILCO_GEMM_SKINNY_M"); const int x = e ? atoi(e) : 640; return x > 0 ? x : 640; }();
-  return v;
-}
-// largest M that takes 16-row workgroups (more workgroups, more re-reads of B).  Inside the planned range (K <= 768, N <= 1024) 16 rows
-// are never slower (profiles/r06_skinny_bm16.txt: 154 x 1024 x 768 9.8 us against 11.4 at 32 rows, 512 x 512 x 512 7.6 against 8.6).
-inline int skinny_bm16_rows() {
-  static const int v = [] { const char* e = getenv("VILCO_GEMM_SKINNY_BM16"); const int x = e ? atoi(e) : 640; return x >= 0 ? x : 640; }();
-  return v;
-}
-inline int skinny_max_k() {
-  static const int v = [] { const char* e = getenv("VILCO_GEMM_SKINNY_K"); const int x = e ? atoi(e) : 768; return x > 0 ? x : 768; }();
-  return v;
-}
-inline bool tapkm_enabled() {
-  static const bool v = [] { const char* e = getenv("VILCO_CONV_DW_KM"); return !(e && e[0] == '0'); }();
-  return v;
+inline Config& config() { static Config c; return c; }
+// 16-bit parts per operand element.  Precision 4 multiplies the leading parts of fp16 x2 planes: the product's own packs write two.
+// `pack_abi`: vilco_pack_bytes / vilco_pack_item_bytes have always sized THREE parts for precision 4 (vilco_pack_many refuses that
+// precision, so nothing is packed into such a buffer) and go on doing so: open, DESIGN_LOG.md R18.1.
+inline int parts_of_precision(int precision, bool pack_abi = false) {
+  if (precision == 1) return 1;
+  if (precision == 0 || precision == 3) return 2;
+  return (precision == 4 && !pack_abi) ? 2 : 3;
 }
 
-void make_plan(const vilco_gemm_desc* d, Plan& p) {
-  p.NP = d->precision == 1 ? 1 : ((d->precision == 0 || d->precision == 3 || d->precision == 4) ? 2 : 3);
-  p.Kp = (int)align_up(d->K > 0 ? d->K : 1, 32);
-  p.a_tr = !d->a_kcontig;
-  p.b_tr = !d->b_kcontig;
-  p.a_tap = p.b_tap = 0;
-  p.tapkm = false;
-  p.a_out_rows = d->M;
-  p.b_out_rows = d->N;
-  long a_batch = (long)d->M * p.Kp, b_batch = (long)d->N * p.Kp;
+// elements of one part of a packed image: the natural [rows32][cols32] layout, and the k=3 convs' zero-padded per-sequence one
+// (vilco_pack_item.seq_len): nseq * (T + 2) padded rows + enough zero rows for both readers -- the forward / dX conv's overlapped
+// spans (operand_layout: a.out_rows) and the weight-gradient product's contraction over the padded rows (Kp + 3 + one K-step)
+inline long natural_image_elems(long rows, long cols) { return align_up(rows, 32) * align_up(cols, 32); }
+inline long seq_image_elems(long nseq, long T, long cols) { return align_up(vilco_tap_plane_rows(nseq, T) * cols, 8); }
+
+// ---- the plan, part 1: operand layout
+struct Side {
+  bool tr, km;          // this call's pack transposes the source | the kernel consumes the operand k-major from natural-layout planes
+  int tap, out_rows;    // pack tap mode (pack.h), plane rows written by the kc pack
+  int nbo, nbi;         // batch levels the planes vary with
+  long pack_batch;      // elements per batch inside a part as this call's own pack lays them out (sizes `bytes`, bounds the 32-bit offsets)
+  long bytes;           // this operand's share of the workspace: reserved whether or not planes are handed in
+  long batch, plane;    // elements per batch inside a part / per part (all batches) of the planes the KERNEL reads: the own pack's,
+                        // or the pre-packed image's (vilco_pack: [part][batch][rows32][cols32], or the per-sequence image)
+};
+struct Layout { int NP, Kp; bool tapkm; Side a, b; };   // tapkm: k=3 conv weight gradient as a k-major x k-major product over zero-padded token rows
+
+// dW[co][j*Cin + c] = sum_tok dZ[tok][co] X[tok + j - 1][c] (zero across sequence ends).  Round 4: no transposing pack.
+// Both operands are packed the way the forward conv packs its input -- token rows in their natural layout, one zero row
+// before and after every sequence (tap mode 1) -- and the product contracts over those PADDED rows r: with dZ' starting
+// at padded row 1, row r of dZ' meets rows r, r+1, r+2 of X' for the taps j = 0, 1, 2; X' has row stride Cin, so
+// "row r, columns j*Cin + c" of the virtual [rows][3 Cin] operand is the plain address r*Cin + j*Cin + c: the kernel's
+// ordinary k-major tile read (the overlapped-row trick of the forward conv, turned on its side).  The padding rows of
+// dZ' are zero, so whatever X' holds opposite them (the next sequence's first token) contributes nothing.
+bool tapkm_layout(const vilco_gemm_desc* d, Layout& L) {
+  if (!(config().km && config().tapkm && (d->tapC % 8) == 0 && (d->M % 8) == 0 && d->tapT > 0 && (d->K % d->tapT) == 0 &&
+        d->batch_outer == 1 && d->batch_inner == 1))
+    return false;
+  Side &a = L.a, &b = L.b;
+  const long nseq = d->K / d->tapT;
+  L.Kp = (int)align_up(nseq * (d->tapT + 2) - 1, 32);
+  a.tap = b.tap = 1; a.tr = b.tr = false; a.km = b.km = true;
+  a.out_rows = L.Kp + 1 + 32; b.out_rows = L.Kp + 3 + 32;          // + the skipped first row (A) + one K-step of over-read
+  a.pack_batch = (long)a.out_rows * d->M; b.pack_batch = (long)b.out_rows * d->tapC;
+  return true;
+}
+// elements per batch of the planes vilco_pack made of an operand: the natural image of its matrix, or -- tap mode 1 -- the convs'
+// per-sequence image, whose rows are the tokens: M of them, tapC wide (taps on A), or K of them, M / tapC wide (the weight gradient's
+// dZ / X).  (a_planes_seq / b_planes_seq do not choose the image: the product does, and gemm_prepare refuses flags that disagree.)
+long prepacked_a(const vilco_gemm_desc* d, const Layout& L) {
+  if (L.a.tap != 1) return natural_image_elems(d->M, L.Kp);
+  return L.tapkm ? seq_image_elems(d->K / d->tapT, d->tapT, d->M) : seq_image_elems(d->M / d->tapT, d->tapT, d->tapC);
+}
+long prepacked_b(const vilco_gemm_desc* d, const Layout& L) {
+  return L.tapkm ? seq_image_elems(d->K / d->tapT, d->tapT, d->tapC) : natural_image_elems(d->N, L.Kp);
+}
+// batch levels, workspace share and the strides the kernel reads, from the own pack's elements per batch (s.pack_batch) and the
+// pre-packed image's (`image`, < 0: the call packs the operand itself)
+void finish_side(const vilco_gemm_desc* d, int NP, Side& s, long so, long si, long image) {
+  s.nbo = (so && d->batch_outer > 1) ? d->batch_outer : 1;
+  s.nbi = (si && d->batch_inner > 1) ? d->batch_inner : 1;
+  s.pack_batch = align_up(s.pack_batch, 8);
+  s.bytes = align_up(s.pack_batch * s.nbo * s.nbi * NP * 2, 256);
+  s.batch = image >= 0 ? image : s.pack_batch;
+  s.plane = s.batch * s.nbo * s.nbi;
+}
+Layout operand_layout(const vilco_gemm_desc* d, bool a_prepacked, bool b_prepacked) {
+  Layout L;
+  Side &a = L.a, &b = L.b;
+  L.NP = parts_of_precision(d->precision);
+  L.Kp = (int)align_up(d->K > 0 ? d->K : 1, 32);
+  a.tr = !d->a_kcontig; b.tr = !d->b_kcontig;
+  a.tap = b.tap = 0;
+  a.out_rows = d->M; b.out_rows = d->N;
+  a.pack_batch = (long)d->M * L.Kp; b.pack_batch = (long)d->N * L.Kp;
   // k-major consumption instead of a transposing pack: plain (no tap, unbatched) operands, 16-byte aligned rows
-  const bool km_ok = use_km() && d->tap_operand == VILCO_TAP_NONE;
-  p.a_km = km_ok && p.a_tr;
-  p.b_km = km_ok && p.b_tr;
-  if (p.a_km) { p.a_tr = false; p.a_out_rows = p.Kp; a_batch = (long)p.Kp * align_up(d->M, 32); }
-  if (p.b_km) { p.b_tr = false; p.b_out_rows = p.Kp; b_batch = (long)p.Kp * align_up(d->N, 32); }
-  if (d->tap_operand == VILCO_TAP_A) {
-    if ((d->tapC % 8) == 0) {
-      p.a_tap = 1;
-      const long nseq = d->M / d->tapT;
-      const long slack = (p.Kp + d->tapC - 1) / d->tapC;       // zero rows covering the last spans' over-read
-      p.a_out_rows = (int)(nseq * (d->tapT + 2) + slack);
-      a_batch = (long)p.a_out_rows * d->tapC;
-    } else {
-      p.a_tap = 2;
-    }
-  } else if (d->tap_operand == VILCO_TAP_B) {
-    // dW[co][j*Cin + c] = sum_tok dZ[tok][co] X[tok + j - 1][c] (zero across sequence ends).  Round 4: no transposing pack.
-    // Both operands are packed the way the forward conv packs its input -- token rows in their natural layout, one zero row
-    // before and after every sequence (tap mode 1) -- and the product contracts over those PADDED rows r: with dZ' starting
-    // at padded row 1, row r of dZ' meets rows r, r+1, r+2 of X' for the taps j = 0, 1, 2; X' has row stride Cin, so
-    // "row r, columns j*Cin + c" of the virtual [rows][3 Cin] operand is the plain address r*Cin + j*Cin + c: the kernel's
-    // ordinary k-major tile read (the overlapped-row trick of the forward conv, turned on its side).  The padding rows of
-    // dZ' are zero, so whatever X' holds opposite them (the next sequence's first token) contributes nothing.
-    if (use_km() && tapkm_enabled() && (d->tapC % 8) == 0 && (d->M % 8) == 0 && d->tapT > 0 && (d->K % d->tapT) == 0 &&
-        d->batch_outer == 1 && d->batch_inner == 1) {
-      const long nseq = d->K / d->tapT;
-      p.tapkm = true;
-      p.Kp = (int)align_up(nseq * (d->tapT + 2) - 1, 32);
-      p.a_tap = p.b_tap = 1;
-      p.a_tr = p.b_tr = false;
-      p.a_km = p.b_km = true;
-      p.a_out_rows = p.Kp + 1 + 32;          // + the skipped first row + one K-step of over-read
-      p.b_out_rows = p.Kp + 3 + 32;
-      a_batch = (long)p.a_out_rows * d->M;
-      b_batch = (long)p.b_out_rows * d->tapC;
-    } else {
-      p.b_tap = 3;
-    }
+  const bool km_ok = config().km && d->tap_operand == VILCO_TAP_NONE;
+  a.km = km_ok && a.tr; b.km = km_ok && b.tr;
+  if (a.km) { a.tr = false; a.out_rows = L.Kp; a.pack_batch = (long)L.Kp * align_up(d->M, 32); }
+  if (b.km) { b.tr = false; b.out_rows = L.Kp; b.pack_batch = (long)L.Kp * align_up(d->N, 32); }
+  L.tapkm = d->tap_operand == VILCO_TAP_B && tapkm_layout(d, L);
+  if (d->tap_operand == VILCO_TAP_B && !L.tapkm) b.tap = 3;
+  if (d->tap_operand == VILCO_TAP_A && (d->tapC % 8) != 0) a.tap = 2;
+  if (d->tap_operand == VILCO_TAP_A && (d->tapC % 8) == 0) {
+    a.tap = 1;
+    const long nseq = d->M / d->tapT;
+    const long slack = (L.Kp + d->tapC - 1) / d->tapC;       // zero rows covering the last spans' over-read
+    a.out_rows = (int)(nseq * (d->tapT + 2) + slack);
+    a.pack_batch = (long)a.out_rows * d->tapC;
   }
-  p.a_nbo = (d->sAo && d->batch_outer > 1) ? d->batch_outer : 1;
-  p.a_nbi = (d->sAi && d->batch_inner > 1) ? d->batch_inner : 1;
-  p.b_nbo = (d->sBo && d->batch_outer > 1) ? d->batch_outer : 1;
-  p.b_nbi = (d->sBi && d->batch_inner > 1) ? d->batch_inner : 1;
-  p.a_batch = align_up(a_batch, 8);
-  p.b_batch = align_up(b_batch, 8);
-  p.a_plane = p.a_batch * p.a_nbo * p.a_nbi;
-  p.b_plane = p.b_batch * p.b_nbo * p.b_nbi;
-  p.a_bytes = align_up(p.a_plane * p.NP * 2, 256);
-  p.b_bytes = align_up(p.b_plane * p.NP * 2, 256);
+  finish_side(d, L.NP, a, d->sAo, d->sAi, a_prepacked ? prepacked_a(d, L) : -1);
+  finish_side(d, L.NP, b, d->sBo, d->sBi, b_prepacked ? prepacked_b(d, L) : -1);
+  return L;
+}
 
-  const long nbatch = (long)d->batch_outer * d->batch_inner;
-  const long tn = (d->N + BN - 1) / BN;
-  const long tiles128 = ((d->M + 127) / 128) * tn * nbatch;
-  const long tiles256 = ((d->M + 255) / 256) * tn * nbatch;
-  // tile / split-K choice, tuned on MI355X with tools/gemm_tune.py (profiles/r01_gemm_tune.txt).  The 128-row tile
-  // (two blocks per CU) wins whenever all its tiles fit one per CU, or M is small; the 256-row tile for the many-tile
-  // problems.  With >= 128 tiles only long K is worth splitting (>= 32 K-steps per split); with fewer, filling the
-  // 256 CUs comes first, but never below 8 K-steps per split.
-  // Tile height by wave quantisation: the grid runs in rounds of one tile per CU (256 CUs), so the cost of a tile
-  // height BM is ceil(tiles / 256) * BM; the commonest shape, M = 4608 x N = 1024, is 144 tiles at 256 rows (44 % of
-  // the CUs idle), 288 at 128 (two rounds) and 192 at 192 rows (one round, 75 % busy).  Ties go to the taller tile
-  // (fewer B re-reads).  The 192-row tile exists for the default precision only.
-  const long tiles192 = ((d->M + 191) / 192) * tn * nbatch;
-  p.k2 = d->precision == 4 && d->band == 0 && k2_enabled();
-  // round 5: the fp16 x2 products run on gemm_gl_kernel (128- or 192-row tiles: two stages of a 64-element chunk of a
-  // 256-row tile do not fit the LDS)
-  // (single-part products: measured in the step, the weight-gradient shapes run 5-15 % slower on it than on gemm_pp_kernel's K2
-  // loop -- 1024 x 3072 x 9082: 103 -> 119 us -- their intervals hold a third of the MFMAs per byte and the late group's DMAs
-  // do not land inside one MFMA phase: they stay there)
-  p.gl = d->precision == 3;
-  if (tiles128 <= 256 || d->M < 2048) {
-    p.BM = 128;
+// ---- the plan, part 2: kernel family, tile height, split-K.  Reads the descriptor and the layout's Kp, nothing else.
+enum class Kern {
+  PP,       // gemm_pp_kernel on bf16 parts (precision 0 / 1 / 2), one K-step (32 k) per barrier interval
+  PP_F16,   // gemm_pp_kernel on the leading fp16 part, one K-step per interval: precision 4 under a band, or with K2 switched off
+  PP_K2,    // precision 4: a barrier interval of gemm_pp_kernel covers two K-steps (64 elements of K)
+  GL,       // gemm_gl_kernel (LDS-DMA staging, 64-element chunks): the fp16 x2 products (precision 3)
+  Skinny    // gemm_skinny_kernel (few rows, NT, precision 3): BM = its rows per workgroup (16 | 32)
+};
+struct Tiling { Kern kern; int BM, ksplit, kchunk; long split_stride, part_bytes; };
+// what the rules below read: the grid of each tile height and the K loop's length
+struct Tiles {
+  long nbatch, tn, t128, t192, t256; int nk;      // nk: barrier intervals of the K loop: gemm_gl_kernel 64 k, gemm_pp_kernel 32 k (K2: 64)
+  long of(int bm) const { return bm == 256 ? t256 : (bm == 192 ? t192 : t128); }
+};
+inline long rounds(long tiles) { return (tiles + 255) / 256; }     // of one tile per CU (256 CUs)
+
+// round 5: the fp16 x2 products run on gemm_gl_kernel (128- or 192-row tiles: two stages of a 64-element chunk of a
+// 256-row tile do not fit the LDS)
+// (single-part products: measured in the step, the weight-gradient shapes run 5-15 % slower on it than on gemm_pp_kernel's K2
+// loop -- 1024 x 3072 x 9082: 103 -> 119 us -- their intervals hold a third of the MFMAs per byte and the late group's DMAs
+// do not land inside one MFMA phase: they stay there)
+Kern kernel_family(const vilco_gemm_desc* d) {
+  if (d->precision == 4) return (d->band == 0 && config().k2) ? Kern::PP_K2 : Kern::PP_F16;
+  return d->precision == 3 ? Kern::GL : Kern::PP;
+}
+
+// tile / split-K choice, tuned on MI355X with tools/gemm_tune.py (profiles/r01_gemm_tune.txt).  The 128-row tile
+// (two blocks per CU) wins whenever all its tiles fit one per CU, or M is small; the 256-row tile for the many-tile
+// problems.  With >= 128 tiles only long K is worth splitting (>= 32 K-steps per split); with fewer, filling the
+// 256 CUs comes first, but never below 8 K-steps per split.
+// Tile height by wave quantisation: the grid runs in rounds of one tile per CU (256 CUs), so the cost of a tile
+// height BM is ceil(tiles / 256) * BM; the commonest shape, M = 4608 x N = 1024, is 144 tiles at 256 rows (44 % of
+// the CUs idle), 288 at 128 (two rounds) and 192 at 192 rows (one round, 75 % busy).  Ties go to the taller tile
+// (fewer B re-reads).  The 192-row tile exists for the default precision only.
+int tile_by_rounds(const vilco_gemm_desc* d, const Tiles& t) {
+  if (t.t128 <= 256 || d->M < 2048) return 128;
+  const long c128 = rounds(t.t128) * 128, c192 = rounds(t.t192) * 192, c256 = rounds(t.t256) * 256;
+  int bm = 256; long best = c256;
+  if (d->precision == 4 && c192 < best) { bm = 192; best = c192; }      // (precision 3, the other fp16 format, is on gemm_gl_kernel)
+  if (c128 < best) bm = 128;
+  return bm;
+}
+
+// gemm_gl_kernel: a round of 128-row tiles takes 0.74 of a round of 192-row tiles, not 2/3 (measured, round 5:
+// 4608 x 4096 x 1024 as 5 rounds of 128 rows 131 us, as 3 rounds of 192 rows 107 us; 8192^3 3.33 vs 2.74 ms)
+int gl_tile_by_rounds(const vilco_gemm_desc* d, const Tiles& t) {
+  if (t.t128 <= 256 || d->M < 2048) return 128;
+  return rounds(t.t128) * 150 < rounds(t.t192) * 192 ? 128 : 192;      // (142 measured; near-ties go to the taller tile: 4608 x 3072 x 1024 92.8 vs 96.6 us)
+}
+
+// Round 6 (tools/lab/fwd_sweep.py, profiles/r06_fwd_sweep.txt): two sub-round cases the rules above sent to 128 rows.
+// (a) M < 2048 with more than one round of 128-row tiles but at most one of 192-row tiles (1152 x 4096 x 1024: 288 vs 192
+//     tiles): 47.4 -> 31.7 us (NT), 51.7 -> 33.0 (NN);
+// (b) 128..175 tiles of 128 rows and a long K (2304 x 1024 x 4096: 144 tiles x 3 splits = 432 workgroups, 1.7 rounds): 96 tiles
+//     of 192 rows x 2 splits fill ONE round with half the slab traffic: 68.1 -> 59.9 us (NT), 74.5 -> 62.7 (NN).
+// Returns the split count that comes with the tile: 2 for (b), else 0 (split-K by rounds decides).
+int sub192(const Tiles& t, Kern kern, int& bm) {
+  if (!config().sub192 || kern != Kern::GL || bm != 128 || t.nbatch != 1) return 0;
+  if (t.t128 > 256 && t.t192 <= 256 && t.t192 >= 176) { bm = 192; return 0; }
+  if (t.t128 >= 128 && t.t128 < 176 && t.nk >= 48 && t.t192 * 2 <= 256 && t.t192 * 2 >= 176) { bm = 192; return 2; }
+  return 0;
+}
+
+// Split-K, re-measured in round 2 with tools/lab/ks_try*.sh (kernel + finish, operands packed): what matters is the
+// number of rounds -- a grid of exactly <= 256 workgroups beats a slightly larger one by 15-20 % (1024 x 1024 x 4608:
+// 4 splits = 256 workgroups 42.7 us, 5 splits = 320 workgroups 50.8 us), and a tile costs ~15-20 K-steps of prologue +
+// epilogue on top of its K loop, so a 75 %-full single round is better left alone (4608 x 1024 x 4096, 192 tiles:
+// unsplit 148 us, 3 splits 172 us) while a 56 %-full one still gains from splitting (2304 x 1024 x 4096: 97 -> 80 us).
+int splitk_by_rounds(const Tiles& t, Kern kern, int bm, int sub192_ks) {
+  const long tiles = t.of(bm);
+  if (tiles >= 256) return 1;
+  const bool gl = kern == Kern::GL;
+  int ks;
+  if (tiles >= 176) {
+    ks = 1;
+  } else if (tiles >= 128) {
+    ks = t.nk / (gl ? 16 : 32);
+    if (ks > 3) ks = 3;
   } else {
-    const long c128 = ((tiles128 + 255) / 256) * 128, c192 = ((tiles192 + 255) / 256) * 192, c256 = ((tiles256 + 255) / 256) * 256;
-    p.BM = 256;
-    long best = c256;
-    if (p.gl) {
-      // gemm_gl_kernel: a round of 128-row tiles takes 0.74 of a round of 192-row tiles, not 2/3 (measured, round 5:
-      // 4608 x 4096 x 1024 as 5 rounds of 128 rows 131 us, as 3 rounds of 192 rows 107 us; 8192^3 3.33 vs 2.74 ms)
-      p.BM = 192; best = c192;
-      if (((tiles128 + 255) / 256) * 150 < best) { p.BM = 128; best = 0; }      // (142 measured; near-ties go to the taller tile: 4608 x 3072 x 1024 92.8 vs 96.6 us)
-    }
-    else if ((d->precision == 3 || d->precision == 4) && c192 < best) { p.BM = 192; best = c192; }
-    if (!p.gl && c128 < best) { p.BM = 128; best = c128; }
+    ks = (int)(256 / tiles);
+    if (ks > t.nk / (gl ? 4 : 8)) ks = t.nk / (gl ? 4 : 8);      // (the same 256 elements of K per split either way)
+    if (ks > 16) ks = 16;
   }
-  // Round 6 (tools/lab/fwd_sweep.py, profiles/r06_fwd_sweep.txt): two sub-round cases the rules above sent to 128 rows.
-  // (a) M < 2048 with more than one round of 128-row tiles but at most one of 192-row tiles (1152 x 4096 x 1024: 288 vs 192
-  //     tiles): 47.4 -> 31.7 us (NT), 51.7 -> 33.0 (NN);
-  // (b) 128..175 tiles of 128 rows and a long K (2304 x 1024 x 4096: 144 tiles x 3 splits = 432 workgroups, 1.7 rounds): 96 tiles
-  //     of 192 rows x 2 splits fill ONE round with half the slab traffic: 68.1 -> 59.9 us (NT), 74.5 -> 62.7 (NN).
-  static const bool sub192 = [] { const char* e = getenv("VILCO_GEMM_SUB192"); return !(e && e[0] == '0'); }();
-  int sub192_ks = 0;
-  if (sub192 && p.gl && d->precision == 3 && p.BM == 128 && nbatch == 1) {
-    const int nk64 = (p.Kp / BK + 1) / 2;
-    if (tiles128 > 256 && tiles192 <= 256 && tiles192 >= 176) p.BM = 192;
-    else if (tiles128 >= 128 && tiles128 < 176 && nk64 >= 48 && tiles192 * 2 <= 256 && tiles192 * 2 >= 176) { p.BM = 192; sub192_ks = 2; }
+  if (ks < 1) ks = 1;
+  return sub192_ks ? sub192_ks : ks;
+}
+
+// Round 6: the single-part products on gemm_pp_kernel's K2 loop (the weight gradients: M = Cout = 1024 rows, long K) were always
+// planned at 128 rows (M < 2048).  A 128 x 128 tile of ONE part is bound by its staging traffic (a 64-k interval moves 32 KB for
+// 128 MFMAs per CU); a 256-row tile does 2x the MFMAs for 1.5x the bytes, and the lost tile count is made up by split-K.  Measured
+// per 64-k interval and round (tools/lab/dw_sweep.py, profiles/r06_dw_sweep_pp.txt): 0.70 us at 128 rows, 0.95 at 192, 1.02 at 256,
+// + ~9 us per launch, + the slab traffic of a split.  The plan takes the cheapest of {128 as before, 192, 256 with the split count
+// that fills one round}, and leaves 128 unless the model says >= 8 % (1024 x 3072 x 9082: 109.9 -> 81.5 us, 1024 x 6912 x 4608:
+// 101.1 -> 78.3, 3072 x 1024 x 4608: 51.4 -> 46.0; the 1024 x 1024 and x 4096 shapes keep their plan).
+void dw_tall(const vilco_gemm_desc* d, const Tiles& t, Kern kern, int& bm, int& ks) {
+  if (!config().dw_tall || kern != Kern::PP_K2 || t.nbatch != 1 || bm != 128) return;
+  auto model = [&](int rows, int k, double c) {
+    const long tiles = ((d->M + rows - 1) / rows) * t.tn;
+    const long r = (tiles * k + 255) / 256;
+    const double split = k > 1 ? 3.0 + (double)d->M * d->N * 4.0 * (k + 1) / 5e6 : 0.0;
+    return 9.0 + (double)r * ((t.nk + k - 1) / k) * c + split;
+  };
+  const double base = model(128, ks, 0.70);
+  double best_t = base; int best_bm = 128, best_ks = ks;
+  const int bms[2] = {192, 256}; const double cs[2] = {0.95, 1.02};
+  for (int q = 0; q < 2; ++q) {
+    const long tiles = ((d->M + bms[q] - 1) / bms[q]) * t.tn;
+    int k = tiles >= 256 ? 1 : (int)(256 / tiles);
+    if (k > t.nk / 8) k = t.nk / 8;
+    if (k > 16) k = 16;
+    if (k < 1) k = 1;
+    const double m = model(bms[q], k, cs[q]);
+    if (m < best_t) { best_t = m; best_bm = bms[q]; best_ks = k; }
   }
-  const long tiles = p.BM == 256 ? tiles256 : (p.BM == 192 ? tiles192 : tiles128);
-  const int nk32p = p.Kp / BK;
-  // barrier intervals of the K loop: gemm_gl_kernel 64 k, gemm_pp_kernel 32 k (K2: 64)
-  const int nk = (p.gl || p.k2) ? (nk32p + 1) / 2 : nk32p;
-  int ks = 1;
-  // Split-K, re-measured in round 2 with tools/lab/ks_try*.sh (kernel + finish, operands packed): what matters is the
-  // number of rounds -- a grid of exactly <= 256 workgroups beats a slightly larger one by 15-20 % (1024 x 1024 x 4608:
-  // 4 splits = 256 workgroups 42.7 us, 5 splits = 320 workgroups 50.8 us), and a tile costs ~15-20 K-steps of prologue +
-  // epilogue on top of its K loop, so a 75 %-full single round is better left alone (4608 x 1024 x 4096, 192 tiles:
-  // unsplit 148 us, 3 splits 172 us) while a 56 %-full one still gains from splitting (2304 x 1024 x 4096: 97 -> 80 us).
-  if (tiles < 256) {
-    if (tiles >= 176) {
-      ks = 1;
-    } else if (tiles >= 128) {
-      ks = nk / (p.gl ? 16 : 32);
-      if (ks > 3) ks = 3;
-    } else {
-      ks = (int)(256 / tiles);
-      if (ks > nk / (p.gl ? 4 : 8)) ks = nk / (p.gl ? 4 : 8);      // (the same 256 elements of K per split either way)
-      if (ks > 16) ks = 16;
-    }
-    if (ks < 1) ks = 1;
-    if (sub192_ks) ks = sub192_ks;
-  }
-  // Round 6: the single-part products on gemm_pp_kernel's K2 loop (the weight gradients: M = Cout = 1024 rows, long K) were always
-  // planned at 128 rows (M < 2048).  A 128 x 128 tile of ONE part is bound by its staging traffic (a 64-k interval moves 32 KB for
-  // 128 MFMAs per CU); a 256-row tile does 2x the MFMAs for 1.5x the bytes, and the lost tile count is made up by split-K.  Measured
-  // per 64-k interval and round (tools/lab/dw_sweep.py, profiles/r06_dw_sweep_pp.txt): 0.70 us at 128 rows, 0.95 at 192, 1.02 at 256,
-  // + ~9 us per launch, + the slab traffic of a split.  The plan takes the cheapest of {128 as before, 192, 256 with the split count
-  // that fills one round}, and leaves 128 unless the model says >= 8 % (1024 x 3072 x 9082: 109.9 -> 81.5 us, 1024 x 6912 x 4608:
-  // 101.1 -> 78.3, 3072 x 1024 x 4608: 51.4 -> 46.0; the 1024 x 1024 and x 4096 shapes keep their plan).
-  static const bool dw_tall = [] { const char* e = getenv("VILCO_GEMM_DW_TALL"); return !(e && e[0] == '0'); }();
-  if (dw_tall && d->precision == 4 && p.k2 && !p.gl && nbatch == 1 && p.BM == 128) {
-    auto model = [&](int bm, int k, double c) {
-      const long t = ((d->M + bm - 1) / bm) * tn;
-      const long rounds = (t * k + 255) / 256;
-      const double split = k > 1 ? 3.0 + (double)d->M * d->N * 4.0 * (k + 1) / 5e6 : 0.0;
-      return 9.0 + (double)rounds * ((nk + k - 1) / k) * c + split;
-    };
-    const double base = model(128, ks, 0.70);
-    double best_t = base; int best_bm = 128, best_ks = ks;
-    const int bms[2] = {192, 256}; const double cs[2] = {0.95, 1.02};
-    for (int q = 0; q < 2; ++q) {
-      const long t = ((d->M + bms[q] - 1) / bms[q]) * tn;
-      int k = t >= 256 ? 1 : (int)(256 / t);
-      if (k > nk / 8) k = nk / 8;
-      if (k > 16) k = 16;
-      if (k < 1) k = 1;
-      const double m = model(bms[q], k, cs[q]);
-      if (m < best_t) { best_t = m; best_bm = bms[q]; best_ks = k; }
-    }
-    if (best_bm != 128 && best_t <= 0.92 * base) { p.BM = best_bm; ks = best_ks; }
-  }
-  // tuning overrides (tools/gemm_tune.py): VILCO_GEMM_BM = 128|256, VILCO_GEMM_KS = forced split count
-  // (read once per process: the plan is made twice per launch)
-  const int force_bm = tune().bm, force_ks = tune().ks;
-  if (force_bm == 128 || (force_bm == 256 && !p.gl) || (force_bm == 192 && d->precision >= 3)) p.BM = force_bm;
-  if (force_ks >= 1 && force_ks <= nk) ks = force_ks;
-  // few-row NT products of the default precision: one launch of gemm_skinny_kernel instead of a split-K plan + its reduce launch
-  p.skinny = false;
-  if (skinny_enabled() && force_bm == 0 && force_ks < 1 && d->precision == 3 && !p.a_tr && !p.b_tr && !p.a_km && !p.b_km &&
-      d->tap_operand == VILCO_TAP_NONE && d->band == 0 && nbatch == 1 && d->M <= skinny_max_rows() && d->K >= 64 && d->K <= skinny_max_k() &&
-      d->N <= 1024) {
-    // (tools/lab/skinny_ab.py, hipGraph replays: 16..512 x 512 x 512 7.3-8.8 us against 10.7-12.2 tiled, 154 x 1024 x 768 9.8 against
-    // 12.5; from K = 1024 or N = 2048 on the 16..32-row tiles' re-reads of B cost more than the second launch: 288 x 1024 x 1024 14.3
-    // against 13.3, 576 x 1024 x 4096 91 against 28)
-    p.skinny = true;
-    p.gl = false;
-    p.BM = d->M <= skinny_bm16_rows() ? 16 : 32;       // (64 rows per workgroup spill at two waves per SIMD)
+  if (best_bm != 128 && best_t <= 0.92 * base) { bm = best_bm; ks = best_ks; }
+}
+
+// tuning overrides (tools/gemm_tune.py): VILCO_GEMM_BM = 128|256, VILCO_GEMM_KS = forced split count
+// (read once per process: the plan is made twice per launch)
+void force_override(const vilco_gemm_desc* d, const Tiles& t, Kern kern, int& bm, int& ks) {
+  const int force_bm = config().force_bm, force_ks = config().force_ks;
+  if (force_bm == 128 || (force_bm == 256 && kern != Kern::GL) || (force_bm == 192 && d->precision >= 3)) bm = force_bm;
+  if (force_ks >= 1 && force_ks <= t.nk) ks = force_ks;
+}
+
+// few-row NT products of the default precision: one launch of gemm_skinny_kernel instead of a split-K plan + its reduce launch
+// (tools/lab/skinny_ab.py, hipGraph replays: 16..512 x 512 x 512 7.3-8.8 us against 10.7-12.2 tiled, 154 x 1024 x 768 9.8 against
+// 12.5; from K = 1024 or N = 2048 on the 16..32-row tiles' re-reads of B cost more than the second launch: 288 x 1024 x 1024 14.3
+// against 13.3, 576 x 1024 x 4096 91 against 28)
+bool skinny_eligible(const vilco_gemm_desc* d, const Tiles& t) {
+  const Config& c = config();
+  return c.skinny && c.force_bm == 0 && c.force_ks < 1 && d->precision == 3 && d->a_kcontig && d->b_kcontig &&
+         d->tap_operand == VILCO_TAP_NONE && d->band == 0 && t.nbatch == 1 && d->M <= c.skinny_max_rows && d->K >= 64 &&
+         d->K <= c.skinny_max_k && d->N <= 1024;
+}
+
+// The order in which the rules may override one another: each line may replace what the lines above it chose.
+Tiling plan_tiling(const vilco_gemm_desc* d, int Kp) {
+  Tiling p;
+  p.kern = kernel_family(d);
+  const long nbatch = (long)d->batch_outer * d->batch_inner, tn = (d->N + BN - 1) / BN;
+  const Tiles t = {nbatch, tn, ((d->M + 127) / 128) * tn * nbatch, ((d->M + 191) / 192) * tn * nbatch, ((d->M + 255) / 256) * tn * nbatch,
+                   (p.kern == Kern::GL || p.kern == Kern::PP_K2) ? (Kp / BK + 1) / 2 : Kp / BK};
+  int bm = p.kern == Kern::GL ? gl_tile_by_rounds(d, t) : tile_by_rounds(d, t);      // tile height by rounds of the grid
+  const int sub_ks = sub192(t, p.kern, bm);                                          // 128 -> 192 rows (+ its 2 splits)
+  int ks = splitk_by_rounds(t, p.kern, bm, sub_ks);                                  // split count for that tile height
+  dw_tall(d, t, p.kern, bm, ks);                                                     // 128 -> 192 | 256 rows with their own split count
+  force_override(d, t, p.kern, bm, ks);                                              // vilco_gemm_force: tile height and / or split count
+  if (skinny_eligible(d, t)) {                                                       // the few-row kernel: family, rows, no split
+    p.kern = Kern::Skinny;
+    bm = d->M <= config().skinny_bm16_rows ? 16 : 32;       // (64 rows per workgroup spill at two waves per SIMD)
     ks = 1;
   }
-  p.kchunk = (nk + ks - 1) / ks;
-  p.ksplit = (nk + p.kchunk - 1) / p.kchunk;
+  p.BM = bm;
+  p.kchunk = (t.nk + ks - 1) / ks;
+  p.ksplit = (t.nk + p.kchunk - 1) / p.kchunk;
   long out_span = 0;
   if (p.ksplit > 1) {   // a split slab covers the whole (strided) output footprint
     out_span = (long)(d->batch_outer - 1) * d->sCo + (long)(d->batch_inner - 1) * d->sCi + (long)(d->M - 1) * d->ldc + d->N;
@@ -1278,48 +1328,262 @@ void make_plan(const vilco_gemm_desc* d, Plan& p) {
   }
   p.split_stride = out_span;
   p.part_bytes = p.ksplit > 1 ? align_up(out_span * p.ksplit * 4, 256) : 0;
+  return p;
 }
 
-template <int BM, int NP, bool F16, bool AKM, bool BKM, bool K2 = false>
-void launch_pp_km(const GArgs& g, dim3 grid, hipStream_t s) {
-  constexpr size_t a_el = AKM ? 32 * ((BM == 192 ? 256 : BM) + 16) : BM * 32, b_el = BKM ? 32 * (BN + 16) : BN * 32;
-  constexpr size_t pipe = (size_t)2 * NP * (a_el + b_el) * sizeof(__bf16), epi = (size_t)8 * 16 * (BM / 64) * EPI_LD * 4;
-  constexpr size_t lds = pipe > epi ? pipe : epi;
-  static const bool once = [] {
-    hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_pp_kernel<BM, NP, F16, AKM, BKM, K2>),
-                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    (void)hipGetLastError();
-    return true;
-  }();
+struct Plan : Layout, Tiling {};
+Plan make_plan(const vilco_gemm_desc* d) {
+  const Layout L = operand_layout(d, d->a_planes != nullptr, d->b_planes != nullptr);
+  return Plan{L, plan_tiling(d, L.Kp)};
+}
+inline size_t workspace_need(const Plan& p) { return (size_t)(p.a.bytes + p.b.bytes + p.part_bytes + 512 + SCALE_BYTES); }
+// workgroups of the split-K finish = max|C| partials it leaves: one per block, either form of splitk_reduce_kernel
+inline long splitk_blocks(const vilco_gemm_desc* d) {
+  return std::min(2048L, ((long)d->M * d->N * d->batch_outer * d->batch_inner + 255) / 256);
+}
+// ---- launch: the kernel's dynamic-LDS limit is set on its first use, and the launch asks for the same figure
+template <auto KERNEL, class ARGS>
+void launch_gemm(size_t lds, dim3 grid, hipStream_t s, const ARGS& args) {
+  static const bool once = ((void)hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
+                            (void)hipGetLastError(), true);
   (void)once;
-  hipLaunchKernelGGL((gemm_pp_kernel<BM, NP, F16, AKM, BKM, K2>), grid, dim3(512), lds, s, g);
+  hipLaunchKernelGGL(KERNEL, grid, dim3(512), lds, s, args);
 }
-
-template <int BM, bool AKM, bool BKM>
-void launch_gl_km(const GArgs& g, dim3 grid, hipStream_t s) {
-  constexpr size_t lds = (size_t)4 * (BM + BN) * 128;          // two stages x two slots x (A + B) x 128 B
-  static const bool once = [] {
-    hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_gl_kernel<BM, AKM, BKM>),
-                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    (void)hipGetLastError();
-    return true;
-  }();
-  (void)once;
-  hipLaunchKernelGGL((gemm_gl_kernel<BM, AKM, BKM>), grid, dim3(512), lds, s, g);
-}
-template <int BM>
-void launch_gl(const GArgs& g, dim3 grid, hipStream_t s, bool akm, bool bkm) {
-  if (akm && bkm) launch_gl_km<BM, true, true>(g, grid, s);
-  else if (bkm) launch_gl_km<BM, false, true>(g, grid, s);
-  else launch_gl_km<BM, false, false>(g, grid, s);
-}
-
 // operand orientations in use: (kc,kc) forward / convs, (kc,km) dX = dY W, (km,km) dW = dY^T X
-template <int BM, int NP, bool F16 = false, bool K2 = false>
-void launch_pp(const GArgs& g, dim3 grid, hipStream_t s, bool akm = false, bool bkm = false) {
-  if (akm && bkm) launch_pp_km<BM, NP, F16, true, true, K2>(g, grid, s);
-  else if (bkm) launch_pp_km<BM, NP, F16, false, true, K2>(g, grid, s);
-  else launch_pp_km<BM, NP, F16, false, false, K2>(g, grid, s);
+template <class F>
+void with_km(bool akm, bool bkm, F&& f) {
+  if (akm && bkm) f(std::true_type{}, std::true_type{});
+  else if (bkm) f(std::false_type{}, std::true_type{});
+  else f(std::false_type{}, std::false_type{});
+}
+// f(tile height as a constant): the first of the list that equals bm, else the last one
+template <int B0, int... BMS, class F>
+void with_bm(int bm, F&& f) {
+  if constexpr (sizeof...(BMS) == 0) f(std::integral_constant<int, B0>{});
+  else if (bm == B0) f(std::integral_constant<int, B0>{});
+  else with_bm<BMS...>(bm, f);
+}
+template <int BM, int NP, bool F16, bool K2>
+void launch_pp(const GArgs& g, dim3 grid, hipStream_t s, bool akm, bool bkm) {
+  with_km(akm, bkm, [&](auto A, auto B) {
+    constexpr bool AKM = decltype(A)::value, BKM = decltype(B)::value;
+    launch_gemm<&gemm_pp_kernel<BM, NP, F16, AKM, BKM, K2>>(pp_lds<BM, NP, AKM, BKM>(), grid, s, g);
+  });
+}
+
+// The launch table (GEMM: the instantiations that exist): kernel family x tile rows (x parts) x orientation.
+// PP_K2: two slots = two K-steps of part 0;  PP_F16: one slot of part 0, plane strides unchanged (the planes hold two parts).
+void launch_plan(const Plan& p, const GArgs& g, dim3 grid, hipStream_t s) {
+  const bool ak = p.a.km, bk = p.b.km;
+  switch (p.kern) {
+    case Kern::Skinny:
+      return with_bm<16, 32>(p.BM, [&](auto R) {
+        constexpr int BMS = decltype(R)::value;
+        launch_gemm<&gemm_skinny_kernel<BMS>>(skinny_lds<BMS>(), dim3(((g.N + 63) / 64) * ((g.M + BMS - 1) / BMS)), s, g);
+      });
+    case Kern::GL:
+      return with_bm<192, 128>(p.BM, [&](auto R) {
+        constexpr int BM = decltype(R)::value;
+        with_km(ak, bk, [&](auto A, auto B) { launch_gemm<&gemm_gl_kernel<BM, decltype(A)::value, decltype(B)::value>>(gl_lds<BM>(), grid, s, g); });
+      });
+    case Kern::PP_K2:
+      return with_bm<256, 192, 128>(p.BM, [&](auto R) { launch_pp<decltype(R)::value, 2, true, true>(g, grid, s, ak, bk); });
+    case Kern::PP_F16:
+      return with_bm<256, 192, 128>(p.BM, [&](auto R) { launch_pp<decltype(R)::value, 1, true, false>(g, grid, s, ak, bk); });
+    case Kern::PP:
+      return with_bm<256, 128>(p.BM, [&](auto R) {
+        constexpr int BM = decltype(R)::value;
+        if (p.NP == 1) launch_pp<BM, 1, false, false>(g, grid, s, ak, bk);
+        else if (p.NP == 2) launch_pp<BM, 2, false, false>(g, grid, s, ak, bk);
+        else launch_pp<BM, 3, false, false>(g, grid, s, ak, bk);
+      });
+  }
+}
+
+// ---- optional timing of the MFMA kernel alone (bench.py's roofline line): HIP events on the caller's stream
+struct ProfRec { int64_t v[10]; };   // M, N, K, batch, BM, ksplit, precision, a_km, b_km, tap
+struct ProfState {
+  bool on = false;
+  std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;
+  std::vector<ProfRec> rec;          // one per event pair
+  std::vector<double> ms;            // filled by profile_end, read by profile_records
+};
+ProfState& prof() { static ProfState p; return p; }
+// brackets the launches of its scope with an event pair while a profile is being taken; the record is filed on exit
+struct ProfScope {
+  hipStream_t s; ProfRec rec; hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  ProfScope(hipStream_t s_, const ProfRec& r) : s(s_), rec(r) {
+    if (prof().on) { hipEventCreate(&ev0); hipEventCreate(&ev1); hipEventRecord(ev0, s); }
+  }
+  ~ProfScope() {
+    if (ev0) { hipEventRecord(ev1, s); prof().ev.emplace_back(ev0, ev1); prof().rec.push_back(rec); }
+  }
+};
+
+// number of max|C| partials a vilco_gemm call with this descriptor writes to desc->amax_out (0: too many -- do not ask)
+long amax_out_parts(const vilco_gemm_desc* d, const Plan& p) {
+  if (p.ksplit > 1) return splitk_blocks(d);
+  if (p.kern == Kern::Skinny) return (long)((d->N + 63) / 64) * ((d->M + p.BM - 1) / p.BM);
+  const long n = (long)((d->N + BN - 1) / BN) * ((d->M + p.BM - 1) / p.BM) * d->batch_outer * d->batch_inner;
+  return n <= 8192 ? n : 0;
+}
+
+// ---- one operand side: the pack of the fp32 source, or the view of a pre-packed buffer, and the kernel's operand block
+struct OperandIn {
+  const float* src; long ld, so, si;        // fp32 matrix: row stride, outer / inner batch strides
+  int rows;                                 // M | N
+  const void* planes;                       // vilco_pack buffer (a_planes / b_planes) or null: the call packs the operand itself
+  __bf16* dst; float* amax; float* inv;     // this side's share of the workspace: planes, amax partials, {1/s, s}
+  bool seq_rows;                            // rows are addressed per sequence: A under tap mode 1
+  int tap_cols;                             // tapkm: width of the padded token rows (A: dZ, Cout = M wide; B: X, Cin = tapC wide)
+  int skip_rows;                            // tapkm: dZ' = padded rows 1 ... (A: 1, B: 0)
+};
+struct Operand { PackArgs pk; PlaneOp op; const float* inv_scale; bool own_pack; };
+// (The same kind of host code as attn.hip's pack_operand, which hipcc 7.2 miscompiled at -O3; this one compared bit-equal against
+// the inline code it replaces -- DESIGN_LOG.md R18.1 -- and carries no optnone.)
+Operand make_operand(const vilco_gemm_desc* d, const Layout& L, const Side& sd, const OperandIn& in) {
+  const bool f16 = d->precision == 3 || d->precision == 4;      // 4: fp16 x2 planes, the product uses their first parts only
+  Operand o;
+  PackArgs& pk = o.pk;
+  pk.src = in.src; pk.dst = in.dst; pk.ld = in.ld; pk.rows = in.rows; pk.K = d->K; pk.Kp = L.Kp;
+  pk.plane_stride = sd.plane; pk.batch_stride = sd.batch; pk.nbi = sd.nbi;
+  pk.so = sd.nbo > 1 ? in.so : 0; pk.si = sd.nbi > 1 ? in.si : 0;
+  pk.tap = sd.tap; pk.tapC = d->tapC > 0 ? d->tapC : 1; pk.tapT = d->tapT > 0 ? d->tapT : 1;
+  pk.out_rows = sd.out_rows;
+  if (sd.km) { pk.rows = d->K; pk.K = in.rows; pk.Kp = (int)align_up(in.rows, 32); }   // natural [K][M] / [K][N] view
+  if (L.tapkm) { pk.tapC = in.tap_cols; pk.K = in.tap_cols; }                          // token rows, zero-padded per sequence
+  pk.vec = vilco_aligned(in.src, 16) && (in.ld % 4) == 0 && (in.so % 4) == 0 && (in.si % 4) == 0;
+  pk.amax = f16 ? in.amax : nullptr; pk.namax = 0; pk.inv_scale = in.inv;
+  o.own_pack = in.planes == nullptr;
+  const __bf16* planes = in.dst;
+  o.inv_scale = in.inv;
+  if (!o.own_pack) {    // planes from vilco_pack: [part][rows32][cols32] behind the header
+    const unsigned char* u = reinterpret_cast<const unsigned char*>(in.planes);
+    planes = reinterpret_cast<const __bf16*>(u + PACK_HDR);
+    o.inv_scale = reinterpret_cast<const float*>(u) + AMAX_MAX_BLOCKS;
+  }
+  PlaneOp& op = o.op;
+  op.p = planes; op.plane_stride = sd.plane; op.batch_stride = sd.batch; op.nbi = sd.nbi;
+  op.has_o = sd.nbo > 1; op.has_i = sd.nbi > 1; op.rows = in.rows;
+  if (in.seq_rows) { op.seqT = d->tapT; op.seq_stride = (long)(d->tapT + 2) * d->tapC; op.row_stride = d->tapC; }
+  else { op.seqT = 0x7fffffff; op.seq_stride = 0; op.row_stride = L.Kp; }
+  op.cols = 0;
+  if (sd.km) { op.row_stride = align_up(in.rows, 32); op.cols = (int)align_up(in.rows, 32); }
+  if (L.tapkm) { op.p = planes + (long)in.skip_rows * in.tap_cols; op.row_stride = in.tap_cols; op.cols = in.rows; }   // dZ' = padded rows 1 ...; X' seen as [rows][3 Cin], row stride Cin
+  op.bytes = 2 * (sd.batch - (op.p - planes));      // one part of one batch, less the skipped row (gemm_gl_kernel's buffer range)
+  return o;
+}
+// max|x| for an operand this call packs: partials left by its producer (vilco_gemm_desc.a_amax / b_amax) replace the amax pass
+void choose_amax(Operand& o, const AmaxOp& own_pass, const float* parts, int nparts, AmaxArgs& am, int& nops) {
+  if (!o.own_pack) return;
+  if (parts && nparts > 0) { o.pk.amax = parts; o.pk.namax = nparts; }
+  else { am.op[nops++] = own_pass; o.pk.namax = own_pass.nblocks; }
+}
+
+// ---- a product up to its main launch
+struct Prepared { bool empty = false; Plan p; GArgs g; int nz; hipStream_t s; };     // empty: M or N = 0, nothing to launch
+// the descriptor on its own; the order of the checks decides which code a doubly wrong descriptor gets.  empty: M or N = 0
+int check_desc(const vilco_gemm_desc* d, bool& empty) {
+  if (!d || !d->C || (!d->A && !d->a_planes) || (!d->B && !d->b_planes)) return VILCO_ERR_BADARG;
+  if (d->a_planes || d->b_planes) {
+    // pre-packed operands: untapped problems, or the plain (weight) operand B of a k=3 conv whose taps are on A
+    // (k=3 convs: the tapped operand's planes must be the zero-padded per-sequence image, vilco_pack_item.seq_len; checked
+    //  against the plan below)
+    const bool tap_ok = d->tap_operand == VILCO_TAP_NONE || (d->tap_operand == VILCO_TAP_A && d->b_kcontig) ||
+                        d->tap_operand == VILCO_TAP_B;
+    if (!tap_ok || !config().km) return VILCO_ERR_UNSUPPORTED;
+    if (!vilco_aligned(d->a_planes, 256) || !vilco_aligned(d->b_planes, 256)) return VILCO_ERR_BADARG;
+  }
+  if (d->M < 0 || d->N < 0 || d->K < 0 || d->batch_outer < 1 || d->batch_inner < 1) return VILCO_ERR_BADARG;
+  if (d->M == 0 || d->N == 0) { empty = true; return VILCO_OK; }
+  if (d->precision < 0 || d->precision > 4) return VILCO_ERR_BADARG;
+  if (d->act < 0 || d->act > 2) return VILCO_ERR_BADARG;
+  if (d->band < 0 || d->band > 3 || (d->band && d->bandT <= 0)) return VILCO_ERR_BADARG;
+  if (!(d->drop_p >= 0.f) || d->drop_p >= 1.f) return VILCO_ERR_BADARG;
+  if (d->drop_p > 0.f && (d->ldc != d->N || d->batch_outer != 1 || d->batch_inner != 1)) return VILCO_ERR_UNSUPPORTED;
+  if (d->row_len && d->rowT <= 0) return VILCO_ERR_BADARG;
+  if (d->row_mask && (d->batch_outer != 1 || d->batch_inner != 1)) return VILCO_ERR_UNSUPPORTED;
+  if (d->a_kcontig == 0 && d->b_kcontig == 1) return VILCO_ERR_UNSUPPORTED;  // "TT" is never needed
+  if (d->tap_operand != VILCO_TAP_NONE) {
+    if (d->tapC <= 0 || d->tapT <= 0) return VILCO_ERR_BADARG;
+    if (d->batch_outer != 1 || d->batch_inner != 1) return VILCO_ERR_UNSUPPORTED;
+    if (d->tap_operand == VILCO_TAP_A) {
+      if (!(d->a_kcontig == 1 && d->K == 3 * d->tapC && d->lda == d->tapC && (d->M % d->tapT) == 0)) return VILCO_ERR_BADARG;
+    } else if (d->tap_operand == VILCO_TAP_B) {
+      if (!(d->b_kcontig == 0 && d->N == 3 * d->tapC && d->ldb == d->tapC && (d->K % d->tapT) == 0)) return VILCO_ERR_BADARG;
+    } else {
+      return VILCO_ERR_BADARG;
+    }
+  }
+  return VILCO_OK;
+}
+// the descriptor against its plan
+int check_plan(const vilco_gemm_desc* d, const Plan& p) {
+  // operand planes must come in the layout the product reads: natural for plain operands, the per-sequence image for tapped ones
+  const bool a_seq = d->a_planes && d->a_planes_seq, b_seq = d->b_planes && d->b_planes_seq;
+  const bool a_want = d->a_planes && ((d->tap_operand == VILCO_TAP_A && p.a.tap == 1) || p.tapkm);
+  const bool b_want = d->b_planes && p.tapkm;
+  if (a_seq != a_want || b_seq != b_want) return VILCO_ERR_UNSUPPORTED;
+  if (d->tap_operand == VILCO_TAP_A && d->a_planes && p.a.tap != 1) return VILCO_ERR_UNSUPPORTED;   // tapC % 8 != 0: expanded rows
+  if (d->tap_operand == VILCO_TAP_B && (d->a_planes || d->b_planes) && !(p.tapkm && d->a_planes && d->b_planes)) return VILCO_ERR_UNSUPPORTED;
+  // the kernel's staging loads address one operand matrix (one batch element of one part) with 32-bit byte offsets
+  // (buffer loads: lane offset + K-step offset, gemm_pp_kernel); the last K-step may over-read one tile
+  const long lim = (1L << 31) - (1L << 20);
+  const long a_el = std::max(p.a.pack_batch, natural_image_elems(d->M, p.Kp));
+  const long b_el = std::max(p.b.pack_batch, natural_image_elems(d->N, p.Kp));
+  if (a_el * 2 >= lim || b_el * 2 >= lim) return VILCO_ERR_UNSUPPORTED;
+  return (!d->workspace || d->workspace_bytes < workspace_need(p)) ? VILCO_ERR_WORKSPACE : VILCO_OK;
+}
+
+// validates, plans, packs what is not pre-packed and fills the kernel arguments
+int gemm_prepare(const vilco_gemm_desc* d, void* stream, Prepared& pr) {
+  int rc = check_desc(d, pr.empty);
+  if (rc != VILCO_OK || pr.empty) return rc;
+  const Plan& p = pr.p = make_plan(d);
+  if ((rc = check_plan(d, p)) != VILCO_OK) return rc;
+  hipStream_t s = pr.s = reinterpret_cast<hipStream_t>(stream);
+
+  unsigned char* ws = reinterpret_cast<unsigned char*>(align_up((long)reinterpret_cast<uintptr_t>(d->workspace), 256));
+  float* scales = reinterpret_cast<float*>(ws);            // [A partials | B partials | 1/sA, sA, 1/sB, sB]
+  ws += SCALE_BYTES;
+  float* parts = reinterpret_cast<float*>(ws + p.a.bytes + p.b.bytes);
+
+  // ---- pack A and B into bf16 planes
+  Operand A = make_operand(d, p, p.a, OperandIn{d->A, d->lda, d->sAo, d->sAi, d->M, d->a_planes, reinterpret_cast<__bf16*>(ws), scales,
+                                                scales + 2 * AMAX_MAX_BLOCKS, p.a.tap == 1, d->M, 1});
+  Operand B = make_operand(d, p, p.b, OperandIn{d->B, d->ldb, d->sBo, d->sBi, d->N, d->b_planes, reinterpret_cast<__bf16*>(ws + p.a.bytes),
+                                                scales + AMAX_MAX_BLOCKS, scales + 2 * AMAX_MAX_BLOCKS + 2, false, d->tapC, 0});
+  if ((d->precision == 3 || d->precision == 4) && (A.own_pack || B.own_pack)) {      // the fp16 formats scale by max|x|
+    AmaxArgs am;
+    int nops = 0;
+    choose_amax(A, amax_view(A.pk, p.a.tr, p.a.nbo, scales), d->a_amax, d->a_namax, am, nops);
+    choose_amax(B, amax_view(B.pk, p.b.tr, p.b.nbo, scales + AMAX_MAX_BLOCKS), d->b_amax, d->b_namax, am, nops);
+    if (nops) launch_amax(am, nops, s);
+  }
+  if (A.own_pack) dispatch_pack(p.NP, A.pk, p.a.tr, p.a.nbo * p.a.nbi, s);
+  if (B.own_pack) dispatch_pack(p.NP, B.pk, p.b.tr, p.b.nbo * p.b.nbi, s);
+
+  // ---- MFMA kernel
+  GArgs& g = pr.g;
+  g.a = A.op; g.b = B.op;
+  g.ldc = d->ldc; g.M = d->M; g.N = d->N; g.Kp = p.Kp;
+  g.batch_inner = d->batch_inner; g.sCo = d->sCo; g.sCi = d->sCi;
+  g.tiles_n = (d->N + BN - 1) / BN;
+  g.ntiles = g.tiles_n * ((d->M + p.BM - 1) / p.BM);
+  g.ksplit = p.ksplit; g.kchunk = p.kchunk; g.split_stride = p.split_stride;
+  g.inv_a = A.inv_scale; g.inv_b = B.inv_scale;
+  g.band = d->band; g.bandT = d->bandT;
+  g.drop_thresh = vilco_drop_threshold_host(d->drop_p); g.drop_seed = d->drop_seed; g.drop_inv_keep = 1.f / (1.f - d->drop_p); g.seed_word = vilco_seed_word_dev();
+  g.vec_out = (d->N % 4) == 0 && (d->ldc % 4) == 0 && (d->sCo % 4) == 0 && (d->sCi % 4) == 0 && vilco_aligned(d->C, 16) &&
+              vilco_aligned(d->bias, 16) && vilco_aligned(d->preact, 16) && vilco_aligned(d->colscale, 16) &&
+              vilco_aligned(d->residual, 16);
+  g.c = p.ksplit > 1 ? parts : d->C;
+  g.cfinal = d->C;
+  g.amax_out = d->band == 1 ? nullptr : d->amax_out;
+  g.e = Epi{d->alpha, d->beta, d->bias, d->preact, d->act, d->row_len, d->rowT, d->colscale, d->residual,
+            d->res_masked, d->row_mask};
+  pr.nz = d->batch_outer * d->batch_inner;
+  return VILCO_OK;
 }
 
 }  // namespace
@@ -1330,48 +1594,9 @@ extern "C" int vilco_lab_read(unsigned long long* out) {
 }
 #endif
 
-// ---- optional timing of the MFMA kernel alone (bench.py's roofline line): HIP events on the caller's stream
-namespace {
-template <int BMS>
-static void launch_skinny(const GArgs& g, hipStream_t s) {
-  constexpr size_t lds = (size_t)8 * BMS * SK_LD * 4;
-  static const bool once = [] {
-    hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_skinny_kernel<BMS>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    (void)hipGetLastError();
-    return true;
-  }();
-  (void)once;
-  const int tiles = ((g.N + 63) / 64) * ((g.M + BMS - 1) / BMS);
-  hipLaunchKernelGGL((gemm_skinny_kernel<BMS>), dim3(tiles), dim3(512), lds, s, g);
-}
-
-struct ProfRec { int64_t v[10]; };   // M, N, K, batch, BM, ksplit, precision, a_km, b_km, tap
-struct ProfState {
-  bool on = false;
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;
-  std::vector<ProfRec> rec;          // one per event pair
-  std::vector<double> ms;            // filled by profile_end, read by profile_records
-};
-ProfState& prof() { static ProfState p; return p; }
-}  // namespace
-
-// number of max|C| partials a vilco_gemm call with this descriptor writes to desc->amax_out (0: too many -- do not ask)
-static long amax_out_parts(const vilco_gemm_desc* d, const Plan& p) {
-  const long nz = (long)d->batch_outer * d->batch_inner;
-  if (p.ksplit > 1) {
-    long blocks = ((long)d->M * d->N * nz + 255) / 256;
-    return blocks > 2048 ? 2048 : blocks;
-  }
-  if (p.skinny) return (long)((d->N + 63) / 64) * ((d->M + p.BM - 1) / p.BM);
-  const long n = (long)((d->N + BN - 1) / BN) * ((d->M + p.BM - 1) / p.BM) * nz;
-  return n <= 8192 ? n : 0;
-}
-
 extern "C" int32_t vilco_gemm_amax_parts(const vilco_gemm_desc* d) {
   if (!d || d->M <= 0 || d->N <= 0 || d->band == 1) return 0;      // band 1 leaves tiles unwritten
-  Plan p;
-  make_plan(d, p);
-  return (int32_t)amax_out_parts(d, p);
+  return (int32_t)amax_out_parts(d, make_plan(d));
 }
 
 extern "C" int vilco_gemm_profile_begin(void) {
@@ -1413,32 +1638,25 @@ extern "C" int64_t vilco_gemm_profile_records(int64_t* desc, double* ms, int64_t
   return n;
 }
 
-static inline int np_of_precision(int precision) { return precision == 1 ? 1 : ((precision == 0 || precision == 3) ? 2 : 3); }
-
 extern "C" size_t vilco_pack_bytes(int64_t rows, int64_t cols, int32_t precision) {
   if (rows < 0 || cols < 0) return 0;
-  return (size_t)(PACK_HDR + align_up(rows > 0 ? rows : 1, 32) * align_up(cols > 0 ? cols : 1, 32) * 2 * np_of_precision(precision));
+  return (size_t)(PACK_HDR + natural_image_elems(rows > 0 ? rows : 1, cols > 0 ? cols : 1) * 2 * parts_of_precision(precision, true));
 }
 
 static inline long item_cols(const vilco_pack_item& it) { return it.relshift ? it.rows + it.cols : it.cols; }
 
-// rows of a zero-padded per-sequence plane image (vilco_pack_item.seq_len): nseq * (T + 2) padded rows + enough zero rows for
-// both readers -- the forward / dX conv's overlapped spans (make_plan: a_out_rows) and the weight-gradient product's
-// contraction over the padded rows (Kp + 3 + one K-step)
-static inline long tap_plane_rows(long nseq, long T) { return vilco_tap_plane_rows(nseq, T); }
-
 extern "C" size_t vilco_pack_item_bytes(const vilco_pack_item* it, int32_t precision) {
   if (!it || it->rows <= 0 || it->cols <= 0) return 0;
-  if (it->seq_len > 0)
-    return (size_t)(PACK_HDR + align_up(tap_plane_rows(it->rows / it->seq_len, it->seq_len) * it->cols, 8) * 2 * np_of_precision(precision));
+  const int NP = parts_of_precision(precision, true);
+  if (it->seq_len > 0) return (size_t)(PACK_HDR + seq_image_elems(it->rows / it->seq_len, it->seq_len, it->cols) * 2 * NP);
   const long nb = it->nbatch > 1 ? it->nbatch : 1;
-  return (size_t)(PACK_HDR + nb * align_up(it->rows, 32) * align_up(item_cols(*it), 32) * 2 * np_of_precision(precision));
+  return (size_t)(PACK_HDR + nb * natural_image_elems(it->rows, item_cols(*it)) * 2 * NP);
 }
 
 extern "C" int vilco_pack_many(const vilco_pack_item* items, int32_t n, int32_t precision, void* stream) {
   if (!items || n < 1 || n > 4 || precision < 0 || precision > 3) return VILCO_ERR_BADARG;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const int NP = np_of_precision(precision);
+  const int NP = parts_of_precision(precision, true);
   PackArgs4 pk;
   AmaxArgs am;
   bool have_amax[4] = {false, false, false, false};
@@ -1461,7 +1679,7 @@ extern "C" int vilco_pack_many(const vilco_pack_item* items, int32_t n, int32_t 
     pa.vec = vilco_aligned(it.src, 16) && (it.ld % 4) == 0 && (it.batch_stride % 4) == 0;
     if (it.seq_len > 0) {          // the k=3 convs' image: [nseq * (T + 2) + zero rows][cols], first and last row of a sequence zero
       if (it.relshift || nbatch != 1 || (it.cols % 8) != 0 || (it.rows % it.seq_len) != 0) return VILCO_ERR_UNSUPPORTED;
-      const long tr = tap_plane_rows(it.rows / it.seq_len, it.seq_len);
+      const long tr = vilco_tap_plane_rows(it.rows / it.seq_len, it.seq_len);
       pa.tap = 1; pa.tapC = (int)it.cols; pa.tapT = it.seq_len; pa.out_rows = (int)tr;
       pa.plane_stride = align_up(tr * it.cols, 8); pa.batch_stride = pa.plane_stride;
     }
@@ -1498,240 +1716,34 @@ extern "C" int vilco_pack(const float* src, int64_t rows, int64_t cols, int64_t 
 
 extern "C" size_t vilco_gemm_workspace(const vilco_gemm_desc* d) {
   if (!d || d->M <= 0 || d->N <= 0 || d->K < 0) return 512;
-  Plan p;
-  make_plan(d, p);
-  return (size_t)(p.a_bytes + p.b_bytes + p.part_bytes + 512 + SCALE_BYTES);
+  return workspace_need(make_plan(d));
 }
 
-// gout / pout non-null: validate, plan and fill the kernel arguments of a product whose operands are already packed, WITHOUT
-// launching anything (vilco_gemm_group collects the members of a grouped launch this way)
-static int gemm_impl(const vilco_gemm_desc* d, void* stream, GArgs* gout, Plan* pout) {
-  if (!d || !d->C || (!d->A && !d->a_planes) || (!d->B && !d->b_planes)) return VILCO_ERR_BADARG;
-  if (gout && !(d->a_planes && d->b_planes)) return VILCO_ERR_UNSUPPORTED;
-  if (d->a_planes || d->b_planes) {
-    // pre-packed operands: untapped problems, or the plain (weight) operand B of a k=3 conv whose taps are on A
-    // (k=3 convs: the tapped operand's planes must be the zero-padded per-sequence image, vilco_pack_item.seq_len; checked
-    //  against the plan below)
-    const bool tap_ok = d->tap_operand == VILCO_TAP_NONE || (d->tap_operand == VILCO_TAP_A && d->b_kcontig) ||
-                        d->tap_operand == VILCO_TAP_B;
-    if (!tap_ok || !use_km()) return VILCO_ERR_UNSUPPORTED;
-    if (!vilco_aligned(d->a_planes, 256) || !vilco_aligned(d->b_planes, 256)) return VILCO_ERR_BADARG;
-  }
-  if (d->M < 0 || d->N < 0 || d->K < 0 || d->batch_outer < 1 || d->batch_inner < 1) return VILCO_ERR_BADARG;
-  if (d->M == 0 || d->N == 0) return VILCO_OK;
-  if (d->precision < 0 || d->precision > 4) return VILCO_ERR_BADARG;
-  if (d->act < 0 || d->act > 2) return VILCO_ERR_BADARG;
-  if (d->band < 0 || d->band > 3 || (d->band && d->bandT <= 0)) return VILCO_ERR_BADARG;
-  if (!(d->drop_p >= 0.f) || d->drop_p >= 1.f) return VILCO_ERR_BADARG;
-  if (d->drop_p > 0.f && (d->ldc != d->N || d->batch_outer != 1 || d->batch_inner != 1)) return VILCO_ERR_UNSUPPORTED;
-  if (d->row_len && d->rowT <= 0) return VILCO_ERR_BADARG;
-  if (d->row_mask && (d->batch_outer != 1 || d->batch_inner != 1)) return VILCO_ERR_UNSUPPORTED;
-  if (d->a_kcontig == 0 && d->b_kcontig == 1) return VILCO_ERR_UNSUPPORTED;  // "TT" is never needed
-  if (d->tap_operand != VILCO_TAP_NONE) {
-    if (d->tapC <= 0 || d->tapT <= 0) return VILCO_ERR_BADARG;
-    if (d->batch_outer != 1 || d->batch_inner != 1) return VILCO_ERR_UNSUPPORTED;
-    if (d->tap_operand == VILCO_TAP_A) {
-      if (!(d->a_kcontig == 1 && d->K == 3 * d->tapC && d->lda == d->tapC && (d->M % d->tapT) == 0)) return VILCO_ERR_BADARG;
-    } else if (d->tap_operand == VILCO_TAP_B) {
-      if (!(d->b_kcontig == 0 && d->N == 3 * d->tapC && d->ldb == d->tapC && (d->K % d->tapT) == 0)) return VILCO_ERR_BADARG;
-    } else {
-      return VILCO_ERR_BADARG;
-    }
-  }
-  Plan p;
-  make_plan(d, p);
-  // operand planes must come in the layout the product reads: natural for plain operands, the per-sequence image for tapped ones
-  {
-    const bool a_seq = d->a_planes && d->a_planes_seq, b_seq = d->b_planes && d->b_planes_seq;
-    const bool a_want = d->a_planes && ((d->tap_operand == VILCO_TAP_A && p.a_tap == 1) || p.tapkm);
-    const bool b_want = d->b_planes && p.tapkm;
-    if (a_seq != a_want || b_seq != b_want) return VILCO_ERR_UNSUPPORTED;
-    if (d->tap_operand == VILCO_TAP_A && d->a_planes && p.a_tap != 1) return VILCO_ERR_UNSUPPORTED;   // tapC % 8 != 0: expanded rows
-    if (d->tap_operand == VILCO_TAP_B && (d->a_planes || d->b_planes) && !(p.tapkm && d->a_planes && d->b_planes)) return VILCO_ERR_UNSUPPORTED;
-  }
-  // the kernel's staging loads address one operand matrix (one batch element of one part) with 32-bit byte offsets
-  // (buffer loads: lane offset + K-step offset, gemm_pp_kernel); the last K-step may over-read one tile
-  {
-    const long lim = (1L << 31) - (1L << 20);
-    const long a_el = p.a_batch > (long)align_up(d->M, 32) * p.Kp ? p.a_batch : (long)align_up(d->M, 32) * p.Kp;
-    const long b_el = p.b_batch > (long)align_up(d->N, 32) * p.Kp ? p.b_batch : (long)align_up(d->N, 32) * p.Kp;
-    if (a_el * 2 >= lim || b_el * 2 >= lim) return VILCO_ERR_UNSUPPORTED;
-  }
-  const size_t need = (size_t)(p.a_bytes + p.b_bytes + p.part_bytes + 512 + SCALE_BYTES);
-  if (!d->workspace || d->workspace_bytes < need) return VILCO_ERR_WORKSPACE;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-
-  unsigned char* ws = reinterpret_cast<unsigned char*>(align_up((long)reinterpret_cast<uintptr_t>(d->workspace), 256));
-  float* scales = reinterpret_cast<float*>(ws);            // [A partials | B partials | 1/sA, 1/sB]
-  ws += SCALE_BYTES;
-  __bf16* planesA = reinterpret_cast<__bf16*>(ws);
-  __bf16* planesB = reinterpret_cast<__bf16*>(ws + p.a_bytes);
-  float* parts = reinterpret_cast<float*>(ws + p.a_bytes + p.b_bytes);
-  const bool f16 = d->precision == 3 || d->precision == 4;      // 4: fp16 x2 planes, the product uses their first parts only
-
-  // ---- pack A and B into bf16 planes
-  PackArgs pa;
-  pa.src = d->A; pa.dst = planesA; pa.ld = d->lda; pa.rows = d->M; pa.K = d->K; pa.Kp = p.Kp;
-  pa.plane_stride = p.a_plane; pa.batch_stride = p.a_batch; pa.nbi = p.a_nbi;
-  pa.so = p.a_nbo > 1 ? d->sAo : 0; pa.si = p.a_nbi > 1 ? d->sAi : 0;
-  pa.tap = p.a_tap; pa.tapC = d->tapC > 0 ? d->tapC : 1; pa.tapT = d->tapT > 0 ? d->tapT : 1;
-  pa.out_rows = p.a_out_rows;
-  if (p.a_km) { pa.rows = d->K; pa.K = d->M; pa.Kp = (int)align_up(d->M, 32); }   // natural [K][M] view
-  if (p.tapkm) { pa.tapC = d->M; pa.K = d->M; }                                     // dZ rows: Cout wide, zero-padded per sequence
-  pa.vec = vilco_aligned(d->A, 16) && (d->lda % 4) == 0 && (d->sAo % 4) == 0 && (d->sAi % 4) == 0;
-  pa.amax = f16 ? scales : nullptr; pa.namax = 0; pa.inv_scale = scales + 2 * AMAX_MAX_BLOCKS;
-  const bool packA = d->a_planes == nullptr, packB = d->b_planes == nullptr;
-
-  PackArgs pb;
-  pb.src = d->B; pb.dst = planesB; pb.ld = d->ldb; pb.rows = d->N; pb.K = d->K; pb.Kp = p.Kp;
-  pb.plane_stride = p.b_plane; pb.batch_stride = p.b_batch; pb.nbi = p.b_nbi;
-  pb.so = p.b_nbo > 1 ? d->sBo : 0; pb.si = p.b_nbi > 1 ? d->sBi : 0;
-  pb.tap = p.b_tap; pb.tapC = d->tapC > 0 ? d->tapC : 1; pb.tapT = d->tapT > 0 ? d->tapT : 1;
-  pb.out_rows = p.b_out_rows;
-  if (p.b_km) { pb.rows = d->K; pb.K = d->N; pb.Kp = (int)align_up(d->N, 32); }   // natural [K][N] view
-  if (p.tapkm) { pb.K = d->tapC; }                                                  // X rows: Cin wide
-  pb.vec = vilco_aligned(d->B, 16) && (d->ldb % 4) == 0 && (d->sBo % 4) == 0 && (d->sBi % 4) == 0;
-  pb.amax = f16 ? scales + AMAX_MAX_BLOCKS : nullptr; pb.namax = 0; pb.inv_scale = scales + 2 * AMAX_MAX_BLOCKS + 2;
-  if (f16 && (packA || packB)) {
-    AmaxOp ma = amax_view(pa, p.a_tr, p.a_nbo, scales), mb = amax_view(pb, p.b_tr, p.b_nbo, scales + AMAX_MAX_BLOCKS);
-    AmaxArgs am;
-    int nops = 0;
-    // partials left by the producer of A / B (vilco_gemm_desc.a_amax / b_amax) replace the amax pass over that operand
-    if (packA) {
-      if (d->a_amax && d->a_namax > 0) { pa.amax = d->a_amax; pa.namax = d->a_namax; }
-      else { am.op[nops++] = ma; pa.namax = ma.nblocks; }
-    }
-    if (packB) {
-      if (d->b_amax && d->b_namax > 0) { pb.amax = d->b_amax; pb.namax = d->b_namax; }
-      else { am.op[nops++] = mb; pb.namax = mb.nblocks; }
-    }
-    if (nops) launch_amax(am, nops, s);
-  }
-  if (packA) dispatch_pack(p.NP, pa, p.a_tr, p.a_nbo * p.a_nbi, s);
-  if (packB) dispatch_pack(p.NP, pb, p.b_tr, p.b_nbo * p.b_nbi, s);
-  const float* inv_a = pa.inv_scale;
-  const float* inv_b = pb.inv_scale;
-  if (!packA) {    // planes from vilco_pack: [part][rows32][cols32] behind the header
-    const unsigned char* u = reinterpret_cast<const unsigned char*>(d->a_planes);
-    planesA = reinterpret_cast<__bf16*>(const_cast<unsigned char*>(u) + PACK_HDR);
-    inv_a = reinterpret_cast<const float*>(u) + AMAX_MAX_BLOCKS;
-    p.a_batch = p.a_km ? (long)p.Kp * align_up(d->M, 32) : align_up(d->M, 32) * (long)p.Kp;
-    if (p.a_tap == 1)                                // the convs' zero-padded image (vilco_pack_item.seq_len)
-      p.a_batch = p.tapkm ? align_up(tap_plane_rows(d->K / d->tapT, d->tapT) * d->M, 8)
-                          : align_up(tap_plane_rows(d->M / d->tapT, d->tapT) * d->tapC, 8);
-    p.a_plane = p.a_batch * p.a_nbo * p.a_nbi;       // batched planes: [part][batch][rows32][cols32]
-  }
-  if (!packB) {
-    const unsigned char* u = reinterpret_cast<const unsigned char*>(d->b_planes);
-    planesB = reinterpret_cast<__bf16*>(const_cast<unsigned char*>(u) + PACK_HDR);
-    inv_b = reinterpret_cast<const float*>(u) + AMAX_MAX_BLOCKS;
-    p.b_batch = p.b_km ? (long)p.Kp * align_up(d->N, 32) : align_up(d->N, 32) * (long)p.Kp;
-    if (p.tapkm) p.b_batch = align_up(tap_plane_rows(d->K / d->tapT, d->tapT) * d->tapC, 8);
-    p.b_plane = p.b_batch * p.b_nbo * p.b_nbi;
-  }
-
-  // ---- MFMA kernel
-  GArgs g;
-  g.a.p = planesA; g.a.plane_stride = p.a_plane; g.a.batch_stride = p.a_batch; g.a.nbi = p.a_nbi;
-  g.a.has_o = p.a_nbo > 1; g.a.has_i = p.a_nbi > 1; g.a.rows = d->M;
-  if (p.a_tap == 1) { g.a.seqT = d->tapT; g.a.seq_stride = (long)(d->tapT + 2) * d->tapC; g.a.row_stride = d->tapC; }
-  else { g.a.seqT = 0x7fffffff; g.a.seq_stride = 0; g.a.row_stride = p.Kp; }
-  g.a.cols = 0;
-  if (p.a_km) { g.a.row_stride = align_up(d->M, 32); g.a.cols = (int)align_up(d->M, 32); }
-  if (p.tapkm) { g.a.p = planesA + d->M; g.a.row_stride = d->M; g.a.cols = d->M; }      // dZ' = padded rows 1 ...
-  g.b.p = planesB; g.b.plane_stride = p.b_plane; g.b.batch_stride = p.b_batch; g.b.nbi = p.b_nbi;
-  g.b.has_o = p.b_nbo > 1; g.b.has_i = p.b_nbi > 1; g.b.rows = d->N;
-  g.b.seqT = 0x7fffffff; g.b.seq_stride = 0; g.b.row_stride = p.Kp;
-  g.b.cols = 0;
-  if (p.b_km) { g.b.row_stride = align_up(d->N, 32); g.b.cols = (int)align_up(d->N, 32); }
-  if (p.tapkm) { g.b.row_stride = d->tapC; g.b.cols = d->N; }                            // X' seen as [rows][3 Cin], row stride Cin
-  g.a.bytes = 2 * (p.a_batch - (g.a.p - planesA)); g.b.bytes = 2 * p.b_batch;      // one part of one batch (gemm_gl_kernel's buffer range)
-  g.ldc = d->ldc; g.M = d->M; g.N = d->N; g.Kp = p.Kp;
-  g.batch_inner = d->batch_inner; g.sCo = d->sCo; g.sCi = d->sCi;
-  g.tiles_n = (d->N + BN - 1) / BN;
-  g.ntiles = g.tiles_n * ((d->M + p.BM - 1) / p.BM);
-  g.ksplit = p.ksplit; g.kchunk = p.kchunk; g.split_stride = p.split_stride;
-  g.inv_a = inv_a; g.inv_b = inv_b;
-  g.band = d->band; g.bandT = d->bandT;
-  g.drop_thresh = vilco_drop_threshold_host(d->drop_p); g.drop_seed = d->drop_seed; g.drop_inv_keep = 1.f / (1.f - d->drop_p); g.seed_word = vilco_seed_word_dev();
-  g.vec_out = (d->N % 4) == 0 && (d->ldc % 4) == 0 && (d->sCo % 4) == 0 && (d->sCi % 4) == 0 && vilco_aligned(d->C, 16) &&
-              vilco_aligned(d->bias, 16) && vilco_aligned(d->preact, 16) && vilco_aligned(d->colscale, 16) &&
-              vilco_aligned(d->residual, 16);
-  g.c = p.ksplit > 1 ? parts : d->C;
-  g.cfinal = d->C;
-  g.amax_out = d->band == 1 ? nullptr : d->amax_out;
-  g.e = Epi{d->alpha, d->beta, d->bias, d->preact, d->act, d->row_len, d->rowT, d->colscale, d->residual,
-            d->res_masked, d->row_mask};
-  const int nz = d->batch_outer * d->batch_inner;
-  if (gout) { *gout = g; *pout = p; return VILCO_OK; }
-  dim3 grid(g.ntiles, p.ksplit, nz);
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  if (prof().on) { hipEventCreate(&ev0); hipEventCreate(&ev1); hipEventRecord(ev0, s); }
-  {
-    const bool ak = p.a_km, bk = p.b_km;
-    if (p.skinny) {
-      if (p.BM == 16) launch_skinny<16>(g, s); else launch_skinny<32>(g, s);
-    } else if (p.gl) {
-      if (p.BM == 192) launch_gl<192>(g, grid, s, ak, bk);
-      else launch_gl<128>(g, grid, s, ak, bk);
-    } else if (d->precision == 4 && p.k2) {  // one MFMA per product on the leading fp16 parts, two K-steps per barrier interval
-      if (p.BM == 256) launch_pp<256, 2, true, true>(g, grid, s, ak, bk);
-      else if (p.BM == 192) launch_pp<192, 2, true, true>(g, grid, s, ak, bk);
-      else launch_pp<128, 2, true, true>(g, grid, s, ak, bk);
-    } else if (d->precision == 4) {   // (band-limited products: one K-step per interval; plane strides unchanged)
-      if (p.BM == 256) launch_pp<256, 1, true>(g, grid, s, ak, bk);
-      else if (p.BM == 192) launch_pp<192, 1, true>(g, grid, s, ak, bk);
-      else launch_pp<128, 1, true>(g, grid, s, ak, bk);
-    } else if (p.BM == 256) {
-      if (p.NP == 1) launch_pp<256, 1>(g, grid, s, ak, bk);
-      else if (p.NP == 2) launch_pp<256, 2>(g, grid, s, ak, bk);
-      else launch_pp<256, 3>(g, grid, s, ak, bk);
-    } else {
-      if (p.NP == 1) launch_pp<128, 1>(g, grid, s, ak, bk);
-      else if (p.NP == 2) launch_pp<128, 2>(g, grid, s, ak, bk);
-      else launch_pp<128, 3>(g, grid, s, ak, bk);
-    }
-  }
-  if (ev0) {
-    hipEventRecord(ev1, s);
-    prof().ev.emplace_back(ev0, ev1);
-    prof().rec.push_back(ProfRec{{d->M, d->N, d->K, nz, p.BM, p.ksplit, d->precision, p.a_km, p.b_km, p.a_tap | (p.b_tap << 4)}});
-  }
-  if (p.ksplit > 1 && vilco_defer_active() && nz == 1 && d->alpha == 1.f && d->beta == 0.f && !d->bias &&
+// a plain sum of the slabs that nothing reads before the end of backward (a weight gradient) is recorded for the deferred pass
+static void splitk_finish(const vilco_gemm_desc* d, const Prepared& pr) {
+  const GArgs& g = pr.g;
+  if (vilco_defer_active() && pr.nz == 1 && d->alpha == 1.f && d->beta == 0.f && !d->bias &&
       !d->preact && d->act == VILCO_ACT_NONE && !d->row_len && !d->row_mask && !d->colscale && !d->residual && d->drop_p == 0.f &&
       !d->amax_out) {
-    // a plain sum of the split slabs whose result nothing reads before the end of backward (a weight gradient): recorded
-    vilco_defer_push_sk(g.c, g.cfinal, g.split_stride, g.ldc, d->M, d->N, p.ksplit);
-  } else if (p.ksplit > 1) {
-    long blocks = ((long)d->M * d->N * nz + 255) / 256;       // == amax_out_parts(): one max|C| partial per block, either form
-    if (blocks > 2048) blocks = 2048;
-    if (g.vec_out) hipLaunchKernelGGL(splitk_reduce_kernel<true>, dim3((int)blocks), dim3(256), 0, s, g, nz);
-    else hipLaunchKernelGGL(splitk_reduce_kernel<false>, dim3((int)blocks), dim3(256), 0, s, g, nz);
+    vilco_defer_push_sk(g.c, g.cfinal, g.split_stride, g.ldc, d->M, d->N, pr.p.ksplit);
+    return;
   }
-  return vilco_launch_status();
+  const dim3 blocks((int)splitk_blocks(d));
+  if (g.vec_out) hipLaunchKernelGGL(splitk_reduce_kernel<true>, blocks, dim3(256), 0, pr.s, g, pr.nz);
+  else hipLaunchKernelGGL(splitk_reduce_kernel<false>, blocks, dim3(256), 0, pr.s, g, pr.nz);
 }
 
-extern "C" int vilco_gemm(const vilco_gemm_desc* d, void* stream) { return gemm_impl(d, stream, nullptr, nullptr); }
-
-template <int BM>
-static void launch_gl_group(const GArgsN& gg, int n, int ntiles, hipStream_t s, bool akm, bool bkm) {
-  constexpr size_t lds = (size_t)4 * (BM + BN) * 128;
-  const dim3 grid(ntiles, 1, n);
-#define VILCO_GROUP_LAUNCH(A_, B_)                                                                                      \
-  do {                                                                                                                  \
-    static const bool once = [] {                                                                                       \
-      hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_gl_group_kernel<BM, A_, B_>),                             \
-                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                        \
-      (void)hipGetLastError();                                                                                          \
-      return true;                                                                                                      \
-    }();                                                                                                                \
-    (void)once;                                                                                                         \
-    hipLaunchKernelGGL((gemm_gl_group_kernel<BM, A_, B_>), grid, dim3(512), lds, s, gg);                                \
-  } while (0)
-  if (akm && bkm) VILCO_GROUP_LAUNCH(true, true);
-  else if (bkm) VILCO_GROUP_LAUNCH(false, true);
-  else VILCO_GROUP_LAUNCH(false, false);
-#undef VILCO_GROUP_LAUNCH
+extern "C" int vilco_gemm(const vilco_gemm_desc* d, void* stream) {
+  Prepared pr;
+  const int rc = gemm_prepare(d, stream, pr);
+  if (rc != VILCO_OK || pr.empty) return rc;
+  const Plan& p = pr.p;
+  {
+    ProfScope timed(pr.s, ProfRec{{d->M, d->N, d->K, pr.nz, p.BM, p.ksplit, d->precision, p.a.km, p.b.km, p.a.tap | (p.b.tap << 4)}});
+    launch_plan(p, pr.g, dim3(pr.g.ntiles, p.ksplit, pr.nz), pr.s);
+  }
+  if (p.ksplit > 1) splitk_finish(d, pr);
+  return vilco_launch_status();
 }
 
 // n (2..4) independent products of ONE shape, orientation and format in one launch (gemm_gl_group_kernel): operands packed
@@ -1739,19 +1751,20 @@ static void launch_gl_group(const GArgsN& gg, int n, int ntiles, hipStream_t s, 
 // shapes -- runs as n ordinary vilco_gemm calls, in order (same results either way: the kernel body is the same).
 extern "C" int vilco_gemm_group(const vilco_gemm_desc* descs, int32_t n, void* stream) {
   if (!descs || n < 1 || n > 4) return VILCO_ERR_BADARG;
-  static const bool enabled = [] { const char* e = getenv("VILCO_GEMM_GROUP"); return !(e && e[0] == '0'); }();
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   GArgsN gg;
   Plan p0;
-  bool ok = enabled && n >= 2;
+  bool ok = config().group && n >= 2;
   for (int i = 0; ok && i < n; ++i) {
     const vilco_gemm_desc& d = descs[i];
-    Plan p;
-    ok = d.precision == 3 && d.batch_outer == 1 && d.batch_inner == 1 && d.tap_operand == VILCO_TAP_NONE && d.band == 0 &&
-         d.M == descs[0].M && d.N == descs[0].N && d.K == descs[0].K && d.a_kcontig == descs[0].a_kcontig &&
-         d.b_kcontig == descs[0].b_kcontig && d.M > 0 && d.N > 0 && gemm_impl(&d, stream, &gg.g[i], &p) == VILCO_OK &&
-         p.gl && p.ksplit == 1 && (i == 0 || (p.BM == p0.BM && p.a_km == p0.a_km && p.b_km == p0.b_km));
-    if (i == 0) p0 = p;
+    Prepared pr;      // (both operands pre-packed: preparing a member launches nothing)
+    ok = d.a_planes && d.b_planes && d.precision == 3 && d.batch_outer == 1 && d.batch_inner == 1 && d.tap_operand == VILCO_TAP_NONE &&
+         d.band == 0 && d.M == descs[0].M && d.N == descs[0].N && d.K == descs[0].K && d.a_kcontig == descs[0].a_kcontig &&
+         d.b_kcontig == descs[0].b_kcontig && d.M > 0 && d.N > 0 && gemm_prepare(&d, stream, pr) == VILCO_OK &&
+         pr.p.kern == Kern::GL && pr.p.ksplit == 1 && (i == 0 || (pr.p.BM == p0.BM && pr.p.a.km == p0.a.km && pr.p.b.km == p0.b.km));
+    if (!ok) break;
+    gg.g[i] = pr.g;
+    if (i == 0) p0 = pr.p;
   }
   if (!ok) {
     for (int i = 0; i < n; ++i) {
@@ -1760,14 +1773,15 @@ extern "C" int vilco_gemm_group(const vilco_gemm_desc* descs, int32_t n, void* s
     }
     return VILCO_OK;
   }
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  if (prof().on) { hipEventCreate(&ev0); hipEventCreate(&ev1); hipEventRecord(ev0, s); }
-  if (p0.BM == 192) launch_gl_group<192>(gg, n, gg.g[0].ntiles, s, p0.a_km, p0.b_km);
-  else launch_gl_group<128>(gg, n, gg.g[0].ntiles, s, p0.a_km, p0.b_km);
-  if (ev0) {
-    hipEventRecord(ev1, s);
-    prof().ev.emplace_back(ev0, ev1);
-    prof().rec.push_back(ProfRec{{descs[0].M, descs[0].N, descs[0].K, n, p0.BM, 1, 3, p0.a_km, p0.b_km, 0x100}});    // (batch field = group size)
+  {
+    ProfScope timed(s, ProfRec{{descs[0].M, descs[0].N, descs[0].K, n, p0.BM, 1, 3, p0.a.km, p0.b.km, 0x100}});    // (batch field = group size)
+    const dim3 grid(gg.g[0].ntiles, 1, n);
+    with_bm<192, 128>(p0.BM, [&](auto R) {
+      constexpr int BM = decltype(R)::value;
+      with_km(p0.a.km, p0.b.km, [&](auto A, auto B) {
+        launch_gemm<&gemm_gl_group_kernel<BM, decltype(A)::value, decltype(B)::value>>(gl_lds<BM>(), grid, s, gg);
+      });
+    });
   }
   return vilco_launch_status();
 }
@@ -1781,14 +1795,14 @@ static int64_t g_config_gen = 0;
 extern "C" int64_t vilco_gemm_config_gen(void) { return g_config_gen; }
 
 extern "C" int vilco_gemm_set_skinny(int32_t on) {
-  skinny_enabled() = on != 0;
+  config().skinny = on != 0;
   ++g_config_gen;
   return VILCO_OK;
 }
 
 extern "C" int vilco_gemm_force(int32_t bm, int32_t ks) {
   if (bm < 0 || ks < 0) return VILCO_ERR_BADARG;
-  tune().bm = bm; tune().ks = ks;
+  config().force_bm = bm; config().force_ks = ks;
   ++g_config_gen;
   return VILCO_OK;
 }
