@@ -112,13 +112,6 @@ def test_op_refuses_cpu_tensors_and_the_fifth_key_raises():
         Prompt(length=2, embed_dim=8, prompt_pool=False)
 
 
-def test_the_switch_is_part_of_the_capture_key(monkeypatch):
-    from vilco_amd import ops
-    a = ops.arithmetic_key()
-    monkeypatch.setattr(ops, "fused_prompt", not ops.fused_prompt)
-    assert ops.arithmetic_key() != a
-
-
 @pytest.mark.parametrize("name", sorted(CASES))
 def test_module_tensor_op_body_matches_the_reference_on_cpu(name, monkeypatch):
     """VILCO_FUSED_PROMPT=0 (ops.fused_prompt False) keeps the tensor-op body; CPU tensors take it in any case"""

@@ -8,7 +8,14 @@ import ctypes as C
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("VILCO_HIP_LIB") or os.path.join(_HERE, "libvilco_hip.so")   # override: tools/lab builds
+if __package__:
+    from . import switches
+else:       # loaded alone by file path (ctypes-only child processes that must not import the package, which imports torch)
+    import importlib.util
+    _spec = importlib.util.spec_from_file_location("vilco_switches", os.path.join(_HERE, "switches.py"))
+    switches = importlib.util.module_from_spec(_spec)
+    _spec.loader.exec_module(switches)
+LIB_PATH = switches.text("VILCO_HIP_LIB") or os.path.join(_HERE, "libvilco_hip.so")   # override: tools/lab builds
 
 ACT_NONE, ACT_RELU, ACT_GELU = 0, 1, 2
 TAP_NONE, TAP_A, TAP_B = 0, 1, 2

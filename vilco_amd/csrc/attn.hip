@@ -1978,10 +1978,9 @@ __global__ __launch_bounds__(ATT_THREADS) void attn_bwd_dkdv_kernel(AttnArgs a) 
 //           its backward kernels exist to produce dS: a backward that wants none is General behind the Hd64XL forward
 enum class Route { General, Hd64, Hd64XL };
 struct RouteKey { int hd, mode, Tq, Tk, precision; bool has_bias, drop, want_ds; };     // want_ds (backward): dbias || ds_planes
-inline bool env_on(const char* name) { const char* e = getenv(name); return !(e && e[0] == '0'); }
 
 Route attn_route(const RouteKey& k, bool bwd) {
-  static const bool fast = env_on("VILCO_ATTN_FAST"), xl = env_on("VILCO_ATTN_XL_FAST");       // read once per process
+  static const bool fast = vilco_env_flag("VILCO_ATTN_FAST", true), xl = vilco_env_flag("VILCO_ATTN_XL_FAST", true);   // read once per process
   if (!fast || k.precision != 3 || k.hd != 64) return Route::General;
   if (!k.has_bias && !k.want_ds && (k.mode == 0 || k.mode == 2) && !k.drop) return Route::Hd64;
   if (xl && k.has_bias && k.mode == 3 && k.Tq == k.Tk && (!bwd || k.want_ds)) return Route::Hd64XL;

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 #include "vilco_hip.h"
 
 #define VILCO_WAVE 64
@@ -12,6 +13,13 @@ static inline int vilco_launch_status() {
 
 static inline bool vilco_aligned(const void* p, size_t a) {
   return (reinterpret_cast<uintptr_t>(p) % a) == 0;
+}
+
+// The library's own environment switches (the list of record: vilco_amd/switches.py).  A flag is on unless its first
+// character is '0'; a number is what atoi reads, and one below `min` falls back to the default.
+static inline bool vilco_env_flag(const char* name, bool dflt) { const char* e = getenv(name); return e ? e[0] != '0' : dflt; }
+static inline int vilco_env_int(const char* name, int dflt, int min) {
+  const char* e = getenv(name); const int x = e ? atoi(e) : dflt; return x >= min ? x : dflt;
 }
 
 // Wavefront reductions, result in every lane.  Inside a row of 16 lanes the partners come through DPP operand modifiers

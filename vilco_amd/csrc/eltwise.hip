@@ -683,7 +683,7 @@ extern "C" int vilco_act_bwd(const vilco_act_bwd_desc* d, void* stream) {
   float* ws = dbias ? reinterpret_cast<float*>(workspace) : nullptr;
   const bool emit = amax_parts && n_parts;
   if (emit) *n_parts = nb * ((C + EW_THREADS - 1) / EW_THREADS);
-  static const bool vec_on = [] { const char* e = getenv("VILCO_ACT_BWD_VEC"); return !(e && e[0] == '0'); }();
+  static const bool vec_on = vilco_env_flag("VILCO_ACT_BWD_VEC", true);
   const bool vec = vec_on && (C % 4) == 0 && vilco_aligned(dy, 16) && vilco_aligned(aux, 16) && vilco_aligned(dz, 16);
   const dim3 grid(nb, (C + EW_THREADS - 1) / EW_THREADS);
 #define ACT_BWD_LAUNCH(K)                                                                                                        \

@@ -1049,25 +1049,21 @@ constexpr long SCALE_BYTES = 2 * AMAX_MAX_BLOCKS * 4 + 256;   // fp16 x2 format:
 constexpr long PACK_HDR = VILCO_PACK_HDR;                      // vilco_pack buffers: amax partials, {1/s, s}, then the planes
 
 // ---- process-wide switches: read from the environment once per process (the plan is made up to three times per launch)
-inline bool env_flag(const char* name, bool dflt) { const char* e = getenv(name); return e ? e[0] != '0' : dflt; }
-inline int env_int(const char* name, int dflt, int min) {      // values below `min` fall back to the default
-  const char* e = getenv(name); const int x = e ? atoi(e) : dflt; return x >= min ? x : dflt;
-}
 struct Config {
-  const bool km = env_int("VILCO_GEMM_KM", 1, INT_MIN) != 0;   // k-major consumption (a number: whatever atoi reads as 0 is off)
-  const bool k2 = env_flag("VILCO_GEMM_K2", true);
-  const bool sub192 = env_flag("VILCO_GEMM_SUB192", true);
-  const bool dw_tall = env_flag("VILCO_GEMM_DW_TALL", true);
-  const bool tapkm = env_flag("VILCO_CONV_DW_KM", true);
-  const bool group = env_flag("VILCO_GEMM_GROUP", true);
-  const int skinny_max_rows = env_int("VILCO_GEMM_SKINNY_M", 640, 1);
+  const bool km = vilco_env_int("VILCO_GEMM_KM", 1, INT_MIN) != 0;   // k-major consumption (a number: whatever atoi reads as 0 is off)
+  const bool k2 = vilco_env_flag("VILCO_GEMM_K2", true);
+  const bool sub192 = vilco_env_flag("VILCO_GEMM_SUB192", true);
+  const bool dw_tall = vilco_env_flag("VILCO_GEMM_DW_TALL", true);
+  const bool tapkm = vilco_env_flag("VILCO_CONV_DW_KM", true);
+  const bool group = vilco_env_flag("VILCO_GEMM_GROUP", true);
+  const int skinny_max_rows = vilco_env_int("VILCO_GEMM_SKINNY_M", 640, 1);
   // largest M that takes 16-row workgroups (more workgroups, more re-reads of B).  Inside the planned range (K <= 768, N <= 1024) 16 rows
   // are never slower (profiles/r06_skinny_bm16.txt: 154 x 1024 x 768 9.8 us against 11.4 at 32 rows, 512 x 512 x 512 7.6 against 8.6).
-  const int skinny_bm16_rows = env_int("VILCO_GEMM_SKINNY_BM16", 640, 0);
-  const int skinny_max_k = env_int("VILCO_GEMM_SKINNY_K", 768, 1);
+  const int skinny_bm16_rows = vilco_env_int("VILCO_GEMM_SKINNY_BM16", 640, 0);
+  const int skinny_max_k = vilco_env_int("VILCO_GEMM_SKINNY_K", 768, 1);
   // the three that vilco_gemm_set_skinny / vilco_gemm_force change
-  bool skinny = env_flag("VILCO_GEMM_SKINNY", true);
-  int force_bm = env_int("VILCO_GEMM_BM", 0, INT_MIN), force_ks = env_int("VILCO_GEMM_KS", 0, INT_MIN);
+  bool skinny = vilco_env_flag("VILCO_GEMM_SKINNY", true);
+  int force_bm = vilco_env_int("VILCO_GEMM_BM", 0, INT_MIN), force_ks = vilco_env_int("VILCO_GEMM_KS", 0, INT_MIN);
 };
 inline Config& config() { static Config c; return c; }
 // 16-bit parts per operand element.  Precision 4 multiplies the leading parts of fp16 x2 planes: the product's own packs write two.

@@ -20,7 +20,7 @@
 //   params:  per channel, d gamma_j / d beta_j / d w_j accumulated over row chunks (no reductions: statistics are saved)
 //   dh:      dh = sum_j dwconv^T(dc_j) + dh from the other consumers, one pass
 // followed by the ordinary LayerNorm backward of LN1 (norm.hip).
-#include <cstdlib>
+#include <climits>
 #include "common.h"
 
 void vilco_reduce_rows(const float* ws, float* out0, float* out1, int nrows, int ncols, int split, hipStream_t s);
@@ -817,7 +817,7 @@ void launch_fwd_tb(const QkvArgs& a, hipStream_t s) {
 // tokens per wave: more tokens = fewer halo re-reads and parameter loads, fewer = more waves in flight and fewer
 // registers.  Measured at [8, 2304, 2304] (r02): TB = 1 / 2 / 4 -> 1.90 / 2.49 / 2.16 TB/s.  VILCO_QKV_TB overrides (tuning).
 int forced_tb() {
-  static const int forced = [] { const char* e = getenv("VILCO_QKV_TB"); return e ? atoi(e) : 0; }();
+  static const int forced = vilco_env_int("VILCO_QKV_TB", 0, INT_MIN);
   return forced;
 }
 
@@ -830,7 +830,7 @@ int ring_seg(int B, int Tout) {
   return seg < 8 ? 8 : seg;
 }
 int ring_mode() {          // VILCO_QKV_RING: 1 = always, 0 = never, unset = where it measured faster
-  static const int m = [] { const char* e = getenv("VILCO_QKV_RING"); return e ? atoi(e) : -1; }();
+  static const int m = vilco_env_int("VILCO_QKV_RING", -1, INT_MIN);
   return m;
 }
 // Device time, forward, ring vs three-pass (r03, graph replays): [8,2304,2304] 112 vs 226 us, [2,2304,2304] 34 vs 66,

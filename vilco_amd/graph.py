@@ -32,15 +32,14 @@ does not take, narration SSL with its fused path switched off by VILCO_FUSED_SSL
 """
 import ctypes as C
 import gc
-import os
 
 import torch
 
-from . import _lib, ops
+from . import _lib, ops, switches
 
 
-_DP_REPLAY_SYNC = os.environ.get("VILCO_DP_REPLAY_SYNC", "1") != "0"
-_OWN_STREAM = os.environ.get("VILCO_GRAPH_OWN_STREAM", "1") != "0"      # replays leave the default (null) stream: GraphedStep._replay
+_DP_REPLAY_SYNC = switches.on("VILCO_DP_REPLAY_SYNC")
+_OWN_STREAM = switches.on("VILCO_GRAPH_OWN_STREAM")      # replays leave the default (null) stream: GraphedStep._replay
 # data-parallel replays: the backward captured as one hipGraph per stage (heads + losses, then block by block -- ops.seg_cut),
 # the gradient buckets a stage completes launched right behind its replay, under the stages that follow.  0: one graph, the
 # whole exchange after it.
@@ -51,11 +50,11 @@ _OWN_STREAM = os.environ.get("VILCO_GRAPH_OWN_STREAM", "1") != "0"      # replay
 # the stage graphs, the small gradients (the ones gathered into their bucket by a copy) came back stale or as garbage once the
 # host ran ahead (not RCCL, not the multi-tensor copy, not Python's GC; exact on any created stream).  _replay therefore moves
 # every replay off the null stream.
-_DP_SEGMENTS = os.environ.get("VILCO_DP_SEGMENTS", "1") != "0"
+_DP_SEGMENTS = switches.on("VILCO_DP_SEGMENTS")
 
 
 _replay_streams = {}
-_SHARED_STREAM = os.environ.get("VILCO_GRAPH_SHARED_STREAM", "1") != "0"
+_SHARED_STREAM = switches.on("VILCO_GRAPH_SHARED_STREAM")
 
 
 def _replay_stream(device):
@@ -109,7 +108,7 @@ class GraphedStep:
         self.between, self.enabled, self.gt_pad, self.max_graphs = between, bool(enabled), gt_pad, int(max_graphs)
         self.narr_pad = int(narr_pad)
         self.reducer = reducer
-        self.comm_in_graph = (os.environ.get("VILCO_DP_GRAPH_COMM", "0") == "1") if comm_in_graph is None else bool(comm_in_graph)
+        self.comm_in_graph = (switches.text("VILCO_DP_GRAPH_COMM") == "1") if comm_in_graph is None else bool(comm_in_graph)
         self.segments = _DP_SEGMENTS if segments is None else bool(segments)
         self._graphs = {}
         self._pool = None

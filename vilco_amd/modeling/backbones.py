@@ -7,7 +7,7 @@ import os
 import torch
 from torch import nn
 
-from .. import ops
+from .. import ops, switches
 from .blocks import (LayerNorm, MaskedConv1D, TransformerBlock, from_tm, get_sinusoid_encoding,
                      lens_to_mask, mask_to_lens, to_tm)
 from .modeling_xlnet_x import XLNetConfig, XLNetModel
@@ -28,7 +28,7 @@ def _find_xlnet_config(n_embd):
     """the reference opens 'configs/xlnet_config_<D>.json' relative to CWD (backbones.py:132);
     VILCO_XLNET_CONFIG_DIR may point elsewhere.  None when no file exists for this width."""
     name = 'xlnet_config_%s.json' % n_embd
-    for d in (os.environ.get("VILCO_XLNET_CONFIG_DIR"), 'configs'):
+    for d in (switches.text("VILCO_XLNET_CONFIG_DIR"), 'configs'):
         if d and os.path.exists(os.path.join(d, name)):
             return os.path.join(d, name)
     return None

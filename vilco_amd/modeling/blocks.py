@@ -14,12 +14,11 @@ the isinstance checks of make_optimizer, train_utils.py:76-77); their forward is
 import math
 
 import numpy as np
-import os
 
 import torch
 from torch import nn
 
-from .. import ops
+from .. import ops, switches
 from ..ops import ACT_GELU, ACT_NONE
 
 
@@ -287,7 +286,7 @@ class ChannelAttention(nn.Module):
     # kept), so the padded rows of a short clip carry non-zero values through it; in a backbone that applies the block
     # twice (no XLNet layer, backbones.py:276-278) the first padded row's gradient reaches ~1e10 x the typical element, more
     # exponent range than ONE power-of-two scale per tensor leaves to the other rows of the fp16 x2 planes.
-    WIDE_PARTS = tuple(x for x in os.environ.get("VILCO_CA_WIDE", "qkv,core,proj").split(",") if x)
+    WIDE_PARTS = tuple(x for x in switches.text("VILCO_CA_WIDE").split(",") if x)
 
     def __init__(self, dim, num_heads=8, qkv_bias=False):
         super().__init__()

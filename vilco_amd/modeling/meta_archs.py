@@ -12,13 +12,12 @@ inference), same state_dict keys and the attributes / methods train_cl.py reads.
 reductions are [4536 x N] / [#valid x ncls] device tensor expressions under autograd.
 """
 import math
-import os
 
 import torch
 from torch import nn
 from torch.nn import functional as F
 
-from .. import ops
+from .. import ops, switches
 from ..cl_methods import Prompt
 from ..utils.nms import batched_nms
 from ..utils.model_ema import ModelEmaV2
@@ -178,7 +177,7 @@ class _ConvHead(nn.Module):
         return all(m.conv.kernel_size[0] == 3 and m.stride == 1 and m.conv.groups == 1 for m in heads)
 
 
-_HEAD_ROWMASK = os.environ.get("VILCO_HEAD_ROWMASK", "1") != "0"
+_HEAD_ROWMASK = switches.on("VILCO_HEAD_ROWMASK")
 
 
 class LevelCat:
@@ -386,9 +385,6 @@ class PtTransformer(nn.Module):
                                              kernel_size=head_kernel_size, num_layers=head_num_layers,
                                              with_ln=head_with_ln, num_bins=0)
 
-        # run both heads over all pyramid levels at once (LevelCat); VILCO_LEVEL_CAT=0 keeps the per-level loop
-        self.level_cat = os.environ.get("VILCO_LEVEL_CAT", "1") != "0"
-
         nc = self.num_classes
         self.mu = nn.Parameter(torch.zeros(nc, 1), requires_grad=True)
         self.sigma = nn.Parameter(torch.ones(nc, 1), requires_grad=True)
@@ -398,9 +394,7 @@ class PtTransformer(nn.Module):
         self.sigma_reg_right = nn.Parameter(torch.ones(nc, 1), requires_grad=True)
 
         self.loss_normalizer = t['init_loss_norm']     # EMA, not checkpointed (:611); a device scalar in the sync-free path
-        self.sync_free_loss = os.environ.get("VILCO_SYNC_FREE_LOSS", "1") != "0"
-        self.fused_loss = os.environ.get("VILCO_FUSED_LOSS", "1") != "0"      # ops.mq_loss (0: tensor expressions)
-        self.fused_ssl = os.environ.get("VILCO_FUSED_SSL", "1") != "0"        # ops.ssl_pool / ssl_nce (0: tensor expressions)
+        self._read_switches()
         self.loss_normalizer_momentum = 0.9
         self.reg_params = {}
 
@@ -433,6 +427,12 @@ class PtTransformer(nn.Module):
             self.adapt_blocks = cl_cfg['adapt_blocks']
             self.num_freeze_epochs = 10
             self.setup_adpat()
+
+    def _read_switches(self):       # at construction: from __init__ and from the NLQ constructor, which does not run this class's
+        self.level_cat = switches.on("VILCO_LEVEL_CAT")             # both heads over all pyramid levels at once (0: the per-level loop)
+        self.sync_free_loss = switches.on("VILCO_SYNC_FREE_LOSS")
+        self.fused_loss = switches.on("VILCO_FUSED_LOSS")           # ops.mq_loss (0: tensor expressions)
+        self.fused_ssl = switches.on("VILCO_FUSED_SSL")             # ops.ssl_pool / ssl_nce (0: tensor expressions)
 
     # ------------------------------------------------------------------ adapters / EMA (ViLCo)
     def setup_adpat(self):
@@ -1179,7 +1179,7 @@ class PtTransformer(nn.Module):
         """threshold -> top-k -> decode per level (meta_archs.py:1594-1692).  On the device the whole pyramid of the clip
         is one vilco_decode call (exact top-k by radix select, one host read: the candidate count); VILCO_DEVICE_DECODE=0
         or host tensors take the tensor-expression path below, which mirrors the reference line by line."""
-        if cls_preds_per_vid is None and out_cls_logits[0].is_cuda and os.environ.get("VILCO_DEVICE_DECODE", "1") != "0":
+        if cls_preds_per_vid is None and out_cls_logits[0].is_cuda and switches.on("VILCO_DEVICE_DECODE"):
             lens = [int(c.shape[0]) for c in out_cls_logits]
             row0 = torch.tensor([sum(lens[:i]) for i in range(len(lens))], dtype=torch.int32, device=out_cls_logits[0].device)
             level_len = torch.stack([m.sum() for m in fpn_masks]).to(torch.int32)

@@ -14,8 +14,6 @@ differs: the constructor (the reference's kwargs and state_dict keys: no mu / si
 kernel are switched off by constant (non-persistent) buffers with sigma = 1e15: exp(-(rel - mu)^2 / 2 sigma^2) is
 exactly 1.0f.
 """
-import os
-
 import torch
 from torch import nn
 
@@ -89,7 +87,6 @@ class PtTransformer(mq.PtTransformer):
                                                 num_layers=head_num_layers, empty_cls=t['head_empty_cls'])
         self.reg_head = mq.PtTransformerRegHead(fpn_dim, head_dim, len(self.fpn_strides), kernel_size=head_kernel_size,
                                                 num_layers=head_num_layers, with_ln=head_with_ln, num_bins=0)
-        self.level_cat = os.environ.get("VILCO_LEVEL_CAT", "1") != "0"
 
         # the MQ loss kernels weight every point by gaussians of learnable (mu, sigma); NLQ has no such weights:
         # constant buffers (not parameters, not in the state_dict) with sigma = 1e15 make every weight exactly 1
@@ -99,9 +96,7 @@ class PtTransformer(mq.PtTransformer):
             self.register_buffer(name, torch.full((nc, 1), val), persistent=False)
 
         self.loss_normalizer = t['init_loss_norm']
-        self.sync_free_loss = os.environ.get("VILCO_SYNC_FREE_LOSS", "1") != "0"
-        self.fused_loss = os.environ.get("VILCO_FUSED_LOSS", "1") != "0"
-        self.fused_ssl = os.environ.get("VILCO_FUSED_SSL", "1") != "0"
+        self._read_switches()
         self.loss_normalizer_momentum = 0.9
         self.reg_params = {}
 

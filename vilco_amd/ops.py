@@ -8,17 +8,16 @@ There is deliberately no CPU / ATen fallback: a non-CUDA tensor raises.
 """
 import ctypes as C
 import math
-import os
 
 import torch
 
-from . import _lib
+from . import _lib, switches
 from ._lib import ACT_GELU, ACT_NONE, ACT_RELU, TAP_A, TAP_B, TAP_NONE, GemmDesc
 
 # 0 = split-bf16 (hi+lo, 3 MFMAs), 1 = single bf16 pass, 2 = three-part bf16 split (6 MFMAs, ~2^-25),
 # 3 = two fp16 parts of per-tensor scaled operands (3 MFMAs, ~2^-22; attention keeps the three bf16 parts)
 _PRECISIONS = {"split": 0, 0: 0, "bf16": 1, 1: 1, "split3": 2, "fp32": 2, 2: 2, "f16x2": 3, 3: 3}
-DEFAULT_PRECISION = _PRECISIONS[os.environ.get("VILCO_PRECISION", "f16x2")]
+DEFAULT_PRECISION = _PRECISIONS[switches.text("VILCO_PRECISION")]
 _precision = DEFAULT_PRECISION
 
 
@@ -31,7 +30,7 @@ _precision = DEFAULT_PRECISION
 # 2e-4 .. 3.5e-4 at K = 4608 (config P, tests/test_fullsize_gpu.py).  So it is used for LONG contractions only (K >= DW_FAST_MIN_K), where
 # the time is; short ones keep three MFMAs.  VILCO_DW_PRECISION=f16x2 restores three MFMAs everywhere.
 _DW = {"f16x1": 4, "f16x2": None}
-dw_precision = _DW[os.environ.get("VILCO_DW_PRECISION", "f16x1")]
+dw_precision = _DW[switches.text("VILCO_DW_PRECISION")]
 DW_FAST_MIN_K = 2048
 
 
@@ -52,15 +51,13 @@ def set_precision(p=None):
 def arithmetic_key():
     """Everything that decides WHICH arithmetic a step's kernels run with and is a module-level switch rather than an input:
     a captured hipGraph replays the kernels it recorded, so graph.GraphedStep keys its graphs on this tuple (VERDICT r04,
-    weak 2: flipping set_precision / dw_precision between replays used to replay the old arithmetic silently)."""
-    return (int(_precision), -1 if dw_precision is None else int(dw_precision), int(DW_FAST_MIN_K), bool(producer_planes),
-            bool(ln_planes), bool(attn_planes), bool(produce_amax), bool(conv_tap_planes), bool(defer_finish), bool(use_qkv_pre),
-            tuple(sorted(_FORKS)), int(_dw_fork_rows),
-            # (ADVICE r05) the remaining switches that change which kernels / roundings a step records, and the library's own
-            # configuration generation (vilco_gemm_force / vilco_gemm_set_skinny)
-            bool(fold_skip_grads), bool(xl_ds_planes), bool(xl_scores_kernel), bool(linear_group_enabled), bool(use_flash),
-            bool(_reuse_packs), bool(_weight_cache), str(range_check), int(_lib.load().vilco_gemm_config_gen()), bool(pack_group_enabled), bool(conv_dz_planes), bool(ln_bwd_amax),
-            bool(fused_prompt))
+    weak 2: flipping set_precision / dw_precision between replays used to replay the old arithmetic silently).  The switches
+    come from switches.TABLE (every row marked KEYED that names an attribute of this module); no variable sets the other
+    three: the active precision, DW_FAST_MIN_K and the library's own configuration generation (vilco_gemm_force /
+    vilco_gemm_set_skinny).  Only ever compared for equality inside one process."""
+    g = globals()
+    return (_precision, DW_FAST_MIN_K, _lib.load().vilco_gemm_config_gen(),
+            *[frozenset(v) if type(v) is set else v for v in map(g.__getitem__, switches.KEYED_OPS)])
 
 
 def get_precision():
@@ -103,7 +100,7 @@ def _grad_out(w):
 # waits for them) beside the dX chain -- they fill the CUs that the 75 %-full GEMM rounds of this model's shapes leave
 # idle.  VILCO_GRAPH_STREAMS lists what is forked ("text,heads,dw"; "" = nothing); only active while a stream is capturing
 # (in eager mode a second queue made the step time erratic, DESIGN_LOG.md 3.6).
-_FORKS = set(x for x in os.environ.get("VILCO_GRAPH_STREAMS", "text,heads").split(",") if x)
+_FORKS = set(x for x in switches.text("VILCO_GRAPH_STREAMS").split(",") if x)
 _side_streams = {}
 _dw_seen = set()
 
@@ -140,7 +137,7 @@ def join_side_streams():
 
 # "dw" forks only the weight-gradient products whose contraction runs over at most this many token rows (0: all of them): the
 # products of the small pyramid levels, which sit on a chain that leaves most of the chip idle anyway
-_dw_fork_rows = int(os.environ.get("VILCO_DW_FORK_ROWS", "0"))
+_dw_fork_rows = switches.number("VILCO_DW_FORK_ROWS")
 
 
 class _DwFork:
@@ -201,7 +198,7 @@ def _ws(nbytes, device):
 #     complete bucket), so it blocks deferral while they are live (`defer_blocked`).
 # Tensors a recorded item reads or writes are held until the flush (a gradient autograd drops would otherwise hand its
 # memory to the next allocation).  VILCO_DEFER_FINISH=0 switches the whole thing off (tested equal).
-defer_finish = os.environ.get("VILCO_DEFER_FINISH", "1") != "0"
+defer_finish = switches.on("VILCO_DEFER_FINISH")
 defer_blocked = False
 _defer = {"on": False, "armed": False, "task": -1, "keep": [], "pending": set(), "seen": set()}
 
@@ -240,7 +237,7 @@ def _defer_flush(final=True):
 #   VILCO_RANGE_CHECK=warn   every Linear backward measures max-row / median-row amax of dZ (a host sync: debug mode only),
 #                            records (M, N, K, spread) in ops.range_events and warns once per shape above 2^20;
 #   VILCO_RANGE_CHECK=auto   ... and runs that call's two backward products in bf16 x3.
-range_check = os.environ.get("VILCO_RANGE_CHECK", "0")
+range_check = switches.text("VILCO_RANGE_CHECK")
 RANGE_SPREAD_LIMIT = float(2 ** 20)
 range_events = []
 _range_warned = set()
@@ -463,9 +460,9 @@ def gemm_group(calls):
 # themselves ("planes": the consumer's `pack` / `pack_tap` is then a lookup, like for a tensor that was packed before).
 # Both hang on the tensor as ONE record (`_Hints`), read and written through the accessors below and nowhere else.
 # amax is ignored once the tensor's version counter moved (in-place edits) or another precision is active.
-produce_amax = os.environ.get("VILCO_PRODUCER_AMAX", "1") != "0"
+produce_amax = switches.on("VILCO_PRODUCER_AMAX")
 AMAX_PARTS = 2048
-_pack_cache = os.environ.get("VILCO_PACK_CACHE", "1") != "0"
+_pack_cache = switches.on("VILCO_PACK_CACHE")
 
 
 class _Hints:
@@ -661,9 +658,9 @@ def pack_many(items, precision=None, nbatch=1, relshift=False):
     return bufs
 
 
-pack_group_enabled = os.environ.get("VILCO_PACK_GROUP", "1") != "0"
-ln_bwd_amax = os.environ.get("VILCO_LN_BWD_AMAX", "1") != "0"                # LayerNorm backward leaves max|dx| partials
-conv_dz_planes = os.environ.get("VILCO_CONV_DZ_PLANES", "1") != "0"      # masked k=3 convs: dZ's operand image from the mask kernel itself
+pack_group_enabled = switches.on("VILCO_PACK_GROUP")
+ln_bwd_amax = switches.on("VILCO_LN_BWD_AMAX")            # LayerNorm backward leaves max|dx| partials
+conv_dz_planes = switches.on("VILCO_CONV_DZ_PLANES")      # masked k=3 convs: dZ's operand image from the mask kernel itself
 
 
 def pack_group(xs, rows, cols, precision=None):
@@ -682,16 +679,16 @@ def pack_group(xs, rows, cols, precision=None):
 
 
 # packed operands are shared between forward, dX and dW (env VILCO_PACK_REUSE=0: every GEMM packs its own operands)
-_reuse_packs = os.environ.get("VILCO_PACK_REUSE", "1") != "0"
+_reuse_packs = switches.on("VILCO_PACK_REUSE")
 # k=3 convs: x and dZ packed once each in the zero-padded per-sequence image, for all three products (VILCO_CONV_TAP_PLANES=0,
 # or VILCO_CONV_DW_KM=0 which also takes the weight gradient back to its transposing packs)
-conv_tap_planes = os.environ.get("VILCO_CONV_TAP_PLANES", "1") != "0" and os.environ.get("VILCO_CONV_DW_KM", "1") != "0"
+conv_tap_planes = switches.on("VILCO_CONV_TAP_PLANES") and switches.on("VILCO_CONV_DW_KM")
 
 # ---- weight planes are packed ONCE per parameter version, not once per step.  A weight's planes (and the re-laid
 # [Cout][tap][Cin] images of k=3 conv weights) are cached on the parameter object, keyed by torch's in-place version
 # counter plus a generation number that everything writing parameters behind autograd's back must bump
 # (`weights_changed()`: FusedOptimizer.step does).  VILCO_WEIGHT_CACHE=0 re-packs on every call.
-_weight_cache = os.environ.get("VILCO_WEIGHT_CACHE", "1") != "0"
+_weight_cache = switches.on("VILCO_WEIGHT_CACHE")
 _weight_gen = [0]
 
 
@@ -757,9 +754,9 @@ def weight_planes(w, rows, cols):
 # dz of a layer goes nowhere but into its two backward products: `_act_bwd(planes=True)` has the kernel write dz as operand planes
 # (vilco_act_bwd_desc.planes: scale from a bound on max|dz|, no pack launch, no fp32 dz) when dy carries its producer's amax partials.
 # VILCO_PRODUCER_PLANES=0: fp32 dz + pack, as before.
-producer_planes = os.environ.get("VILCO_PRODUCER_PLANES", "1") != "0"
-ln_planes = os.environ.get("VILCO_LN_PLANES", "1") != "0"          # the LayerNorm half of it (ops.layernorm(planes=...))
-attn_planes = os.environ.get("VILCO_ATTN_PLANES", "1") != "0"      # the attention-output part (hd = 64 forward kernels)
+producer_planes = switches.on("VILCO_PRODUCER_PLANES")
+ln_planes = switches.on("VILCO_LN_PLANES")          # the LayerNorm half of it (ops.layernorm(planes=...))
+attn_planes = switches.on("VILCO_ATTN_PLANES")      # the attention-output part (hd = 64 forward kernels)
 
 
 def _act_bwd(dy, aux, act, lens, T, want_bias, drop=(0.0, 0), bias_param=None, planes=False, row_mask=None):
@@ -965,7 +962,7 @@ class _LinearGroup(torch.autograd.Function):
         return (None, *dxs, *dws, *dbs)
 
 
-linear_group_enabled = os.environ.get("VILCO_LINEAR_GROUP", "1") != "0"
+linear_group_enabled = switches.on("VILCO_LINEAR_GROUP")
 
 
 def linear_group(xs, ws, bs):
@@ -1548,10 +1545,10 @@ def _flash_fwd(q, k, v, bias, kv_len, H, scale, mode, drop=(0.0, 0), window=0, h
 # buffer per (device, B*H, T) is zeroed when first needed and reused by every later backward (1.36 GB at config P; a step
 # captured as a hipGraph has met it in the eager iterations before the capture).  VILCO_XL_DS_PLANES=0: the fp32 dS + pack path.
 # residual joins: the skip gradient is added inside the LayerNorm backward kernel (VILCO_FOLD_SKIP=0: autograd's own add_)
-fold_skip_grads = os.environ.get("VILCO_FOLD_SKIP", "1") != "0"
-xl_ds_planes = os.environ.get("VILCO_XL_DS_PLANES", "1") != "0"
+fold_skip_grads = switches.on("VILCO_FOLD_SKIP")
+xl_ds_planes = switches.on("VILCO_XL_DS_PLANES")
 # XLNet forward: the position scores by vilco_xl_scores (dedicated kernel) instead of the band-limited K = 64 GEMM (VILCO_XL_SCORES=0)
-xl_scores_kernel = os.environ.get("VILCO_XL_SCORES", "1") != "0"
+xl_scores_kernel = switches.on("VILCO_XL_SCORES")
 _ds_plane_bufs = {}
 
 
@@ -2163,7 +2160,7 @@ def bic_correct(logits, splits, layers, inplace=False):
 # ---------------------------------------------------------------------------------------- L2P prompt pool
 # VILCO_FUSED_PROMPT=0: cl_methods.Prompt keeps its tensor-op body on the device too (A/B runs).  Part of arithmetic_key():
 # a captured step replays the path it recorded.
-fused_prompt = os.environ.get("VILCO_FUSED_PROMPT", "1") != "0"
+fused_prompt = switches.on("VILCO_FUSED_PROMPT")
 PROMPT_KEY_MODES = {'mean': 0, 'max': 1, 'mean_max': 2, 'cls': 3}
 _prompt_windows = {}
 
@@ -2519,7 +2516,7 @@ def qkv_pre_supported(Cn):
     return bool(_lib.load().vilco_qkv_pre_supported(int(Cn)))
 
 
-use_qkv_pre = os.environ.get("VILCO_QKV_PRE", "1") != "0"
+use_qkv_pre = switches.on("VILCO_QKV_PRE")
 
 
 def _ptr3(ts):

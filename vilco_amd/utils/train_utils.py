@@ -14,12 +14,12 @@ import numpy as np
 import torch
 from torch import optim
 
-from .. import _lib, ops
+from .. import _lib, ops, switches
 from ..modeling.blocks import AffineDropPath, LayerNorm, MaskedConv1D, Scale
 from .lr_schedulers import LinearWarmupCosineAnnealingLR, LinearWarmupMultiStepLR
 
 CHUNK = ops.CHUNK
-OPT_AMAX = os.environ.get("VILCO_OPT_AMAX", "1") != "0"      # the update kernels leave max|w| per chunk for the weight packs
+OPT_AMAX = switches.on("VILCO_OPT_AMAX")      # the update kernels leave max|w| per chunk for the weight packs
 
 
 def fix_random_seed(seed, include_cuda=True):
