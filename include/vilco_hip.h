@@ -299,7 +299,11 @@ int vilco_relshift_bwd(const float* ds, float* dbd, float scale, int32_t B, int3
 /* q [B,Tq,H*hd], k/v [B,Tk,H*hd], bias [B,H,Tq,Tk] or null, lse [B,H,Tq] (saved for backward).     */
 /* mask modes as vilco_softmax_fwd (+ 3: XLNet mask with the bias given as unshifted position scores [B,H,Tq,Tq+Tk]; */
 /* + 4: sliding window |i - j| <= window below kv_len, Tq == Tk -- NLQ's LocalMaskedMHCA, NLQ/libs/modeling/blocks.py   */
-/* :417-755; only the key tiles a query tile's windows reach are visited);                                           */
+/* :417-755; only the key tiles a query tile's windows reach are visited.  window >= Tk is taken as window = Tk -- every key    */
+/* below kv_len, the same for any such value up to INT32_MAX.  A query row with no key left (i - window >= kv_len[b]) gives a */
+/* zero row of o and of dq and enters no gradient; kv_len[b] = 0 in this mode gives exact zeros in o, dq, dk and dv of clip b */
+/* and nothing else anywhere.  A query row with exactly one key (window 0, a clip of length 1) has the constant softmax 1: */
+/* it adds exactly zero to dq and dk, and only to dv);                                                                        */
 /* precision as vilco_gemm.  hd <= 160 (<= 64 in bf16 x3), hd % 4 == 0.  drop_p > 0: inverted dropout on the attention probabilities      */
 /* (after the softmax, before P V) with a counter-based mask of its own (round 5; vilco_attn_dropout_mask writes it     */
 /* out): one strong hash per row bh*Tq + i of stream drop_seed, a two-multiply finalizer per element (row key, j);      */

@@ -138,18 +138,27 @@ def test_local_attention_full_size_equals_dense_masked(dev):
     o = ops.attention(q, k, v, lens, H, mode=ops.MASK_LOCAL, window=w)
     wt = torch.randn_like(o)
     (o * wt).sum().backward()
-    # dense reference in fp64 on one (b, h) slice per clip
+    # dense reference in fp64 on one (b, h) slice per clip, with its gradients.  Query rows from L + w on have no key left:
+    # they give zero rows and enter no gradient, so the reference is built on the rows before them.  dk and dv of a head sum
+    # over all of those rows (the ones between L and L + w still attend keys below L); dq is compared below L.
     for b in range(B):
         L = int(lens[b])
+        R = min(T, L + w)
         for h in (0, H - 1):
             sl = slice(h * hd, (h + 1) * hd)
-            qq, kk, vv = [t[b, :, sl].detach().double().cpu() for t in (q, k, v)]
-            att = (qq @ kk.t()) / hd ** 0.5
+            qq, kk, vv = [t[b, :, sl].detach().double().cpu().requires_grad_(True) for t in (q, k, v)]
+            att = (qq[:R] @ kk.t()) / hd ** 0.5
             idx = torch.arange(T)
-            ok = ((idx[:, None] - idx[None, :]).abs() <= w) & (idx[None, :] < L)
+            ok = ((idx[:R, None] - idx[None, :]).abs() <= w) & (idx[None, :] < L)
             att = att.masked_fill(~ok, float('-inf')).softmax(-1)
             want = att @ vv
             assert rel_err(o[b, :L, sl], want[:L]) < 1e-4
+            (want * wt[b, :R, sl].double().cpu()).sum().backward()
+            errs = (rel_err(q.grad[b, :L, sl], qq.grad[:L]), rel_err(k.grad[b, :, sl], kk.grad), rel_err(v.grad[b, :, sl], vv.grad))
+            print("clip %d head %d: dq %.3e dk %.3e dv %.3e" % ((b, h) + errs))
+            assert max(errs) < 1e-4, (b, h, errs)
+            assert torch.count_nonzero(q.grad[b, R:, sl]) == 0 and torch.count_nonzero(k.grad[b, L:, sl]) == 0
+            assert torch.count_nonzero(v.grad[b, L:, sl]) == 0
     k2 = k.detach().clone()
     k2[:, 1000:1100] += 5.0                                    # keys 1000..1099 are outside every window of queries < 980
     o2 = ops.attention(q.detach(), k2, v.detach(), lens, H, mode=ops.MASK_LOCAL, window=w)

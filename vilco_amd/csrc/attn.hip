@@ -297,6 +297,17 @@ __device__ __forceinline__ float mask_score(float s, int i, int j, int len, int 
   return s;
 }
 
+// mode 4: query i has exactly ONE key (its window, cut at kv_len, holds a single index: window 0, a clip of length 1).
+// The row's softmax is the constant 1, so its dS = P (dP - delta) is exactly zero and it takes no part in dq or dk.  dP
+// (an MFMA over the operand planes) and delta (dO . O from the stored output) agree only to rounding, so the backward
+// kernels drop the row's dS instead of leaving that rounding in the gradients; o and dv of the row are untouched.
+__device__ __forceinline__ bool one_key_row(int i, int len, int Tk, int mode, int w) {
+  if (mode != 4) return false;
+  const int kend = len < Tk ? len : Tk;
+  const int hi = i + w + 1 < kend ? i + w + 1 : kend, lo = i - w > 0 ? i - w : 0;      // w <= Tk: launch prologue
+  return hi - lo == 1;
+}
+
 // ------------------------------------------------------------------------------------------ forward
 // dynamic LDS (bytes) of attn_fwd_kernel: sK + sVt + sP.  Every kernel's figure stands like this one above its carve-up;
 // launch_attn() takes both the attribute and the launch size from it
@@ -1003,7 +1014,8 @@ __global__ __launch_bounds__(ATT_THREADS) void attn_bwd_dq_kernel(AttnArgs a) {
   QFrag<HDP, NP> qf, dof;
   load_qfrag<HDP, NP>(qf, a.qn, a.qn.p + (long)bh * a.qn.batch_stride, q0, lane);
   load_qfrag<HDP, NP>(dof, a.don, a.don.p + (long)bh * a.don.batch_stride, q0, lane);
-  const float lse = qi < a.Tq ? a.lse[row_bh + qi] : 0.f;
+  // a row with one key: lse = +inf makes every P below exp(-inf) = 0, hence dS = 0 (P is used for nothing else here)
+  const float lse = one_key_row(qi, len, a.Tk, mmode, a.window) ? INFINITY : (qi < a.Tq ? a.lse[row_bh + qi] : 0.f);
   // (1-p) delta in plane units.  Multiplied by the two scales one after the other: their product alone overflows fp32
   // when both tensors are tiny or zero (a clip dropped by stochastic depth has dO == 0 -> s = 2^126), delta * sdO does not
   // delta_i = dO_i . O_i in exact fp32: lane group g covers channels ks*32 + 8g .. +7 of this lane's query, two
@@ -1848,11 +1860,12 @@ __global__ __launch_bounds__(ATT_THREADS) void attn_bwd_dkdv_kernel(AttnArgs a) 
     }
 
     // lane: key col = lane & 15 (per n-tile), query rows 4*(lane>>4) + r of m-tile mq
-    float lse4[4], dl4[4];
+    float lse4[4], dl4[4], dsc4[4];      // dsc4: the plane scale of dS, or 0 for a row with one key (its dS is zero; P stays)
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int qi = q0 + mq * 16 + (lane >> 4) * 4 + r;
       lse4[r] = qi < a.Tq ? a.lse[row_bh + qi] : 0.f;
+      dsc4[r] = one_key_row(qi, len, a.Tk, mmode, a.window) ? 0.f : (F16 ? ds_scale<HDP>() : 1.f);
       const float dl_ = qi < a.Tq ? a.delta[row_bh + qi] : 0.f;
       dl4[r] = (F16 ? (dl_ * sc.sdo) * sc.sv : dl_) / a.drop_inv_keep;      // see attn_bwd_dq_kernel: never form sdO * sV
     }
@@ -1914,9 +1927,9 @@ __global__ __launch_bounds__(ATT_THREADS) void attn_bwd_dkdv_kernel(AttnArgs a) 
         }
         p[r] = (qi < a.Tq && x != -INFINITY) ? fast_exp(x - lse4[r]) : 0.f;
         const float mf = (!DROP || ((keep_bits >> (nj * 4 + r)) & 1u)) ? 1.f : 0.f;
-        ds[r] = p[r] * (dp[r] * mf - dl4[r]);
+        ds[r] = p[r] * (dp[r] * mf - dl4[r]) * dsc4[r];
         p[r] *= mf;                                      // dV sees the dropped probabilities
-        if (F16) { ds[r] *= ds_scale<HDP>(); p[r] *= P_SCALE; }
+        if (F16) p[r] *= P_SCALE;
       }
       bf16x4 pp[3], dd[3];
       split4s<NP, F16>(p, pp);
@@ -2218,7 +2231,10 @@ int attn_begin(const vilco_attn_desc* d, void* stream, bool bwd, AttnCall& c) {
   if (!d->workspace || d->workspace_bytes < need) return VILCO_ERR_WORKSPACE;
   AttnArgs& a = c.a;
   a.q = d->q; a.k = d->k; a.v = d->v; a.bias = d->bias; a.lse = d->lse; a.kv_len = d->kv_len;
-  a.B = B; a.H = H; a.Tq = Tq; a.Tk = Tk; a.hd = hd; a.C = H * hd; a.scale = d->scale; a.mode = d->mode; a.window = d->window;
+  a.B = B; a.H = H; a.Tq = Tq; a.Tk = Tk; a.hd = hd; a.C = H * hd; a.scale = d->scale; a.mode = d->mode;
+  // |i - j| < Tk always, so any window >= Tk is window = Tk; clamped here so that no kernel's tile bounds (qt * 64 + 63 + window,
+  // k0 + 63 + window: int sums) meet a value they can overflow with
+  a.window = d->window < Tk ? d->window : Tk;
   a.drop_thresh = vilco_drop_threshold_host(d->drop_p); a.drop_seed = d->drop_seed; a.drop_inv_keep = 1.f / (1.f - d->drop_p);
   a.seed_word = vilco_seed_word_dev();
   c.s = reinterpret_cast<hipStream_t>(stream); c.precision = precision;
