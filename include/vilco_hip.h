@@ -131,6 +131,19 @@ int vilco_gemm(const vilco_gemm_desc* d, void* stream);
  * plan without split-K; anything else runs as n vilco_gemm calls in order.  Same arithmetic either way.  VILCO_GEMM_GROUP=0:
  * always ungrouped. */
 int vilco_gemm_group(const vilco_gemm_desc* descs, int32_t n, void* stream);
+/* Precision 4 (the single-part weight gradients dW = dZ^T X; reference: autograd's weight gradient of every nn.Linear / 1x1
+ * MaskedConv1D of blocks.py) is grouped too, for any n >= 2: equal products with packed operands and the plain epilogue (alpha 1,
+ * beta 0, nothing fused), no batch / tap / band, nothing forced by vilco_gemm_force, run as one gemm_pp_group_kernel launch per
+ * 16 products -- n x tiles >= 256 workgroups: no split-K, each dW written once; fewer: the smallest split count that fills one
+ * round of the chip.  One pass over K per output element instead of one per slab: same products, another summation order than
+ * the split plan of a lone launch (bit-equal to a lone launch with one split).  Every member's workspace must hold
+ * vilco_gemm_group_workspace(member, n) bytes.  VILCO_GEMM_GROUP_DW=0 (or a group the plan prices above its members): n
+ * vilco_gemm calls in order. */
+size_t vilco_gemm_group_workspace(const vilco_gemm_desc* d, int32_t n);
+/* the switch of the precision-4 groups (initial value: environment VILCO_GEMM_GROUP_DW, default 1) and its current value; the
+ * setter bumps vilco_gemm_config_gen(): the summation order of the grouped weight gradients differs from the split plans'. */
+int vilco_gemm_set_group_dw(int32_t on);
+int32_t vilco_gemm_group_dw(void);
 
 /* Timing of the MFMA kernel alone (not the packs, not the split-K reduce): between begin and end every vilco_gemm   */
 /* brackets its main kernel with HIP events on the caller's stream; end waits for them and returns the sum.          */

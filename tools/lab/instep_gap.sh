@@ -18,7 +18,9 @@ def gemm_rows(f):
     rows = collections.OrderedDict()
     for r in csv.DictReader(open(f)):
         n = r['Kernel_Name']
-        if 'gemm_gl' not in n and 'gemm_pp' not in n: continue
+        # every kernel a vilco_gemm / vilco_gemm_group record stands for (gemm_pp covers gemm_pp_group_kernel, gemm_gl the grouped
+        # two-part kernel): one left out here shifts every later record against its dispatch
+        if not any(k in n for k in ('gemm_gl', 'gemm_pp', 'gemm_pp_group', 'gemm_skinny')): continue
         rows.setdefault(int(r['Dispatch_Id']), {})[r['Counter_Name']] = float(r['Counter_Value'])
     return [rows[k] for k in sorted(rows)]
 def med(v):

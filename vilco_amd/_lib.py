@@ -165,6 +165,9 @@ SIGNATURES = {
     "vilco_gemm_workspace": (sz, [C.POINTER(GemmDesc)]),
     "vilco_gemm": (C.c_int, [C.POINTER(GemmDesc), c_fp]),
     "vilco_gemm_group": (C.c_int, [C.POINTER(GemmDesc), i32, c_fp]),
+    "vilco_gemm_group_workspace": (sz, [C.POINTER(GemmDesc), i32]),
+    "vilco_gemm_set_group_dw": (C.c_int, [i32]),
+    "vilco_gemm_group_dw": (i32, []),
     "vilco_gemm_amax_parts": (i32, [C.POINTER(GemmDesc)]),
     "vilco_gemm_force": (C.c_int, [i32, i32]),
     "vilco_gemm_set_skinny": (C.c_int, [i32]),

@@ -284,8 +284,14 @@ constexpr size_t pp_lds() {
 // elements of K -- 2 MFMAs per fragment pair, the same fragment reads and staging traffic as a two-part step.  With one
 // part and 32 elements per interval the loop was bound by its MEM phase (16 MFMAs per wave against ~1000 cycles of
 // reads, stores and loads: ~2000 cycles per 32 k, MFMA pipe 25 % busy); the interval's fixed cost now buys twice the K.
-template <int BM, int NP, bool F16, bool AKM, bool BKM, bool K2 = false>
-__global__ __launch_bounds__(512) void gemm_pp_kernel(GArgs g) {
+// XCD-aware tile order: workgroup i runs on XCD i % 8, so XCD x takes a contiguous run of the nwg tiles (its operands stay in its L2)
+__device__ __forceinline__ int xcd_order(int bid, int nwg) {
+  const int q = nwg >> 3, r = nwg & 7, x = bid & 7;
+  return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (bid >> 3);
+}
+// the kernel's body: tile `bid` (already in XCD order) of batch element `z` of the product g (the plain and the grouped kernel)
+template <int BM, int NP, bool F16, bool AKM, bool BKM, bool K2>
+__device__ __forceinline__ void gemm_pp_body(const GArgs& g, const int bid, const int z) {
   static_assert(!K2 || (NP == 2 && F16), "K2: two slots, fp16 parts");
   constexpr int NT = 512;
   constexpr int MI = BM / 64;                    // 16-row A fragments per wave (wave tile = 16*MI x 64)
@@ -309,14 +315,9 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(GArgs g) {
 #endif
   STAMPX(0);
 
-  int bid = blockIdx.x;
-  {
-    const int nwg = g.ntiles, q = nwg >> 3, r = nwg & 7, x = bid & 7;
-    bid = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (bid >> 3);
-  }
   const int tm = bid / g.tiles_n, tn = bid % g.tiles_n;
   const int m0 = tm * BM, n0 = tn * BN;
-  const int z = blockIdx.z, zo = z / g.batch_inner, zi = z % g.batch_inner;
+  const int zo = z / g.batch_inner, zi = z % g.batch_inner;
   const int ks = blockIdx.y;
 
   const __bf16* pa = g.a.p + ((long)(g.a.has_o ? zo : 0) * g.a.nbi + (g.a.has_i ? zi : 0)) * g.a.batch_stride;
@@ -548,8 +549,34 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(GArgs g) {
   }
   STAMPX(2);
 
-  gemm_epilogue<MI, F16>(g, acc, smem_raw, tid, lane, wave, wm, wn, m0, n0, bid, ks, zo, zi, (int)blockIdx.z);
+  gemm_epilogue<MI, F16>(g, acc, smem_raw, tid, lane, wave, wm, wn, m0, n0, bid, ks, zo, zi, z);
   STAMPX(3);
+}
+template <int BM, int NP, bool F16, bool AKM, bool BKM, bool K2 = false>
+__global__ __launch_bounds__(512) void gemm_pp_kernel(GArgs g) {
+  gemm_pp_body<BM, NP, F16, AKM, BKM, K2>(g, xcd_order((int)blockIdx.x, g.ntiles), (int)blockIdx.z);
+}
+
+// Grouped single-part launch: up to GROUP_MAX INDEPENDENT products of one shape, orientation and plan -- the weight gradients
+// dW = dZ^T X of a backward's equal layers -- as ONE grid on the K2 loop above.  One 1024 x 1024 x 4608 product is 64 tiles of
+// 128 rows: alone it needs four K splits to reach 256 workgroups, four fp32 slabs and a later pass that sums them; fourteen of them
+// are 3.5 rounds of the chip with no split, no slabs and one set-up / end-of-kernel write-back.  `g` is product 0's argument block;
+// what differs between the products -- operand planes, their scales, the output -- comes from the table (kernel arguments: 48 bytes
+// per product).  The linear index over (product, tile) is put in XCD order as a WHOLE: an XCD takes a contiguous run of the
+// list, i.e. all tiles of one product, then of the next, so at any time its L2 holds the operands of one or two products (ordering
+// the tiles inside every product instead would spread each product's operands over all eight L2s: n x (1 + 1/8) plane reads per XCD
+// instead of 2 n / 8).  Arithmetic per output element: the plain kernel's (same loop, same K order, same epilogue).
+constexpr int GROUP_MAX = 16;
+struct GroupEnt { const __bf16* a; const __bf16* b; float* c; float* cfinal; const float* inv_a; const float* inv_b; };
+struct GArgsG { GArgs g; GroupEnt e[GROUP_MAX]; int n; };
+template <int BM, bool AKM, bool BKM>
+__global__ __launch_bounds__(512) void gemm_pp_group_kernel(GArgsG gg) {
+  const int idx = xcd_order((int)blockIdx.x, gg.n * gg.g.ntiles);
+  const int prod = idx / gg.g.ntiles;
+  GArgs g = gg.g;
+  const GroupEnt& e = gg.e[prod];
+  g.a.p = e.a; g.b.p = e.b; g.c = e.c; g.cfinal = e.cfinal; g.inv_a = e.inv_a; g.inv_b = e.inv_b;
+  gemm_pp_body<BM, 2, true, AKM, BKM, true>(g, idx - prod * gg.g.ntiles, 0);
 }
 
 
@@ -1061,8 +1088,9 @@ struct Config {
   // are never slower (profiles/r06_skinny_bm16.txt: 154 x 1024 x 768 9.8 us against 11.4 at 32 rows, 512 x 512 x 512 7.6 against 8.6).
   const int skinny_bm16_rows = vilco_env_int("VILCO_GEMM_SKINNY_BM16", 640, 0);
   const int skinny_max_k = vilco_env_int("VILCO_GEMM_SKINNY_K", 768, 1);
-  // the three that vilco_gemm_set_skinny / vilco_gemm_force change
+  // the four that vilco_gemm_set_skinny / vilco_gemm_set_group_dw / vilco_gemm_force change
   bool skinny = vilco_env_flag("VILCO_GEMM_SKINNY", true);
+  bool group_dw = vilco_env_flag("VILCO_GEMM_GROUP_DW", true);
   int force_bm = vilco_env_int("VILCO_GEMM_BM", 0, INT_MIN), force_ks = vilco_env_int("VILCO_GEMM_KS", 0, INT_MIN);
 };
 inline Config& config() { static Config c; return c; }
@@ -1278,6 +1306,41 @@ void dw_tall(const vilco_gemm_desc* d, const Tiles& t, Kern kern, int& bm, int& 
   if (best_bm != 128 && best_t <= 0.92 * base) { bm = best_bm; ks = best_ks; }
 }
 
+// modelled time (us) of `n` equal single-part products as ONE grid of `rows`-row tiles with `k` splits, in dw_tall's constants:
+// ~9 us per launch, `c` us per 64-k interval and round, and per split product two more passes over its slabs
+inline double pp_k2_cost(const vilco_gemm_desc* d, long tn, int nk, int n, int rows, int k, double c) {
+  const long tiles = ((d->M + rows - 1) / rows) * tn * n;
+  const double split = k > 1 ? 3.0 + (double)n * d->M * d->N * 4.0 * (k + 1) / 5e6 : 0.0;
+  return 9.0 + (double)rounds(tiles * k) * ((nk + k - 1) / k) * c + split;
+}
+// The plan of a GROUP of n equal single-part products (vilco_gemm_group, precision 4; gemm_pp_group_kernel): one grid of n x tiles
+// workgroups.  n x tiles >= 256: no split.  Fewer: the smallest split count that fills one round of the 256 CUs (never below 8
+// intervals per split, at most 16 splits).  Tile height: the cheaper of 128 and 256 rows by pp_k2_cost.  Returns false when the
+// model says the group does not beat the n single launches as they are planned today by 5 %: the caller then issues those.
+bool plan_group_dw(const vilco_gemm_desc* d, const Tiling& single, int Kp, int n, Tiling& t) {
+  const long tn = (d->N + BN - 1) / BN;
+  const int nk = (Kp / BK + 1) / 2;
+  const int bms[2] = {128, 256}; const double cs[2] = {0.70, 1.02};
+  double best = 0.0;
+  for (int q = 0; q < 2; ++q) {
+    const long tiles = ((d->M + bms[q] - 1) / bms[q]) * tn * n;
+    int k = tiles >= 256 ? 1 : (int)((256 + tiles - 1) / tiles);
+    if (k > nk / 8) k = nk / 8;
+    if (k > 16) k = 16;
+    if (k < 1) k = 1;
+    const double m = pp_k2_cost(d, tn, nk, n, bms[q], k, cs[q]);
+    if (q == 0 || m < best) { best = m; t.BM = bms[q]; t.ksplit = k; }
+  }
+  const double c1 = single.BM == 256 ? 1.02 : (single.BM == 192 ? 0.95 : 0.70);
+  if (best > 0.95 * n * pp_k2_cost(d, tn, nk, 1, single.BM, single.ksplit, c1)) return false;
+  t.kern = Kern::PP_K2;
+  t.kchunk = (nk + t.ksplit - 1) / t.ksplit;
+  t.ksplit = (nk + t.kchunk - 1) / t.kchunk;
+  t.split_stride = t.ksplit > 1 ? align_up((long)(d->M - 1) * d->ldc + d->N, 64) : 0;
+  t.part_bytes = t.ksplit > 1 ? align_up(t.split_stride * t.ksplit * 4, 256) : 0;
+  return true;
+}
+
 // tuning overrides (tools/gemm_tune.py): VILCO_GEMM_BM = 128|256, VILCO_GEMM_KS = forced split count
 // (read once per process: the plan is made twice per launch)
 void force_override(const vilco_gemm_desc* d, const Tiles& t, Kern kern, int& bm, int& ks) {
@@ -1477,7 +1540,7 @@ void choose_amax(Operand& o, const AmaxOp& own_pass, const float* parts, int npa
 }
 
 // ---- a product up to its main launch
-struct Prepared { bool empty = false; Plan p; GArgs g; int nz; hipStream_t s; };     // empty: M or N = 0, nothing to launch
+struct Prepared { bool empty = false; Plan p; GArgs g; int nz; hipStream_t s; float* parts; };   // parts: where split-K slabs go     // empty: M or N = 0, nothing to launch
 // the descriptor on its own; the order of the checks decides which code a doubly wrong descriptor gets.  empty: M or N = 0
 int check_desc(const vilco_gemm_desc* d, bool& empty) {
   if (!d || !d->C || (!d->A && !d->a_planes) || (!d->B && !d->b_planes)) return VILCO_ERR_BADARG;
@@ -1573,6 +1636,7 @@ int gemm_prepare(const vilco_gemm_desc* d, void* stream, Prepared& pr) {
   g.vec_out = (d->N % 4) == 0 && (d->ldc % 4) == 0 && (d->sCo % 4) == 0 && (d->sCi % 4) == 0 && vilco_aligned(d->C, 16) &&
               vilco_aligned(d->bias, 16) && vilco_aligned(d->preact, 16) && vilco_aligned(d->colscale, 16) &&
               vilco_aligned(d->residual, 16);
+  pr.parts = parts;
   g.c = p.ksplit > 1 ? parts : d->C;
   g.cfinal = d->C;
   g.amax_out = d->band == 1 ? nullptr : d->amax_out;
@@ -1742,11 +1806,101 @@ extern "C" int vilco_gemm(const vilco_gemm_desc* d, void* stream) {
   return vilco_launch_status();
 }
 
-// n (2..4) independent products of ONE shape, orientation and format in one launch (gemm_gl_group_kernel): operands packed
-// beforehand, precision 3, unbatched, untapped, no band; whatever does not qualify -- a split-K plan, unequal
-// shapes -- runs as n ordinary vilco_gemm calls, in order (same results either way: the kernel body is the same).
+// whether the members of a single-part group are ones gemm_pp_group_kernel can take: packed operands, precision 4 on the K2 loop,
+// unbatched, untapped, no band, the plain epilogue (what a weight gradient asks for), nothing forced by vilco_gemm_force
+static bool group_dw_member(const vilco_gemm_desc& d, const vilco_gemm_desc& d0) {
+  return d.a_planes && d.b_planes && d.precision == 4 && d.batch_outer == 1 && d.batch_inner == 1 && d.tap_operand == VILCO_TAP_NONE &&
+         d.band == 0 && d.M == d0.M && d.N == d0.N && d.K == d0.K && d.ldc == d0.ldc && d.a_kcontig == d0.a_kcontig &&
+         d.b_kcontig == d0.b_kcontig && d.M > 0 && d.N > 0 && d.alpha == 1.f && d.beta == 0.f && !d.bias && !d.preact &&
+         d.act == VILCO_ACT_NONE && !d.row_len && !d.row_mask && !d.colscale && !d.residual && d.drop_p == 0.f && !d.amax_out;
+}
+static bool group_dw_allowed() {
+  const Config& c = config();
+  return c.group && c.group_dw && c.km && c.k2 && c.force_bm == 0 && c.force_ks < 1;
+}
+
+// products per launch of a group of n: n itself up to GROUP_MAX, else the size of the larger of its (nearly) equal launches
+static inline int group_launch_size(int n) { const int l = (n + GROUP_MAX - 1) / GROUP_MAX; return l ? (n + l - 1) / l : 0; }
+
+// workspace of a member of a vilco_gemm_group call of n products: enough for the grouped plan (whichever launch of the group the
+// member lands in) and for the product's own launch
+extern "C" size_t vilco_gemm_group_workspace(const vilco_gemm_desc* d, int32_t n) {
+  if (!d || d->M <= 0 || d->N <= 0 || d->K < 0) return 512;
+  const Plan p = make_plan(d);
+  size_t need = workspace_need(p);
+  if (n >= 2 && d->precision == 4 && p.kern == Kern::PP_K2 && group_dw_allowed())
+    for (int m = group_launch_size(n); m >= 2 && m >= group_launch_size(n) - 1; --m) {
+      Tiling t;
+      Plan pg = p;
+      if (plan_group_dw(d, p, p.Kp, m, t)) { pg.part_bytes = t.part_bytes; need = std::max(need, workspace_need(pg)); }
+    }
+  return need;
+}
+
+// precision 4: descs[0 .. n) (n <= GROUP_MAX) as one gemm_pp_group_kernel launch; false: not taken (nothing launched)
+static bool gemm_group_dw(const vilco_gemm_desc* descs, int n, void* stream, int& rc) {
+  if (n < 2 || !group_dw_allowed()) return false;
+  std::vector<Prepared> prs(n);
+  Tiling t;
+  for (int i = 0; i < n; ++i) {
+    const vilco_gemm_desc& d = descs[i];
+    Prepared& pr = prs[i];      // (both operands pre-packed: preparing a member launches nothing)
+    if (!group_dw_member(d, descs[0]) || gemm_prepare(&d, stream, pr) != VILCO_OK || pr.p.kern != Kern::PP_K2) return false;
+    if (i == 0 && !plan_group_dw(&d, pr.p, pr.p.Kp, n, t)) return false;
+    Plan pg = pr.p;
+    pg.part_bytes = t.part_bytes;
+    if (d.workspace_bytes < workspace_need(pg) || pr.g.vec_out != prs[0].g.vec_out || pr.p.a.km != prs[0].p.a.km || pr.p.b.km != prs[0].p.b.km)
+      return false;
+    // the group's tiling replaces the member's own: grid, K range per split, slabs
+    static_cast<Tiling&>(pr.p) = t;
+    GArgs& g = pr.g;
+    g.ntiles = g.tiles_n * ((d.M + t.BM - 1) / t.BM);
+    g.ksplit = t.ksplit; g.kchunk = t.kchunk; g.split_stride = t.split_stride;
+    g.c = t.ksplit > 1 ? pr.parts : d.C;
+  }
+  GArgsG gg;
+  gg.g = prs[0].g;
+  gg.n = n;
+  for (int i = 0; i < n; ++i) gg.e[i] = GroupEnt{prs[i].g.a.p, prs[i].g.b.p, prs[i].g.c, prs[i].g.cfinal, prs[i].g.inv_a, prs[i].g.inv_b};
+  for (int i = n; i < GROUP_MAX; ++i) gg.e[i] = gg.e[0];
+  hipStream_t s = prs[0].s;
+  const Plan& p0 = prs[0].p;
+  {
+    ProfScope timed(s, ProfRec{{descs[0].M, descs[0].N, descs[0].K, n, t.BM, t.ksplit, 4, p0.a.km, p0.b.km, 0x100}});    // (batch field = group size)
+    const dim3 grid(gg.g.ntiles * n, t.ksplit, 1);
+    with_bm<256, 128>(t.BM, [&](auto R) {
+      constexpr int BM = decltype(R)::value;
+      with_km(p0.a.km, p0.b.km, [&](auto A, auto B) {
+        constexpr bool AKM = decltype(A)::value, BKM = decltype(B)::value;
+        launch_gemm<&gemm_pp_group_kernel<BM, AKM, BKM>>(pp_lds<BM, 2, AKM, BKM>(), grid, s, gg);
+      });
+    });
+  }
+  if (t.ksplit > 1)
+    for (int i = 0; i < n; ++i) splitk_finish(&descs[i], prs[i]);
+  rc = vilco_launch_status();
+  return true;
+}
+
+// n independent products of ONE shape, orientation and format in one launch, operands packed beforehand, unbatched, untapped, no
+// band: precision 3 (n <= 4, gemm_gl_group_kernel) or precision 4 with the plain epilogue (any n, gemm_pp_group_kernel, GROUP_MAX
+// products per launch).  Whatever does not qualify -- a split-K plan (precision 3), unequal shapes, a forced plan, a group the plan
+// prices above its members -- runs as n ordinary vilco_gemm calls, in order (same kernel body either way).
 extern "C" int vilco_gemm_group(const vilco_gemm_desc* descs, int32_t n, void* stream) {
-  if (!descs || n < 1 || n > 4) return VILCO_ERR_BADARG;
+  if (!descs || n < 1) return VILCO_ERR_BADARG;
+  if (descs[0].precision == 4) {
+    const int launches = (n + GROUP_MAX - 1) / GROUP_MAX;       // more than GROUP_MAX products: launches of (nearly) equal size
+    for (int l = 0, i0 = 0; l < launches; ++l) {
+      const int m = group_launch_size(n) - (l >= launches - (group_launch_size(n) * launches - n) ? 1 : 0);
+      int rc = VILCO_OK;
+      if (!gemm_group_dw(descs + i0, m, stream, rc))
+        for (int i = i0; i < i0 + m && rc == VILCO_OK; ++i) rc = vilco_gemm(&descs[i], stream);
+      if (rc != VILCO_OK) return rc;
+      i0 += m;
+    }
+    return VILCO_OK;
+  }
+  if (n > 4) return VILCO_ERR_BADARG;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   GArgsN gg;
   Plan p0;
@@ -1795,6 +1949,13 @@ extern "C" int vilco_gemm_set_skinny(int32_t on) {
   ++g_config_gen;
   return VILCO_OK;
 }
+
+extern "C" int vilco_gemm_set_group_dw(int32_t on) {
+  config().group_dw = on != 0;
+  ++g_config_gen;
+  return VILCO_OK;
+}
+extern "C" int32_t vilco_gemm_group_dw(void) { return config().group_dw ? 1 : 0; }
 
 extern "C" int vilco_gemm_force(int32_t bm, int32_t ks) {
   if (bm < 0 || ks < 0) return VILCO_ERR_BADARG;

@@ -207,6 +207,7 @@ def _defer_flush(final=True):
     """issue what is recorded.  final: the end-of-backward callback (or a reset) -- also forgets which parameters this
     backward has already produced a gradient for"""
     st = _defer
+    _dw_group_flush()
     if _lib.load().vilco_defer_pending():
         if torch.cuda.is_current_stream_capturing():
             # recorded items may have been produced on a forked side stream (VILCO_GRAPH_STREAMS "dw": split-K slabs written
@@ -386,11 +387,12 @@ def gemm(A, B, Cc, M, N, K, a_kc, b_kc, lda, ldb, ldc, batch=(1, 1), sA=(0, 0), 
          sC=(0, 0), offA=0, offB=0, offC=0, tap=TAP_NONE, tapC=0, tapT=0, alpha=1.0, beta=0.0,
          bias=None, preact=None, act=ACT_NONE, row_len=None, rowT=0, colscale=None, residual=None,
          res_masked=0, precision=None, a_planes=None, b_planes=None, band=0, bandT=0, drop=(0.0, 0), want_amax=False,
-         a_amax=None, b_amax=None, planes_seq=(False, False), row_mask=None, _into=None):
+         a_amax=None, b_amax=None, planes_seq=(False, False), row_mask=None, _into=None, _group_n=0):
     """Raw launch of vilco_gemm; A/B/Cc are fp32 CUDA tensors, offsets in elements.  a_planes / b_planes: operands
     already packed by `pack` (the fp32 tensor may then be None).  want_amax: the call writes ALL of Cc, which goes on
     into another product -- the kernel leaves max|C| partials and Cc is tagged with them (`_tag_amax`).
-    _into: (internal, gemm_group) a GemmDesc to fill instead of launching; returns what must stay alive + the amax tag."""
+    _into: (internal, gemm_group) a GemmDesc to fill instead of launching; returns what must stay alive + the amax tag;
+    _group_n: ... as a member of a group of that many products (sizes the workspace)."""
     lib = _lib.load()
     d = GemmDesc() if _into is None else _into
     d.A = None if A is None else A.data_ptr() + 4 * offA
@@ -419,7 +421,8 @@ def gemm(A, B, Cc, M, N, K, a_kc, b_kc, lda, ldb, ldc, batch=(1, 1), sA=(0, 0), 
     d.colscale = _p(colscale)
     d.residual = None if residual is None else residual.data_ptr() + 4 * offC
     d.res_masked = int(res_masked)
-    nbytes = lib.vilco_gemm_workspace(C.byref(d))      # bf16 operand planes + split-K partials
+    # bf16 operand planes + split-K partials
+    nbytes = lib.vilco_gemm_group_workspace(C.byref(d), int(_group_n)) if _group_n else lib.vilco_gemm_workspace(C.byref(d))
     ws = torch.empty(nbytes, dtype=torch.uint8, device=Cc.device)
     if _defer["on"]:
         _defer["keep"].extend((ws, Cc.detach()))    # split-K slabs of a recorded weight-gradient product, and (an alias of) its output
@@ -442,15 +445,66 @@ def gemm(A, B, Cc, M, N, K, a_kc, b_kc, lda, ldb, ldc, batch=(1, 1), sA=(0, 0), 
 
 
 def gemm_group(calls):
-    """calls: [(args, kwargs) of `gemm`, ...] (2..4 independent products of one shape with packed operands) as ONE launch
-    (vilco_gemm_group; whatever does not qualify runs one by one inside the library -- same results)."""
+    """calls: [(args, kwargs) of `gemm`, ...]: independent products of one shape with packed operands (2..4 of the ambient
+    two-part format, or any number of single-part ones, precision=4) as ONE launch (vilco_gemm_group; whatever does not
+    qualify runs one by one inside the library -- same results)."""
     lib = _lib.load()
     arr = (GemmDesc * len(calls))()
-    keep = [gemm(*a, _into=arr[i], **k) for i, (a, k) in enumerate(calls)]
+    keep = [gemm(*a, _into=arr[i], _group_n=len(calls), **k) for i, (a, k) in enumerate(calls)]
     _lib.check(lib.vilco_gemm_group(arr, len(calls), _stream()))
     for ws, Cc, parts, n in keep:
         if parts is not None:
             _tag_amax(Cc, parts, n)
+
+
+# ---- the single-part weight gradients of a backward, grouped.  dW = dZ^T X of one 1024 x 1024 layer is 64 tiles: alone it is split
+# four ways over K to fill the chip, writes four fp32 slabs and needs a pass that sums them.  Nothing in backward reads a weight
+# gradient (what `_Deferring` already relies on), and both operand images are complete when backward reaches the layer -- so a
+# product that `_Deferring` would record a slab sum for is itself recorded here, keyed by shape and orientation, and the
+# end-of-backward flush (`_defer_flush`: also every mid-backward flush and, with a staged data-parallel replay, every stage's)
+# issues ONE grouped launch per key (vilco_gemm_group, precision 4: no split where the group fills the chip).  The operand planes
+# are held until then (2 x 9.4 MB per product at 1024 x 1024 x 4608); the fp32 tensors are not.  A key with one member is a plain
+# launch.  vilco_gemm_set_group_dw(0) / VILCO_GEMM_GROUP_DW=0: every product where backward meets it.
+_dw_pending = {}
+
+
+def _dw_gemm(dfr, A, B, Cc, M, N, K, a_kc, b_kc, lda, ldb, ldc, precision=None, a_planes=None, b_planes=None):
+    """a Linear layer's weight-gradient product, inside `with _Deferring(w) as dfr`: launched, or -- single-part, operands
+    packed, its gradient one that may stay unfinished until backward ends -- recorded for the grouped launch"""
+    if not (dfr.on and precision == 4 and a_planes is not None and b_planes is not None and _lib.load().vilco_gemm_group_dw()):
+        return gemm(A, B, Cc, M, N, K, a_kc, b_kc, lda, ldb, ldc, precision=precision, a_planes=a_planes, b_planes=b_planes)
+    key = (int(M), int(N), int(K), int(a_kc), int(b_kc), int(ldc), Cc.data_ptr() % 16 == 0)
+    _dw_pending.setdefault(key, []).append(((None, None, Cc.detach(), M, N, K, a_kc, b_kc, lda, ldb, ldc),
+                                            dict(precision=4, a_planes=a_planes, b_planes=b_planes)))
+
+
+def _dw_group_flush():
+    """issue what `_dw_gemm` recorded: one grouped launch per key, on the "dw" side stream where that is forked"""
+    if not _dw_pending:
+        return
+    items = list(_dw_pending.values())
+    _dw_pending.clear()
+    lib = _lib.load()
+    fork = fork_enabled("dw")
+    if fork:
+        cur, side = torch.cuda.current_stream(), side_stream("dw")
+        side.wait_stream(cur)
+        ctx = torch.cuda.stream(side)
+        ctx.__enter__()
+    lib.vilco_defer_set(1)            # a small group still splits K: its slab sums join the deferred ones, and
+    _defer["on"] = True               # every workspace is held until those have been issued
+    try:
+        for calls in items:
+            if len(calls) == 1:
+                gemm(*calls[0][0], **calls[0][1])
+            else:
+                gemm_group(calls)
+    finally:
+        lib.vilco_defer_set(0)
+        _defer["on"] = False
+        if fork:
+            ctx.__exit__(None, None, None)
+            cur.wait_stream(side)
 
 
 # ---- what a producer already knows about its output.  The fp16 x2 planes need max|x| of the whole tensor before anything can be
@@ -903,9 +957,9 @@ class _Linear(torch.autograd.Function):
             dx = torch.empty_like(x)
             gemm(dz, w, dx, M, K, N, 1, 0, N, K, K, precision=prec, a_planes=pz, b_planes=pw, want_amax=True)   # dX = dZ W     (NN)
         if ctx.needs_input_grad[1]:
-            with _DwFork(w, M), _Deferring(w):       # (a split-K slab sum of this product may finish with the deferred ones)
+            with _DwFork(w, M), _Deferring(w) as dfr:     # (may finish, or run as a whole, with the deferred ones: _dw_gemm)
                 dw = _grad_out(w)
-                gemm(dz, x, dw, N, K, M, 0, 0, N, K, K, precision=_dw_prec(prec, M), a_planes=pz, b_planes=px)   # dW = dZ^T X   (TN)
+                _dw_gemm(dfr, dz, x, dw, N, K, M, 0, 0, N, K, K, precision=_dw_prec(prec, M), a_planes=pz, b_planes=px)   # dW = dZ^T X   (TN)
         return dx, dw, db, None, None, None, None, None, None
 
 
@@ -953,9 +1007,9 @@ class _LinearGroup(torch.autograd.Function):
         dws = []
         for i, (dy, x, w, pz, px) in enumerate(zip(dys, xs, ws, pzs, pxs)):
             if ctx.needs_input_grad[1 + n + i]:
-                with _DwFork(w, M), _Deferring(w):
+                with _DwFork(w, M), _Deferring(w) as dfr:
                     dw = _grad_out(w)
-                    gemm(dy, x, dw, N, K, M, 0, 0, N, K, K, precision=_dw_prec(ctx.prec, M), a_planes=pz, b_planes=px)   # dW = dY^T X
+                    _dw_gemm(dfr, dy, x, dw, N, K, M, 0, 0, N, K, K, precision=_dw_prec(ctx.prec, M), a_planes=pz, b_planes=px)   # dW = dY^T X
                 dws.append(dw)
             else:
                 dws.append(None)
@@ -1026,9 +1080,9 @@ class _LinearKN(torch.autograd.Function):
             dx = torch.empty_like(x)
             gemm(dy, w, dx, M, K, N, 1, 1, N, N, K, precision=prec, a_planes=pz, b_planes=pw)   # dX = dY W^T   (NT)
         if ctx.needs_input_grad[1]:
-            with _DwFork(w, M), _Deferring(w):
+            with _DwFork(w, M), _Deferring(w) as dfr:
                 dw = _grad_out(w)
-                gemm(x, dy, dw, K, N, M, 0, 0, K, N, N, precision=_dw_prec(prec, M), a_planes=px, b_planes=pz)   # dW = X^T dY   (TN)
+                _dw_gemm(dfr, x, dy, dw, K, N, M, 0, 0, K, N, N, precision=_dw_prec(prec, M), a_planes=px, b_planes=pz)   # dW = X^T dY   (TN)
         if ctx.has_bias and ctx.needs_input_grad[2]:
             db = colsum(dy.view(M, N)).view(ctx.bshape)
         return dx, dw, db

@@ -18,6 +18,7 @@ Switch = namedtuple("Switch", "env default readers key meaning")
 KEYED = "keyed"                 # an `ops` attribute that decides which kernels a step records: part of ops.arithmetic_key()
 VIA_SET = "ops.set_precision moves ops._precision, which is keyed"
 ONCE = "read once per process"
+GEN = "read once per process; its setter bumps vilco_gemm_config_gen(), which is part of ops.arithmetic_key()"
 BUILT = "read at construction and fixed in the object"
 INFERENCE = "inference only"
 HOST = "host scheduling only"
@@ -75,6 +76,7 @@ TABLE = (
     Switch("VILCO_GEMM_SUB192", "1", ("gemm.hip",), ONCE, "the two sub-round 192-row plans"),
     Switch("VILCO_GEMM_DW_TALL", "1", ("gemm.hip",), ONCE, "single-part weight-gradient products planned on 192- / 256-row tiles"),
     Switch("VILCO_GEMM_GROUP", "1", ("gemm.hip",), ONCE, "grouped GEMM launches"),
+    Switch("VILCO_GEMM_GROUP_DW", "1", ("gemm.hip",), GEN, "initial vilco_gemm_set_group_dw: a backward's equal single-part weight gradients as one launch"),
     Switch("VILCO_GEMM_SKINNY", "1", ("gemm.hip",), ONCE, "initial vilco_gemm_set_skinny: skinny NT products on small workgroups"),
     Switch("VILCO_GEMM_SKINNY_M", "640", ("gemm.hip",), ONCE, "largest M of a skinny product"),
     Switch("VILCO_GEMM_SKINNY_BM16", "640", ("gemm.hip",), ONCE, "largest M on 16-row workgroups"),
