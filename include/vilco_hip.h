@@ -687,6 +687,45 @@ int vilco_cl_distill_fwd(const vilco_distill_desc* d, float* out, void* workspac
 int vilco_cl_distill_bwd(const vilco_distill_desc* d, const float* g_out, float* d_logits, void* stream);
 
 /* ------------------------------------------------------------------------------------------ */
+/* Dark Experience Replay (Buzzega et al., "Dark Experience for General Continual Learning", NeurIPS 2020; the reference   */
+/* has no logit replay): every memory clip of the batch against the logits it produced when it entered the memory           */
+/* (csrc/der.hip).  x = the concatenated head output [B][R][C] (level l in rows level_row[l] .. + level_T[l]); z_b = the    */
+/* record of batch row b, fp32 [sum T_l][n_b], levels end to end without separators, n_b <= C (the head has grown since).   */
+/*   der_tab   = DEVICE int64 [B][2]: der_tab[b][0] = address of z_b, or 0: row b has no record; der_tab[b][1] = n_b, the     */
+/*               record's class count AND row stride.  A row with n_b outside [1, C] is skipped, not trusted.               */
+/*   level_len = DEVICE int32 [B][L]: V_bl, the valid length of level l of row b (what vilco_loss_desc.level_len holds).     */
+/*   S = sum_{b: rec} sum_l sum_{t < V_bl} sum_{y < n_b} (x[b, level_row[l] + t, y] - z_b[off_l + t, y])^2                  */
+/*       (every term in fp32: one rounding for the difference, one for the square; the sum in fp64, in a fixed order)        */
+/*   N = sum_{b: rec} n_b sum_l V_bl                                     (int64, formed on the device)                       */
+/*   out  = (float)(alpha * S / N)   if N > 0, else 0                                                                        */
+/*   c    = (float)(2.0 * alpha * g_out / N)                             (formed in double, rounded once)                    */
+/*   d_logits[b, level_row[l] + t, y] = fl(fl(x - z) * c)   on exactly the compared elements                                */
+/* level_row / level_T are HOST arrays (validated before anything is enqueued); level_dev is their device copy, int32      */
+/* [2][L], which the kernels walk.  der_tab and level_len are read when the kernels RUN, so a captured launch follows a      */
+/* table rewritten between replays; the records it names must stay where they are for as long as a graph may replay.        */
+/* fwd: two launches; out = device float[1]; N is left in the workspace (vilco_der_workspace(B * sum T_l) bytes; the int64  */
+/* at its first 256-byte boundary), where bwd reads it: hand bwd the SAME workspace, untouched in between.                   */
+/* bwd: one launch; g_out = device scalar; the compared elements of d_logits are ASSIGNED and nothing else is written (the  */
+/* caller supplies the zero-filled tensor); N == 0 writes nothing.  No atomics: the same bits on every call.                 */
+/* A null pointer, L <= 0, B <= 0, a level outside R: VILCO_ERR_BADARG; a short workspace: VILCO_ERR_WORKSPACE -- both       */
+/* before anything is enqueued.                                                                                            */
+/* ------------------------------------------------------------------------------------------ */
+typedef struct vilco_der_desc {
+  const float* logits;        /* [B][R][C] */
+  const int32_t* level_row;   /* host [L]: first row of every level inside R */
+  const int32_t* level_T;     /* host [L]: rows of every level */
+  const int32_t* level_dev;   /* device [2][L]: level_row, level_T */
+  const int32_t* level_len;   /* device [B][L]: valid lengths */
+  const int64_t* der_tab;     /* device [B][2]: record address or 0, n_b */
+  int32_t B, R, C, L;
+  double alpha;               /* der_alpha */
+} vilco_der_desc;
+size_t vilco_der_workspace(int64_t n_pairs);            /* n_pairs = B * sum T_l */
+int vilco_der_fwd(const vilco_der_desc* d, float* out, void* workspace, size_t workspace_bytes, void* stream);
+int vilco_der_bwd(const vilco_der_desc* d, const float* g_out, float* d_logits, const void* workspace,
+                  size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------ */
 /* BiC bias correction of the classification head's output (MQ/libs/modeling/meta_archs.py:26-35: BiasLayer,           */
 /* alpha * x + beta; :821-836: one layer per task over its slice of the class columns, the slices concatenated again)    */
 /* as one launch over the concatenated head output (csrc/bic.hip):                                                       */

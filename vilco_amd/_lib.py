@@ -140,6 +140,12 @@ class DistillDesc(C.Structure):
                 ("scale", f32)]
 
 
+class DerDesc(C.Structure):
+    _cname_ = "vilco_der_desc"
+    _fields_ = [("logits", c_fp), ("level_row", c_fp), ("level_T", c_fp), ("level_dev", c_fp), ("level_len", c_fp),
+                ("der_tab", c_fp), ("B", i32), ("R", i32), ("C", i32), ("L", i32), ("alpha", C.c_double)]
+
+
 class BicCorrectDesc(C.Structure):
     _cname_ = "vilco_bic_correct_desc"
     _fields_ = [("x", c_fp), ("y", c_fp), ("splits", c_fp), ("table", c_fp), ("rows", i64), ("C", i32), ("S", i32),
@@ -240,6 +246,9 @@ SIGNATURES = {
     "vilco_cl_distill_workspace": (sz, [i64]),
     "vilco_cl_distill_fwd": (C.c_int, [C.POINTER(DistillDesc), c_fp, c_fp, sz, c_fp]),
     "vilco_cl_distill_bwd": (C.c_int, [C.POINTER(DistillDesc), c_fp, c_fp, c_fp]),
+    "vilco_der_workspace": (sz, [i64]),
+    "vilco_der_fwd": (C.c_int, [C.POINTER(DerDesc), c_fp, c_fp, sz, c_fp]),
+    "vilco_der_bwd": (C.c_int, [C.POINTER(DerDesc), c_fp, c_fp, c_fp, sz, c_fp]),
     "vilco_cl_penalty": (C.c_int, [C.POINTER(ChunkTable), f32, i32, c_fp, c_fp, c_fp]),
     "vilco_cl_accumulate": (C.c_int, [C.POINTER(ChunkTable), i32, f32, f32, c_fp]),
     "vilco_agem_project": (C.c_int, [C.POINTER(ChunkTable), c_fp, c_fp, c_fp]),

@@ -121,6 +121,13 @@ DEFAULTS = {'init_rand_seed': 765421321,
          'schedule_gamma': 0.1}}
 
 
+# Defaults of the keys this project adds to the reference's surface.  They are merged under every config like DEFAULTS, but kept
+# apart from it: DEFAULTS stays the reference's table, key for key (tests/test_cabi_cpu.py holds it to the golden copy).
+#   cl_cfg.der_alpha: weight of the logit-replay term of cl_cfg.name 'der' (cl_methods/der.py).  0.1 is the starting value of the
+#   DER paper's grids; a hyper-parameter, not tuned here.
+EXTRA_DEFAULTS = {'cl_cfg': {'der_alpha': 0.1}}
+
+
 def _merge(src, dst):
     """fill `dst` with whatever `src` has and `dst` lacks (recursively for dict values)"""
     for key, val in src.items():
@@ -147,6 +154,7 @@ def load_config(config_file, defaults=DEFAULTS):
     with open(config_file, "r") as fd:
         config = yaml.load(fd, Loader=yaml.FullLoader)
     _merge(defaults, config)
+    _merge(copy.deepcopy(EXTRA_DEFAULTS), config)
     return _update_config(config)
 
 
@@ -154,4 +162,5 @@ def make_config(**overrides):
     """DEFAULTS (deep-copied) under a dict of overrides -- `load_config` without the YAML file."""
     cfg = copy.deepcopy(overrides)
     _merge(copy.deepcopy(DEFAULTS), cfg)
+    _merge(copy.deepcopy(EXTRA_DEFAULTS), cfg)
     return _update_config(cfg)

@@ -25,7 +25,7 @@ Intelligence -- the path integrals `omega`, which the captured update advances o
 addresses (vilco_optim_desc.si_ptrs; table and omegas are kept alive by the optimizer).
 
 What is captured is what ran: graphs are keyed by the input shapes, task id, the identity / requires_grad of every
-parameter and BiC's split table with the addresses of its layers, and dropped when parameters were written from outside (load_state_dict, an eager optimizer step) or Synaptic Intelligence was attached / re-attached to the optimizer (a new task's omegas) -- cached
+parameter, the continual-learning method and BiC's split table with the addresses of its layers, and dropped when parameters were written from outside (load_state_dict, an eager optimizer step) or Synaptic Intelligence was attached / re-attached to the optimizer (a new task's omegas) -- cached
 operand planes and max|w| partials would be stale otherwise.  Steps the device half cannot run alone (distillation
 against host-side NumPy targets or in a batch without a cached clip, a BiC model whose split table the correction kernel
 does not take, narration SSL with its fused path switched off by VILCO_FUSED_SSL=0) fall back to the eager path.
@@ -150,7 +150,7 @@ class GraphedStep:
         inp = self._prepare(video_list, prev_out_cls_logits)
         if not (self.enabled and model.training and model.capturable(inp, task_id, prev_out_cls_logits)):
             return self._eager(inp, video_list, task_id, prev_out_cls_logits)
-        key = (inp.signature(), int(task_id), self._param_sig(), int(model.n_known), ops.arithmetic_key(), self._bic_sig())
+        key = self._key(inp, task_id)
         ent = self._graphs.get(key)
         if ent is None:
             ent = self._graphs[key] = {'seen': 0}
@@ -178,7 +178,17 @@ class GraphedStep:
         if tgt is not None:
             inp.dist_tgt, inp.dist_lens = tgt
             inp.dist_kind = self.model.cl_name       # whom the buffer was attached for (PtTransformer.capturable)
+        if getattr(self.model, "cl_name", None) == 'der':
+            # every iteration: the captured term (csrc/der.hip) reads its records through this table, which names the records of
+            # THIS batch's memory clips (all zeros: none) -- the bank keeps the buffers where they are
+            from .cl_methods import der
+            inp.der_tab = der.step_table(self.model, video_list)
         return inp
+
+    def _key(self, inp, task_id):
+        model = self.model
+        return (inp.signature(), int(task_id), self._param_sig(), int(model.n_known), ops.arithmetic_key(), self._bic_sig(),
+                getattr(model, "cl_name", None))
 
     def try_capture(self, video_list, task_id=0, prev_out_cls_logits=None):
         """Capture the graphs of this batch's signature NOW, without replaying them (no collective is issued: a staged capture
@@ -191,7 +201,7 @@ class GraphedStep:
             return False
         if self.reducer is not None and self.reducer.enabled and self.reducer.planned() is None:
             return False                         # (the bucket plan comes from an eager finish(): run an eager step first)
-        key = (inp.signature(), int(task_id), self._param_sig(), int(model.n_known), ops.arithmetic_key(), self._bic_sig())
+        key = self._key(inp, task_id)
         ent = self._graphs.get(key)
         if ent is None:
             ent = self._graphs[key] = {'seen': 0}

@@ -295,15 +295,17 @@ class StepInputs:
     narr_cf [B,Cn,n_pad] tokens, narr_lens int32 [B] token counts, narr_mask float [B] (the clip has a narration); narr =
     the unfused path's narration tuple or None; dist_tgt float [sum T_l, ldt] = the iCaRL / BiC distillation targets of the
     step (one cached clip's levels end to end, PtTransformer.distill_target) with dist_lens = (T_l, ...), or None; dist_kind =
-    the method ('icarl' / 'bic') the caller that replays the step attached dist_tgt for (graph.GraphedStep._prepare), or None"""
+    the method ('icarl' / 'bic') the caller that replays the step attached dist_tgt for (graph.GraphedStep._prepare), or None;
+    der_tab int64 [B, 2] = (address of the row's DER record or 0, its class count) of a cl_name 'der' step
+    (cl_methods.der.step_table), or None: the step then builds it from the clip list"""
     __slots__ = ("feats_cf", "lens", "T", "text_cf", "text_lens", "narr", "gt", "narr_cf", "narr_lens", "narr_mask",
-                 "dist_tgt", "dist_lens", "dist_kind")
+                 "dist_tgt", "dist_lens", "dist_kind", "der_tab")
     HOST = ("T", "narr", "dist_lens", "dist_kind")          # not device buffers: a captured step takes them over as they are
 
     def tensors(self):
         """(name, tensor) of every device buffer a replayed step reads"""
         return [(k, getattr(self, k)) for k in ("feats_cf", "lens", "text_cf", "text_lens", "gt", "narr_cf", "narr_lens",
-                                                "narr_mask", "dist_tgt") if getattr(self, k, None) is not None]
+                                                "narr_mask", "dist_tgt", "der_tab") if getattr(self, k, None) is not None]
 
     def signature(self):
         return (tuple((k, tuple(t.shape)) for k, t in self.tensors()) + (("narr", self.narr is not None),) +
@@ -406,6 +408,8 @@ class PtTransformer(nn.Module):
         self.list_bias_layers, self.list_splits = [], []
         self.bic_raw_logits = False          # True while cl_methods/bic.py caches the logits BEFORE the bias correction
         self.cl_name = cl_cfg['name']
+        self.der_alpha = float(cl_cfg.get('der_alpha', 0.1))      # cl_name 'der' (cl_methods/der.py)
+        self.der_bank = None                 # cl_methods.der.DERBank: the memory clips' insertion-time logits (train_cl.run_episodes)
 
         self.prompt_pool = cl_cfg['prompt_pool']
         self.use_prompt_mask = True
@@ -595,6 +599,7 @@ class PtTransformer(nn.Module):
         inp.feats_cf, inp.lens, inp.T = self._batch_cf(video_list, is_training)
         inp.text_cf = inp.text_lens = inp.narr = inp.narr_cf = inp.narr_lens = inp.narr_mask = None
         inp.dist_tgt = inp.dist_lens = inp.dist_kind = None        # filled by the caller that replays the step (graph.GraphedStep)
+        inp.der_tab = None
         if self.use_cross_modal:
             inp.text_cf, inp.text_lens, narr = self._query_batch_cf(video_list, narr_pad=narr_pad)
             if isinstance(narr, dict):
@@ -664,6 +669,10 @@ class PtTransformer(nn.Module):
             dev = self.device
             if any(p.device != dev for l in self.list_bias_layers for p in (l.alpha, l.beta)):
                 return False
+        elif self.n_known > 0 and self.cl_name == 'der':
+            # the replayed term reads its records through the table in `inp.der_tab` (GraphedStep._prepare fills the slot)
+            if getattr(inp, "der_tab", None) is None or prev_out_cls_logits:
+                return False
         elif prev_out_cls_logits:
             return False
         if hasattr(self, 'prompt') and not (0 <= task_id and (task_id + 1) * self.prompt.top_k <= self.prompt.pool_size):
@@ -681,6 +690,8 @@ class PtTransformer(nn.Module):
         narr = inp.narr
         # a step prepared for replay carries its distillation targets as one buffer; it wins over the lists it was made of
         self._dist_tgt = None if getattr(inp, "dist_tgt", None) is None else (inp.dist_tgt, inp.dist_lens)
+        # a 'der' step: the table the caller attached, or the clips to build it from (_der_loss)
+        self._der_step = (getattr(inp, "der_tab", None), video_list)
         if self.use_cross_modal:
             text_tm, text_lens = ops.transpose(inp.text_cf), inp.text_lens
 
@@ -942,7 +953,8 @@ class PtTransformer(nn.Module):
         level_T = [int(p.shape[0]) for p in points]
         level_row = cat.off if cat is not None else [sum(level_T[:i]) for i in range(len(level_T))]
         return self._cl_terms({'cls_loss': cls_loss, 'reg_loss': reg_loss, 'al_loss': al_loss}, final_loss,
-                              out_cls_logits, prev_out_cls_logits, reduce_sim, cat_logits=(logits, level_row))
+                              out_cls_logits, prev_out_cls_logits, reduce_sim, cat_logits=(logits, level_row),
+                              level_len=level_len)
 
     # ------------------------------------------------------------------ losses
     @property
@@ -1027,7 +1039,9 @@ class PtTransformer(nn.Module):
         level_T = [int(x.shape[1]) for x in out_cls_logits]
         return self._cl_terms({'cls_loss': cls_loss, 'reg_loss': reg_loss, 'al_loss': al_loss}, final_loss, out_cls_logits,
                               prev_out_cls_logits, reduce_sim,
-                              cat_logits=(logits_all, [sum(level_T[:i]) for i in range(len(level_T))]))
+                              cat_logits=(logits_all, [sum(level_T[:i]) for i in range(len(level_T))]),
+                              level_len=torch.stack([m.sum(1) for m in fpn_masks], dim=1).to(torch.int32).contiguous()
+                              if self.cl_name == 'der' else None)
 
     @staticmethod
     def _icarl_levels(prev_out_cls_logits, len_f):
@@ -1077,12 +1091,42 @@ class PtTransformer(nn.Module):
         return ops.cl_distill(logits, level_row, level_T, targets, self.n_known,
                               ops.DISTILL_BIC if bic else ops.DISTILL_ICARL, 0.01 * self.n_known / n_classes)
 
-    def _cl_terms(self, out, final_loss, out_cls_logits, prev_out_cls_logits, reduce_sim, cat_logits=None):
+    def _der_levels(self):
+        """the level lengths of a training step (every batch is padded to max_seq_len): what a usable DER record was made with"""
+        return tuple(self.max_seq_len // s for s in self.fpn_strides)
+
+    def _der_loss(self, out_cls_logits, cat_logits, level_len):
+        """cl_name 'der' (ours; cl_methods/der.py): der_alpha * mean (x - z)^2 over the memory clips of the batch against their
+        insertion-time logits.  On the device ONE ops.der_replay call (csrc/der.hip) over the concatenated head output, the
+        records named by a device table; a CPU model evaluates the same term in tensor ops."""
+        from ..cl_methods import der
+        (tab, video_list), self._der_step = getattr(self, "_der_step", None) or (None, None), None
+        logits, level_row = cat_logits
+        level_T = tuple(int(x.shape[1]) for x in out_cls_logits)
+        if logits.is_cuda:
+            if tab is None:
+                if video_list is None:
+                    raise ValueError("a cl_name 'der' step needs StepInputs.der_tab or the list of its clips")
+                tab = der.step_table(self, video_list, level_T)
+            return ops.der_replay(logits, level_row, level_T, level_len, tab, self.der_alpha)
+        if video_list is None:
+            raise ValueError("a cl_name 'der' step on a CPU model needs the list of its clips")
+        vids, bank = der.labelled(video_list), self.der_bank
+        rows = bank.rows_for(vids, [der.clip_len(v) for v in vids], level_T) if bank is not None else [(0, 0)] * len(vids)
+        records = [bank.get(der.clip_key(v))[0] if r[0] else None for v, r in zip(vids, rows)]
+        return der.der_term(logits, level_row, level_T, level_len, records, self.der_alpha)[0]
+
+    def _cl_terms(self, out, final_loss, out_cls_logits, prev_out_cls_logits, reduce_sim, cat_logits=None, level_len=None):
         """continual-learning terms on top of the detection loss (meta_archs.py:1478-1519).  On the device the iCaRL / BiC
         distillation term is one fused op (cat_logits = the concatenated logits and every level's first row in them); a
-        CPU model walks the reference's loops."""
+        CPU model walks the reference's loops.  level_len: int32 [B, L] valid lengths, read by the 'der' term only."""
         if self.n_known > 0 and self.cl_name == 'l2p':
             final_loss = final_loss - 0.1 * reduce_sim
+        if self.n_known > 0 and self.cl_name == 'der':
+            der_loss = self._der_loss(out_cls_logits, cat_logits, level_len)
+            out['der_loss'] = der_loss
+            out['final_loss'] = final_loss + der_loss
+            return out
         if self.n_known > 0 and self.cl_name in ('bic', 'icarl') and out_cls_logits[0].is_cuda:
             dist_loss = self._device_distill(out_cls_logits, prev_out_cls_logits, cat_logits)
             out['dist_loss'] = dist_loss

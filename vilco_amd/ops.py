@@ -2078,6 +2078,72 @@ def cl_distill(logits, level_row, level_T, targets, n_known, mode, scale, clip=0
                             (int(n_known), int(mode), float(scale), int(clip)))
 
 
+# ---------------------------------------------------------------------------------------- Dark Experience Replay
+def der_pairs_per_round():
+    """(batch row, pyramid row) pairs the capped grid of csrc/der.hip covers in one round (4 waves per block); beyond it
+    the waves walk further pairs.  Read off vilco_der_workspace, which holds one partial per block."""
+    lib = _lib.load()
+    return 4 * ((lib.vilco_der_workspace(1 << 40) - 256) // 8 - 1)
+
+
+class _DerReplay(torch.autograd.Function):
+    """the logit-replay term of DER / DER++ over the concatenated head output: two launches forward, one backward
+    (vilco_der_fwd / _bwd); the gradient is non-zero on the compared elements only"""
+
+    @staticmethod
+    def forward(ctx, logits, tab, level_len, der_tab, alpha):
+        _chk(logits)
+        lib = _lib.load()
+        d = _lib.DerDesc()
+        d.logits, d.level_len, d.der_tab = logits.data_ptr(), level_len.data_ptr(), der_tab.data_ptr()
+        d.level_row, d.level_T, d.level_dev = C.addressof(tab[0]), C.addressof(tab[1]), tab[2].data_ptr()
+        d.B, d.R, d.C, d.L = logits.shape[0], logits.shape[1], logits.shape[2], len(tab[0])
+        d.alpha = float(alpha)
+        nws = lib.vilco_der_workspace(logits.shape[0] * sum(tab[1]))
+        # the workspace is this call's own: backward reads N from it (not ops._ws, whose buffers deferred stages may share)
+        ws = torch.empty(int(nws), dtype=torch.uint8, device=logits.device)
+        out = torch.empty(1, dtype=torch.float32, device=logits.device)
+        _lib.check(lib.vilco_der_fwd(C.byref(d), out.data_ptr(), ws.data_ptr(), nws, _stream()))
+        ctx.desc, ctx.tab, ctx.nws = d, tab, nws
+        ctx.save_for_backward(logits, level_len, der_tab, ws)
+        off = (-ws.data_ptr()) % 256
+        count = ws[off:off + 8].view(torch.int64)[0]
+        ctx.mark_non_differentiable(count)
+        return out[0], count
+
+    @staticmethod
+    def backward(ctx, g, _g_count):
+        logits, level_len, der_tab, ws = ctx.saved_tensors
+        g = g.contiguous().float()
+        dl = torch.zeros_like(logits)          # the kernel assigns its footprint; autograd adds this to mq_loss' gradient
+        _lib.check(_lib.load().vilco_der_bwd(C.byref(ctx.desc), g.data_ptr(), dl.data_ptr(), ws.data_ptr(), ctx.nws, _stream()))
+        return dl, None, None, None, None
+
+
+def der_replay(logits, level_row, level_T, valid_lens, der_tab, alpha, return_count=False):
+    """Dark Experience Replay's term (include/vilco_hip.h: vilco_der_desc) -> scalar alpha * S / N, 0 when nothing is compared.
+    logits: [B, R, C] with level l in rows level_row[l] .. level_row[l] + level_T[l]; valid_lens: device int32 [B, L], the
+    valid length of every level of every row (what ops.mq_loss is given); der_tab: device int64 [B, 2] = (address of the row's
+    record [sum T_l, n_b] or 0, n_b) -- cl_methods.der.DERBank.table_for builds it and keeps the records alive.
+    return_count: also the device int64 scalar N (compared elements)."""
+    for t in (logits, valid_lens, der_tab):
+        if not (torch.is_tensor(t) and t.is_cuda):
+            raise RuntimeError("vilco_amd ops run on the HIP device only (got a %s tensor); there is no CPU fallback"
+                               % (t.device if torch.is_tensor(t) else type(t).__name__))
+    if logits.dim() != 3:
+        raise ValueError("der_replay: logits must be [B, R, C]")
+    tab = _distill_levels(level_row, level_T, logits.device)
+    B, L = logits.shape[0], len(tab[0])
+    if valid_lens.dtype != torch.int32 or tuple(valid_lens.shape) != (B, L):
+        raise ValueError("der_replay: valid_lens must be int32 [%d, %d], got %s %s" % (B, L, valid_lens.dtype, tuple(valid_lens.shape)))
+    if der_tab.dtype != torch.int64 or tuple(der_tab.shape) != (B, 2):
+        raise ValueError("der_replay: der_tab must be int64 [%d, 2], got %s %s" % (B, der_tab.dtype, tuple(der_tab.shape)))
+    if valid_lens.device != logits.device or der_tab.device != logits.device:
+        raise RuntimeError("der_replay: all tensors must live on one device")
+    loss, count = _DerReplay.apply(logits.contiguous(), tab, valid_lens.contiguous(), der_tab.contiguous(), float(alpha))
+    return (loss, count) if return_count else loss
+
+
 # ---------------------------------------------------------------------------------------- BiC bias correction
 _bic_tabs = {}
 

@@ -13,6 +13,7 @@ reference driver MQ/train_cl.py:206-389 (+ load_best_checkpoint :31-40), written
           and scheduler                                             (:373-389)
       [cl_cfg.name 'si' (ours): si_begin_task before the epochs, consolidation right after them, before the reload]
       [cl_cfg.name 'agem' (ours): once the memory holds clips, a reference gradient per iteration and the projection]
+      [cl_cfg.name 'der' (ours): after the reload the new memory clips' logits are recorded; later steps replay them]
 
 What is ours rather than the reference's: the stream is any iterable with QILSetTask's contract
 (`(data, loader, num_next_classes)` per task, a `.memory` attribute; utils/cl_stream.py has an in-memory one --
@@ -29,6 +30,9 @@ import torch
 
 from .cl_methods import regularizers
 from .utils.train_utils import make_optimizer, make_scheduler, save_checkpoint, train_one_epoch
+
+
+DER_BANK_FILE = 'der_bank.pt'      # cl_cfg.name 'der': DERBank.state_dict(), written next to the memory pickle
 
 
 def load_best_checkpoint(model, file_folder, file_name, current_task, gpu_id):
@@ -148,12 +152,31 @@ def run_episodes(cfg, model, train_stream, validate=None, ckpt_folder=None, gpu_
     A-GEM proper wants a stream built with train_enable=False, whose task loader does not mix the memory in; with
     train_enable=True the method is replay plus projection.  With use_graph the task batch's step replays as usual and
     the reference pass stays eager between the replays.  Not with a reducer (ValueError).
+    cl_cfg.name 'der' (ours; cl_methods/der.py): at the end of every task -- memory updated, best checkpoint reloaded, head not
+    yet grown -- the clips that entered the memory get their logits recorded in `model.der_bank` and evicted clips lose their
+    record; from the next task on every step adds cl_cfg['der_alpha'] times the mean squared distance between the memory
+    clips' logits and their records ('der_loss' in the loss dict; ops.der_replay, part of a replayed step).  A stream built
+    with train_enable=True gives DER++ (the memory clips' labels are in the detection loss); with train_enable=False no
+    memory clip reaches a batch and the term is zero.  With ckpt_folder the bank is written next to the memory pickle
+    (DER_BANK_FILE) and start_task > 0 reads it back -- or raises.  Not with a reducer, nor with type_sampling 'icarl'.
     Returns (model, optimizer, scheduler, log) with log = list of per-task dicts."""
     from .cl_methods import agem as agem_mod
+    from .cl_methods import der as der_mod
     is_main = int(os.environ.get("LOCAL_RANK", "0")) == 0
     imp_opts = regularizers.importance_options(cfg['cl_cfg'])      # a bad value fails here, not after the first task
     use_si = _si_check(cfg, start_epoch)
     use_agem = agem_mod.check_supported(cfg['cl_cfg']['name'], reducer)
+    use_der = der_mod.check_supported(cfg['cl_cfg']['name'], reducer, type_sampling=cfg['cl_cfg'].get('type_sampling'))
+    if use_der:
+        model.der_alpha = float(cfg['cl_cfg'].get('der_alpha', model.der_alpha))
+        if getattr(model, 'der_bank', None) is None:
+            model.der_bank = der_mod.DERBank()
+        if start_task > 0:
+            path = None if ckpt_folder is None else os.path.join(ckpt_folder, DER_BANK_FILE)
+            if path is None or not os.path.exists(path):
+                raise ValueError("cl_cfg.name 'der' resumed at task %d needs the recorded logits of the memory (%s, written next "
+                                 "to the memory pickle after every task): none found" % (start_task, path or DER_BANK_FILE))
+            model.der_bank.load_state_dict(torch.load(path, map_location='cpu', weights_only=False), device=model.device)
     optimizer = make_optimizer(model, cfg['opt'])
 
     def make_graph(opt):
@@ -233,6 +256,14 @@ def run_episodes(cfg, model, train_stream, validate=None, ckpt_folder=None, gpu_
             # EVERY rank reloads the task's best state (train_cl.py:363 runs on every rank): replicas that kept their
             # last-epoch weights would never meet the others again -- the gradient average does not re-align weights
             model = load_best_checkpoint(model, ckpt_folder, ck_name, j, gpu_id)
+        if use_der:
+            # the memory is final for this task and the model is the one the next task starts from, its head not yet grown:
+            # clips that entered the memory now get their record, evicted clips lose theirs, older records stay as they are
+            bank = model.der_bank
+            entry['der_dropped'] = bank.drop_missing(model.memory)
+            entry['der_recorded'] = der_mod.record_memory(model, bank, model.memory, j)
+            if ckpt_folder is not None and is_main:
+                torch.save(bank.state_dict(), os.path.join(ckpt_folder, DER_BANK_FILE))
         if validate is not None:
             entry['final_metric'] = validate(model, max_epochs - 1, j)
         log.append(entry)
@@ -283,6 +314,8 @@ def run_episodes_bic(cfg, model, train_stream, validate=None, ckpt_folder=None, 
     from .cl_methods.bic import BiCCache, fit_bias_layer, newest_split
     from .utils.cl_stream import DistributedBatchLoader
     agem_mod.check_supported(cfg['cl_cfg']['name'], driver='run_episodes_bic')
+    from .cl_methods import der as der_mod
+    der_mod.check_supported(cfg['cl_cfg']['name'], driver='run_episodes_bic')      # 'der': run_episodes only, as 'agem'
     optimizer = make_optimizer(model, cfg['opt'])
 
     def make_graph(opt):
@@ -429,6 +462,8 @@ def run_episodes_nlq(cfg, model, train_stream, val_stream, evaluator, ckpt_folde
     from .cl_methods import agem as agem_mod
     from .utils import train_utils_nlq as tu
     agem_mod.check_supported(cfg['cl_cfg']['name'], driver='run_episodes_nlq')
+    from .cl_methods import der as der_mod
+    der_mod.check_supported(cfg['cl_cfg']['name'], driver='run_episodes_nlq')      # 'der': run_episodes only, as 'agem'
     is_main = int(os.environ.get("LOCAL_RANK", "0")) == 0
     imp_opts = regularizers.importance_options(cfg['cl_cfg'])
     use_si = _si_check(cfg, start_epoch)
