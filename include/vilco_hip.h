@@ -1100,6 +1100,48 @@ int vilco_prompt_bwd(const vilco_prompt_desc* d, const float* g_prompted, const 
 /* it (tests, end-of-epoch checks); bit 0 = a prompt index outside [0, P).                                               */
 int vilco_status_word_take(int32_t* out);
 
+/* ------------------------------------------------------------------------------------------ */
+/* CODA-Prompt (Smith et al., "CODA-Prompt: COntinual Decomposed Attention-based Prompting for Rehearsal-Free         */
+/* Continual Learning", CVPR 2023): soft weighting of the pool's components, prepend (csrc/coda.hip).  The reference   */
+/* project has no counterpart; tests/coda_restatement.py states the same formulas in float64.                          */
+/*   query     xk[b] = mean_l x[b][l] over all L rows (padding rows count, as in the L2P op's mean mode)                */
+/*   weights   for m < f: u = xk[b] (.) attn[m];  alpha[b][m] = <u, key[m]> / (max(|u|, 1e-12) max(|key[m]|, 1e-12))    */
+/*             (F.normalize semantics: a zero vector gives exactly 0);  alpha[b][m] = 0 for m >= f                      */
+/*   outputs   prompted[b] = [ sum_{m < f} alpha[b][m] prompt[m] (in order of m) ; x[b] ]  -- the x rows are bit copies;  */
+/*             want_ortho: ortho = pen(key[:f]) + pen(attn[:f]) + pen(prompt[:f] as [f][len C]),                        */
+/*             pen(T) = mean over the f x f entries of (T T^t - I)^2;  otherwise no Gram launch and ortho = 0 exactly.  */
+/* fwd: two launches, three with want_ortho.  bwd: at most two.  g_prompted [B][len + L][C], g_ortho device float[1]    */
+/* (read with want_ortho only).  The query is a constant (d_x = g_prompted[:, len:] is the caller's view, no launch);   */
+/* g_alpha[b][m] = <g_prompted[b][:len], prompt[m]>;  d_prompt[m] = sum_b alpha[b][m] g_prompted[b][:len];  d_key and    */
+/* d_attn through the cosine: d alpha / d u = (k^ - alpha u^) / |u|, d alpha / d key = (u^ - alpha k^) / |key|,          */
+/* d_attn[m] = sum_b g_alpha xk[b] (.) d alpha / d u, a norm below the clamp treated as the clamp's constant; plus the   */
+/* penalty's g_ortho 4 / f^2 (T T^t - I) T.  Sums over b in order.  Rows [s, f) only: rows [0, s) (frozen, detached in   */
+/* the method) and [f, M) (unused) of all three gradients are exact zeros.  Each of d_prompt / d_key / d_attn may be    */
+/* NULL.  alpha is handed out in fp32 and kept in fp64 in the workspace: every other value is computed from the fp64    */
+/* copy.  No host read, no float atomics, fp64 sums in a fixed order: the same bits on every call.  `workspace`         */
+/* (vilco_coda_workspace bytes, 256-byte aligned) is written by fwd and read by bwd: keep it between the two.           */
+/* BADARG before any device work: !(1 <= f <= M <= 128), !(0 <= s < f), len, B, L, C < 1, null operands.                */
+/* ------------------------------------------------------------------------------------------ */
+typedef struct vilco_coda_desc {
+  const float* x;           /* [B][L][C] */
+  const float* prompt;      /* [M][len][C] */
+  const float* key;         /* [M][C] */
+  const float* attn;        /* [M][C] */
+  int32_t B, L, C, M, len;
+  int32_t s, f;             /* the task's rows [s, f); rows [0, s) are used but frozen, rows [f, M) unused */
+  int32_t want_ortho;
+  /* outputs of fwd */
+  float* alpha;             /* [B][M] */
+  float* prompted;          /* [B][len + L][C] */
+  float* ortho;             /* [1] */
+  void* workspace;
+  size_t workspace_bytes;
+} vilco_coda_desc;
+size_t vilco_coda_workspace(const vilco_coda_desc* d);
+int vilco_coda_fwd(const vilco_coda_desc* d, void* stream);
+int vilco_coda_bwd(const vilco_coda_desc* d, const float* g_prompted, const float* g_ortho, float* d_prompt,
+                   float* d_key, float* d_attn, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

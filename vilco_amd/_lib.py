@@ -160,6 +160,13 @@ class PromptDesc(C.Structure):
                 ("reduce_sim", c_fp), ("workspace", c_fp), ("workspace_bytes", sz)]
 
 
+class CodaDesc(C.Structure):
+    _cname_ = "vilco_coda_desc"
+    _fields_ = [("x", c_fp), ("prompt", c_fp), ("key", c_fp), ("attn", c_fp),
+                ("B", i32), ("L", i32), ("C", i32), ("M", i32), ("len", i32), ("s", i32), ("f", i32), ("want_ortho", i32),
+                ("alpha", c_fp), ("prompted", c_fp), ("ortho", c_fp), ("workspace", c_fp), ("workspace_bytes", sz)]
+
+
 # name -> (restype, argtypes); must list every symbol include/vilco_hip.h declares
 SIGNATURES = {
     "vilco_status_str": (C.c_char_p, [C.c_int]),
@@ -297,6 +304,9 @@ SIGNATURES = {
     "vilco_prompt_fwd": (C.c_int, [C.POINTER(PromptDesc), c_fp]),
     "vilco_prompt_bwd": (C.c_int, [C.POINTER(PromptDesc), c_fp, c_fp, c_fp, c_fp, c_fp, c_fp]),
     "vilco_status_word_take": (C.c_int, [C.POINTER(i32)]),
+    "vilco_coda_workspace": (sz, [C.POINTER(CodaDesc)]),
+    "vilco_coda_fwd": (C.c_int, [C.POINTER(CodaDesc), c_fp]),
+    "vilco_coda_bwd": (C.c_int, [C.POINTER(CodaDesc), c_fp, c_fp, c_fp, c_fp, c_fp, c_fp]),
 }
 
 _lib = None

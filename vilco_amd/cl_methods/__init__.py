@@ -1,1 +1,2 @@
 from .prompt import Prompt  # noqa: F401
+from .coda import CodaPrompt  # noqa: F401

@@ -125,7 +125,12 @@ DEFAULTS = {'init_rand_seed': 765421321,
 # apart from it: DEFAULTS stays the reference's table, key for key (tests/test_cabi_cpu.py holds it to the golden copy).
 #   cl_cfg.der_alpha: weight of the logit-replay term of cl_cfg.name 'der' (cl_methods/der.py).  0.1 is the starting value of the
 #   DER paper's grids; a hyper-parameter, not tuned here.
-EXTRA_DEFAULTS = {'cl_cfg': {'der_alpha': 0.1}}
+#   cl_cfg.prompt_type: which module a prompt pool (cl_cfg.prompt_pool) builds: 'l2p' (cl_methods/prompt.py, the reference's)
+#   or 'coda' (cl_methods/coda.py, CODA-Prompt).  cl_cfg.coda_tasks: the number of tasks the pool's components are divided
+#   among (None: run_episodes fills it from the stream; a model built directly needs it).  cl_cfg.coda_ortho_mu: weight of the
+#   orthogonality penalty, 0.0 in the method's official configs (then the penalty is not computed at all).  cl_cfg.coda_seed:
+#   task t draws its components from a generator seeded with coda_seed + t.
+EXTRA_DEFAULTS = {'cl_cfg': {'der_alpha': 0.1, 'prompt_type': 'l2p', 'coda_tasks': None, 'coda_ortho_mu': 0.0, 'coda_seed': 0}}
 
 
 def _merge(src, dst):

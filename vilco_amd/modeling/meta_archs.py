@@ -18,7 +18,7 @@ from torch import nn
 from torch.nn import functional as F
 
 from .. import ops, switches
-from ..cl_methods import Prompt
+from ..cl_methods import CodaPrompt, Prompt
 from ..utils.nms import batched_nms
 from ..utils.model_ema import ModelEmaV2
 from .blocks import LayerNorm, MaskedConv1D, Scale, from_tm, lens_to_mask, to_tm
@@ -413,7 +413,16 @@ class PtTransformer(nn.Module):
 
         self.prompt_pool = cl_cfg['prompt_pool']
         self.use_prompt_mask = True
-        if cl_cfg['length'] is not None and cl_cfg['pool_size'] is not None and self.prompt_pool:
+        self.coda_ortho_mu = float(cl_cfg.get('coda_ortho_mu', 0.0))      # prompt_type 'coda' (cl_methods/coda.py)
+        self._coda_ortho = None              # the step's penalty, from forward_prepared to _cl_terms
+        prompt_type = cl_cfg.get('prompt_type', 'l2p')
+        if prompt_type not in ('l2p', 'coda'):
+            raise ValueError("cl_cfg.prompt_type must be 'l2p' or 'coda', got %r" % (prompt_type,))
+        if cl_cfg['length'] is not None and cl_cfg['pool_size'] is not None and self.prompt_pool and prompt_type == 'coda':
+            # ours: CODA-Prompt in the L2P pool's place.  Raises ValueError without coda_tasks or when it does not divide the pool
+            self.prompt = CodaPrompt(cl_cfg['pool_size'], cl_cfg['length'], cl_cfg['embed_dim'], cl_cfg.get('coda_tasks'),
+                                     ortho=self.coda_ortho_mu != 0.0, seed=cl_cfg.get('coda_seed', 0))
+        elif cl_cfg['length'] is not None and cl_cfg['pool_size'] is not None and self.prompt_pool:
             self.prompt = Prompt(length=cl_cfg['length'], embed_dim=cl_cfg['embed_dim'], embedding_key='mean',
                                  prompt_init='uniform', prompt_pool=True, prompt_key=True,
                                  pool_size=cl_cfg['pool_size'], top_k=cl_cfg['topk'], batchwise_prompt=True,
@@ -675,6 +684,9 @@ class PtTransformer(nn.Module):
                 return False
         elif prev_out_cls_logits:
             return False
+        if isinstance(getattr(self, 'prompt', None), CodaPrompt):
+            # ops.coda_prompt reads nothing on the host; the tensor-op body slices by host integers only, but stays eager
+            return bool(ops.fused_prompt and 0 <= task_id < self.prompt.n_tasks)
         if hasattr(self, 'prompt') and not (0 <= task_id and (task_id + 1) * self.prompt.top_k <= self.prompt.pool_size):
             # a task past the pool selects its prompts by similarity: only ops.prompt_pool does that without reading the host
             if not (ops.fused_prompt and task_id >= 0):
@@ -696,7 +708,15 @@ class PtTransformer(nn.Module):
             text_tm, text_lens = ops.transpose(inp.text_cf), inp.text_lens
 
         reduce_sim = None
-        if hasattr(self, 'prompt'):
+        self._coda_ortho = None
+        if isinstance(getattr(self, 'prompt', None), CodaPrompt):
+            # CODA-Prompt: one weighted prompt of `length` tokens in front of the text; a task outside the pool's division
+            # raises (ValueError) on the host while training, an eval forward uses every component up to the stored task's
+            res = self.prompt(text_tm, task_id=task_id, train=is_training)
+            self.total_prompt_len = res['total_prompt_len']
+            text_tm = res['prompted_embedding']
+            self._coda_ortho = res['ortho'] if is_training else None
+        elif hasattr(self, 'prompt'):
             # L2P prompts are prepended to the text tokens (meta_archs.py:759-780).  The reference
             # rebuilds the mask over the first len(text) positions of the prompted sequence only.
             prompt_mask = None
@@ -1120,8 +1140,12 @@ class PtTransformer(nn.Module):
         """continual-learning terms on top of the detection loss (meta_archs.py:1478-1519).  On the device the iCaRL / BiC
         distillation term is one fused op (cat_logits = the concatenated logits and every level's first row in them); a
         CPU model walks the reference's loops.  level_len: int32 [B, L] valid lengths, read by the 'der' term only."""
-        if self.n_known > 0 and self.cl_name == 'l2p':
+        if self.n_known > 0 and self.cl_name == 'l2p' and reduce_sim is not None:      # (a CODA-Prompt pool has no pull term)
             final_loss = final_loss - 0.1 * reduce_sim
+        coda_ortho = getattr(self, '_coda_ortho', None)             # set by forward_prepared on a model with a CodaPrompt
+        if coda_ortho is not None and self.coda_ortho_mu != 0.0:
+            out['ortho_loss'] = self.coda_ortho_mu * coda_ortho
+            final_loss = final_loss + out['ortho_loss']
         if self.n_known > 0 and self.cl_name == 'der':
             der_loss = self._der_loss(out_cls_logits, cat_logits, level_len)
             out['der_loss'] = der_loss

@@ -2395,6 +2395,74 @@ def prompt_pool(x, prompt, key, idx=None, top_k=None, batchwise=False, embedding
     return _PromptPool.apply(x.contiguous(), prompt.contiguous(), key.contiguous(), idx, cls, (k, mode, bool(batchwise)))
 
 
+# ---------------------------------------------------------------------------------------- CODA-Prompt
+def _coda_desc(x, prompt, key, attn, s, f, want_ortho):
+    d = _lib.CodaDesc()
+    d.x, d.prompt, d.key, d.attn = x.data_ptr(), prompt.data_ptr(), key.data_ptr(), attn.data_ptr()
+    d.B, d.L, d.C = x.shape
+    d.M, d.len = prompt.shape[0], prompt.shape[1]
+    d.s, d.f, d.want_ortho = int(s), int(f), int(bool(want_ortho))
+    return d
+
+
+class _CodaPrompt(torch.autograd.Function):
+    """vilco_coda_fwd / _bwd: two launches forward (three with the penalty), at most two backward, no host read"""
+
+    @staticmethod
+    def forward(ctx, x, prompt, key, attn, cfg):
+        _chk(x, prompt, key, attn)
+        lib = _lib.load()
+        dev, (B, L, Cn) = x.device, x.shape
+        M, length = prompt.shape[0], prompt.shape[1]
+        d = _coda_desc(x, prompt, key, attn, *cfg)
+        f32 = dict(dtype=torch.float32, device=dev)
+        alpha, prompted, ortho = torch.empty(B, M, **f32), torch.empty(B, max(length, 0) + L, Cn, **f32), torch.empty((), **f32)
+        nws = lib.vilco_coda_workspace(C.byref(d))
+        ws = torch.empty(max(int(nws), 4), dtype=torch.uint8, device=dev)      # written forward, read backward: kept on ctx
+        d.alpha, d.prompted, d.ortho, d.workspace, d.workspace_bytes = alpha.data_ptr(), prompted.data_ptr(), ortho.data_ptr(), ws.data_ptr(), nws
+        _lib.check(lib.vilco_coda_fwd(C.byref(d), _stream()))
+        # the backward reads the operands and the workspace through the descriptor (never the three outputs it also names)
+        ctx.desc, ctx.keep = d, (x, prompt, key, attn, ws)
+        ctx.mark_non_differentiable(alpha)
+        return prompted, ortho, alpha
+
+    @staticmethod
+    def backward(ctx, g_prompted, g_ortho, *unused):
+        x, prompt, key, attn = ctx.keep[:4]
+        d, dev = ctx.desc, x.device
+        g_prompted = (torch.zeros(d.B, d.len + d.L, d.C, dtype=torch.float32, device=dev) if g_prompted is None
+                      else g_prompted.contiguous().float())
+        g_ortho = torch.zeros((), dtype=torch.float32, device=dev) if g_ortho is None else g_ortho.contiguous().float()
+        want_x, want_p, want_k, want_a = ctx.needs_input_grad[:4]
+        dp = torch.empty_like(prompt) if want_p else None
+        dk = torch.empty_like(key) if want_k else None
+        da = torch.empty_like(attn) if want_a else None
+        _lib.check(_lib.load().vilco_coda_bwd(C.byref(d), g_prompted.data_ptr(), g_ortho.data_ptr(), _p(dp), _p(dk), _p(da),
+                                              _stream()))
+        dx = g_prompted[:, d.len:] if want_x else None              # the query is a constant: the slice, no launch
+        return dx, dp, dk, da, None
+
+
+def coda_prompt(x, prompt, key, attn, s, f, want_ortho=False):
+    """CODA-Prompt as one operator (include/vilco_hip.h: vilco_coda_desc; Smith et al., CVPR 2023).  x [B, L, C], prompt
+    [M, len, C], key [M, C], attn [M, C]: fp32 on the device.  Components [0, f) are mixed, [s, f) are the task's own: with
+    xk = mean_l x, alpha[b][m] = cos(xk[b] * attn[m], key[m]) (F.normalize semantics) and p[b] = sum_{m < f} alpha[b][m]
+    prompt[m]  -> (prompted [B, len + L, C] = [p ; x], ortho (0-dim; the orthogonality penalty over rows [0, f) of the three
+    tensors when want_ortho, else an exact 0 and no Gram launch), alpha [B, M] with zeros in columns >= f).
+    Gradients reach prompt, key and attn (each only if it requires one; rows outside [s, f) are exact zeros) from prompted and
+    ortho, and x as the slice g_prompted[:, len:] (the query is a constant, as in the paper).  alpha is non-differentiable."""
+    for t in (x, prompt, key, attn):
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise RuntimeError("vilco_amd ops run on the HIP device only (got a %s tensor); there is no CPU fallback"
+                               % (t.device if torch.is_tensor(t) else type(t).__name__))
+    if (x.dim() != 3 or prompt.dim() != 3 or key.dim() != 2 or prompt.shape[2] != x.shape[2]
+            or key.shape != (prompt.shape[0], x.shape[2]) or attn.shape != key.shape):
+        raise ValueError("coda_prompt: x [B, L, C], prompt [M, len, C], key [M, C], attn [M, C]; got %s %s %s %s" %
+                         (tuple(x.shape), tuple(prompt.shape), tuple(key.shape), tuple(attn.shape)))
+    return _CodaPrompt.apply(x.contiguous(), prompt.contiguous(), key.contiguous(), attn.contiguous(),
+                             (int(s), int(f), bool(want_ortho)))
+
+
 # ---------------------------------------------------------------------------------------- inference decode
 def decode(logits, offsets, points, level_row0, level_len, topk, pre_nms_thresh, duration_thresh):
     """vilco_decode: threshold -> exact top-k -> segment decode -> duration filter of one clip's pyramid (all levels, one

@@ -135,6 +135,27 @@ def _si_consolidate(cfg, model, optimizer):
     return {k: list(v) for k, v in reg.items()}
 
 
+def _coda_begin(cfg, model, train_stream, start_task, reducer):
+    """CODA-Prompt at the start of run_episodes -> whether the run uses it.  cl_cfg['coda_tasks'] None is filled from the stream;
+    a model that holds a CodaPrompt must divide its pool among as many tasks as the stream has; the first task's components
+    are (re)drawn -- `set_task(start_task)`, which for task 0 repeats what construction did, bit for bit."""
+    from .cl_methods import coda as coda_mod
+    cl_cfg = cfg['cl_cfg']
+    if not (cl_cfg.get('prompt_pool') and coda_mod.check_supported(cl_cfg.get('prompt_type', 'l2p'), reducer)):
+        return False
+    if cl_cfg.get('coda_tasks') is None:
+        cl_cfg['coda_tasks'] = int(train_stream.num_tasks)
+    prompt = getattr(model, 'prompt', None)
+    if not isinstance(prompt, coda_mod.CodaPrompt):
+        raise ValueError("cl_cfg.prompt_type 'coda': the model holds no CodaPrompt (build it with cl_cfg.coda_tasks = %d)"
+                         % cl_cfg['coda_tasks'])
+    if prompt.n_tasks < train_stream.num_tasks:
+        raise ValueError("cl_cfg.prompt_type 'coda': the pool is divided among %d tasks, the stream has %d"
+                         % (prompt.n_tasks, train_stream.num_tasks))
+    prompt.set_task(start_task)
+    return True
+
+
 def run_episodes(cfg, model, train_stream, validate=None, ckpt_folder=None, gpu_id=0, start_task=0, start_epoch=0,
                  combine_train=False, reducer=None, logger=None, print_freq=20, on_step_history=None, use_graph=False,
                  keep_history=True):
@@ -159,6 +180,10 @@ def run_episodes(cfg, model, train_stream, validate=None, ckpt_folder=None, gpu_
     with train_enable=True gives DER++ (the memory clips' labels are in the detection loss); with train_enable=False no
     memory clip reaches a batch and the term is zero.  With ckpt_folder the bank is written next to the memory pickle
     (DER_BANK_FILE) and start_task > 0 reads it back -- or raises.  Not with a reducer, nor with type_sampling 'icarl'.
+    cl_cfg.prompt_type 'coda' (ours; cl_methods/coda.py): cl_cfg['coda_tasks'] None is filled from the stream's task count
+    before the model is used, and `model.prompt.set_task(j)` runs at the start of task j -- after the previous task's checkpoint
+    reload and head growth, before task j's optimizer is built (its rows are new values: their moments start at zero).  Not
+    with a reducer (ValueError).
     Returns (model, optimizer, scheduler, log) with log = list of per-task dicts."""
     from .cl_methods import agem as agem_mod
     from .cl_methods import der as der_mod
@@ -177,6 +202,7 @@ def run_episodes(cfg, model, train_stream, validate=None, ckpt_folder=None, gpu_
                 raise ValueError("cl_cfg.name 'der' resumed at task %d needs the recorded logits of the memory (%s, written next "
                                  "to the memory pickle after every task): none found" % (start_task, path or DER_BANK_FILE))
             model.der_bank.load_state_dict(torch.load(path, map_location='cpu', weights_only=False), device=model.device)
+    use_coda = _coda_begin(cfg, model, train_stream, start_task, reducer)
     optimizer = make_optimizer(model, cfg['opt'])
 
     def make_graph(opt):
@@ -278,6 +304,8 @@ def run_episodes(cfg, model, train_stream, validate=None, ckpt_folder=None, gpu_
                                                                **imp_opts)
             elif use_si:
                 model.reg_params = si_reg      # (the reload above put the checkpoint's older dictionary back)
+            if use_coda:
+                model.prompt.set_task(j + 1)   # the next task's components, before its optimizer exists
             optimizer = make_optimizer(model, cfg['opt'])
             scheduler = make_scheduler(optimizer, cfg['opt'], iters_per_epoch)
             if reducer is not None:
@@ -316,6 +344,9 @@ def run_episodes_bic(cfg, model, train_stream, validate=None, ckpt_folder=None, 
     agem_mod.check_supported(cfg['cl_cfg']['name'], driver='run_episodes_bic')
     from .cl_methods import der as der_mod
     der_mod.check_supported(cfg['cl_cfg']['name'], driver='run_episodes_bic')      # 'der': run_episodes only, as 'agem'
+    from .cl_methods import coda as coda_mod
+    if cfg['cl_cfg'].get('prompt_pool'):
+        coda_mod.check_supported(cfg['cl_cfg'].get('prompt_type', 'l2p'), driver='run_episodes_bic')      # CODA-Prompt: run_episodes only
     optimizer = make_optimizer(model, cfg['opt'])
 
     def make_graph(opt):
@@ -464,6 +495,9 @@ def run_episodes_nlq(cfg, model, train_stream, val_stream, evaluator, ckpt_folde
     agem_mod.check_supported(cfg['cl_cfg']['name'], driver='run_episodes_nlq')
     from .cl_methods import der as der_mod
     der_mod.check_supported(cfg['cl_cfg']['name'], driver='run_episodes_nlq')      # 'der': run_episodes only, as 'agem'
+    from .cl_methods import coda as coda_mod
+    if cfg['cl_cfg'].get('prompt_pool'):
+        coda_mod.check_supported(cfg['cl_cfg'].get('prompt_type', 'l2p'), driver='run_episodes_nlq')      # CODA-Prompt: run_episodes only
     is_main = int(os.environ.get("LOCAL_RANK", "0")) == 0
     imp_opts = regularizers.importance_options(cfg['cl_cfg'])
     use_si = _si_check(cfg, start_epoch)

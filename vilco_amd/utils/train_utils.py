@@ -15,6 +15,7 @@ import torch
 from torch import optim
 
 from .. import _lib, ops, switches
+from ..cl_methods.coda import CodaPrompt
 from ..modeling.blocks import AffineDropPath, LayerNorm, MaskedConv1D, Scale
 from .lr_schedulers import LinearWarmupCosineAnnealingLR, LinearWarmupMultiStepLR
 
@@ -58,6 +59,10 @@ def param_groups(model):
             elif pn.endswith('scale') and isinstance(m, (Scale, AffineDropPath)):
                 no_decay.add(full)
             elif pn.endswith('rel_pe'):
+                no_decay.add(full)
+            elif isinstance(m, CodaPrompt):
+                # ours: CODA-Prompt trains its components without decay -- with a fresh optimizer per task that is also what
+                # keeps the frozen rows (zero gradient, zero moments) bit-stable
                 no_decay.add(full)
     names = {pn for pn, _ in model.named_parameters()}
     remain = names - (decay | no_decay)
