@@ -301,7 +301,12 @@ __device__ __forceinline__ float mask_score(float s, int i, int j, int len, int 
 // The row's softmax is the constant 1, so its dS = P (dP - delta) is exactly zero and it takes no part in dq or dk.  dP
 // (an MFMA over the operand planes) and delta (dO . O from the stored output) agree only to rounding, so the backward
 // kernels drop the row's dS instead of leaving that rounding in the gradients; o and dv of the row are untouched.
+// mode 1 (the XLNet mask, also under mode 3): query i sees the keys below kv_len and its own position, which is ONE key when
+// kv_len == 0 (an empty clip: every row), when kv_len == 1 and i == 0, and when Tk == 1.  The same holds there -- dqw, dqr,
+// dk (and a per-clip dkr) of an empty clip are exactly zero -- in the general kernels through this function and in the
+// hd = 64 XL kernels (attn_bwd_dq64_kernel<true>: lse = +inf; attn_bwd_dkdv64_kernel<true>: dS' = 0, P kept for dV).
 __device__ __forceinline__ bool one_key_row(int i, int len, int Tk, int mode, int w) {
+  if (mode == 1) return len <= 0 || (len == 1 && i == 0) || Tk == 1;
   if (mode != 4) return false;
   const int kend = len < Tk ? len : Tk;
   const int hi = i + w + 1 < kend ? i + w + 1 : kend, lo = i - w > 0 ? i - w : 0;      // w <= Tk: launch prologue
@@ -968,8 +973,15 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void xl_scores64_kernel(AttnArgs a)
 #pragma unroll
       for (int mi = 0; mi < 4; ++mi) {
         const int p = p0 + mi * 16 + g4 * 4;
-        if (i < T && p + 3 >= T - i && p < P - i && p + 3 < P)      // some of the 4 columns lie in row i's band
-          *reinterpret_cast<float4*>(orow[g] + p) = make_float4(s[g][mi][0] * unscale, s[g][mi][1] * unscale, s[g][mi][2] * unscale, s[g][mi][3] * unscale);
+        if (i < T && p + 3 >= T - i && p < P - i) {                 // some of the 4 columns lie in row i's band
+          if (p + 3 < P)
+            *reinterpret_cast<float4*>(orow[g] + p) = make_float4(s[g][mi][0] * unscale, s[g][mi][1] * unscale, s[g][mi][2] * unscale, s[g][mi][3] * unscale);
+          else {                        // odd T: P = 2 (mod 4), the row's last group p = P - 2 holds two columns only (rows 0 and 1 need them)
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+              if (p + r < P) orow[g][p + r] = s[g][mi][r] * unscale;
+          }
+        }
       }
     }
   }
@@ -1245,6 +1257,7 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void attn_bwd_dq64_kernel(AttnArgs 
     const int qi = q0 + 16 * g + (lane & 15);
     // P * 2^-22 = exp2(acc * c2 - lse2): natural-log lse to the log2 domain, the fp16 range shift of dS folded in
     lse2[g] = qi < a.Tq ? a.lse[row_bh + qi] * 1.44269504088896340736f + 22.f : 0.f;
+    if constexpr (XL) { if (one_key_row(qi, len, a.Tk, 1, 0)) lse2[g] = INFINITY; }      // P = exp2(-inf) = 0, hence dS = 0
     // delta_i = dO_i . O_i in exact fp32 (lane group g4 covers channels ks*32 + 8 g4 .. +7); also left for attn_bwd_dkdv
     const float delta_i = delta64(a, b, h, qi, g4);
     if (g4 == 0 && qi < a.Tq) a.delta[row_bh + qi] = delta_i;
@@ -1543,6 +1556,7 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void attn_bwd_dkdv64_kernel(AttnArg
     xl_dma_rows<16>(bias, bias_ld, a.Tq, q0 + wave_s * 16, bias_voff, sbias_lds + (unsigned)(stage * 64 + wave_s * 16) * 272u);
   };
   const bool xl_edge = XL && (k0 + 64 > len || k0 + 64 > a.Tk);      // some key of this workgroup is beyond kv_len / Tk
+  [[maybe_unused]] const bool xl_one = XL && (len <= 1 || a.Tk == 1);      // some query row of this clip has ONE key: one_key_row()
 
   QFrag<HDP, 2> kf, vf;                                     // B fragments of this wave's 16 keys (rows >= Tk read as zero)
   load_qfrag<HDP, 2>(kf, a.kn, a.kn.p + (long)bh * a.kn.batch_stride, k0 + wave * 16, lane);
@@ -1679,8 +1693,14 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void attn_bwd_dkdv64_kernel(AttnArg
         f32x2 dv = {(da * sc.sdo) * sc.sv, (db * sc.sdo) * sc.sv};
         f32x2 pv = {dp[bb][r], dp[bb][r + 1]};
         if constexpr (XL) { dv = dv / f32x2{a.drop_inv_keep, a.drop_inv_keep}; pv = pv * f32x2{keep0, keep1}; }
-        const f32x2 d = p * ((pv - dv) * t37v);
-        if constexpr (XL) p = p * f32x2{keep0, keep1};       // dV sees the dropped probabilities
+        f32x2 d = p * ((pv - dv) * t37v);
+        if constexpr (XL) {
+          if (xl_one) {                                      // (workgroup-uniform) rows with one key: dS is zero, P stays
+            if (one_key_row(qa, len, a.Tk, 1, 0)) d[0] = 0.f;
+            if (one_key_row(qa + 1, len, a.Tk, 1, 0)) d[1] = 0.f;
+          }
+          p = p * f32x2{keep0, keep1};                       // dV sees the dropped probabilities
+        }
         const f16x2 hp = {(_Float16)p[0], (_Float16)p[1]}, hd = {(_Float16)d[0], (_Float16)d[1]};
         const uint32_t hpu = __builtin_bit_cast(uint32_t, hp), hdu = __builtin_bit_cast(uint32_t, hd);
         uint32_t lp, ld;
