@@ -589,6 +589,43 @@ typedef struct vilco_si_desc {
   float xi;                    /* > 0 (Zenke: 0.1) */
 } vilco_si_desc;
 int vilco_si_consolidate(const vilco_si_desc* d, void* stream);
+/* RWalk (Riemannian Walk: Chaudhry, Dokania, Ajanthan, Torr, "Riemannian Walk for Incremental Learning: Understanding Forgetting   */
+/* and Intransigence", ECCV 2018) inside the update: vilco_optim_step's update (p, the optimizer state and chunk_amax get the bits  */
+/* they get there) which also keeps, per element of every tensor t with optim.si_ptrs[t] != 0, four fp32 states:                   */
+/*   F  = fisher   <- F + alpha * (gr*gr - F)            gr as for si_ptrs; four roundings, in this order                           */
+/*   w  = omega    <- fmaf(-gr, p_new - p_old, w)        optim.si_ptrs is its table                                                 */
+/*   and when *tick % delta_t == 0 (a checkpoint update; *tick = iterations since the task began, counted after this one):          */
+/*   s  = score    <- s + max(w, 0) / (0.5 * F * d*d + eps),  d = p_new - theta_ck   (new F and w; double, rounded once)            */
+/*   w <- 0 ;  theta_ck <- p_new                                                                                                    */
+/* score and theta_ck are neither read nor written by other updates; a tensor with si_ptrs[t] == 0 has none of its states touched.  */
+/* tick is read from device memory by the kernel (a captured launch follows it); the caller advances it once per iteration.         */
+/* EVERY block reads it, whether its tensor is tracked or not: it must be a device address whenever the call launches.             */
+/* A NULL descriptor, NULL optim.si_ptrs / rw_ptrs / tick, alpha outside (0, 1], eps <= 0, delta_t < 1, and whatever                */
+/* vilco_optim_step refuses: VILCO_ERR_BADARG before anything is read.                                                              */
+typedef struct vilco_rwalk_step_desc {
+  vilco_optim_desc optim;      /* si_ptrs = the omega table (required) */
+  const int64_t* rw_ptrs;      /* device int64 [3][n]: fisher, score, theta_ck of tensor t (read only where si_ptrs[t] != 0) */
+  const int32_t* tick;         /* device, one word */
+  float alpha;                 /* in (0, 1]: the weight of the new squared gradient (the paper: 0.9) */
+  float eps;                   /* > 0 */
+  int32_t delta_t;             /* >= 1 (the paper: 10) */
+} vilco_rwalk_step_desc;
+int vilco_optim_step_rwalk(const vilco_rwalk_step_desc* d, void* stream);
+/* RWalk, end of a task: three launches over all regularised tensors, no value read by the host.                                    */
+/*   flush   s += max(w, 0) / (0.5 * F * (p - theta_ck)^2 + eps) (double, rounded once) ; w = 0 ; per-chunk max F and max s into     */
+/*           partial (device float[2 * nchunks])                                                                                    */
+/*   finish  out (device float[2]) = {max F, max s}; a NaN among them reaches out                                                   */
+/*   apply   importance = F / maxF + s / maxS (double, rounded once; a term whose max is 0 contributes 0) ; optpar = p ;             */
+/*           s = s / 2 ; theta_ck = p ; F is kept                                                                                   */
+/* n <= 0, a null table / out_ptrs / partial / out, eps <= 0: VILCO_ERR_BADARG.  nchunks == 0 launches nothing.                     */
+typedef struct vilco_rwalk_desc {
+  vilco_chunk_table table;     /* rows: param, fisher, score, omega, theta_ck; numel[t] = elements of the parameter */
+  const int64_t* out_ptrs;     /* device int64 [2][n]: importance, optpar (written, not read) */
+  float* partial;              /* device float[2 * nchunks] */
+  float* out;                  /* device float[2] */
+  float eps;                   /* > 0 */
+} vilco_rwalk_desc;
+int vilco_rwalk_consolidate(const vilco_rwalk_desc* d, void* stream);
 /* dst[0..n) = vals[0..n): n <= 16 HOST floats carried as kernel arguments (stream-ordered, no staging buffer) -- how the */
 /* host hands this iteration's learning rates to a captured optimizer step.                                              */
 int vilco_store_f32(float* dst, const float* vals, int32_t n, void* stream);

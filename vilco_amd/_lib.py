@@ -133,6 +133,16 @@ class SiDesc(C.Structure):
     _fields_ = [("table", ChunkTable), ("numel_old", c_fp), ("xi", f32)]
 
 
+class RwalkStepDesc(C.Structure):
+    _cname_ = "vilco_rwalk_step_desc"
+    _fields_ = [("optim", OptimDesc), ("rw_ptrs", c_fp), ("tick", c_fp), ("alpha", f32), ("eps", f32), ("delta_t", i32)]
+
+
+class RwalkDesc(C.Structure):
+    _cname_ = "vilco_rwalk_desc"
+    _fields_ = [("table", ChunkTable), ("out_ptrs", c_fp), ("partial", c_fp), ("out", c_fp), ("eps", f32)]
+
+
 class DistillDesc(C.Structure):
     _cname_ = "vilco_distill_desc"
     _fields_ = [("logits", c_fp), ("targets", c_fp), ("level_row", c_fp), ("level_T", c_fp), ("level_dev", c_fp),
@@ -236,6 +246,8 @@ SIGNATURES = {
     "vilco_grad_norm": (C.c_int, [C.POINTER(ChunkTable), f32, c_fp, c_fp, c_fp]),
     "vilco_optim_step": (C.c_int, [C.POINTER(OptimDesc), c_fp]),
     "vilco_si_consolidate": (C.c_int, [C.POINTER(SiDesc), c_fp]),
+    "vilco_optim_step_rwalk": (C.c_int, [C.POINTER(RwalkStepDesc), c_fp]),
+    "vilco_rwalk_consolidate": (C.c_int, [C.POINTER(RwalkDesc), c_fp]),
     "vilco_store_f32": (C.c_int, [c_fp, C.POINTER(f32), i32, c_fp]),
     "vilco_qkv_pre_supported": (C.c_int, [i32]),
     "vilco_qkv_pre_amax_parts": (C.c_int, [i32, i32, i32]),

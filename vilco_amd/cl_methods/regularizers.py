@@ -16,7 +16,8 @@ dictionary for the whole stream; both do their arithmetic in vilco_cl_accumulate
 launch per batch / per merge.
 
 Synaptic Intelligence (kind='si', bottom of the file) shares the penalty and MAS's 'importance' key; its importance is a
-path integral the optimizer's update kernel takes at every step, consolidated by one launch at the end of a task."""
+path integral the optimizer's update kernel takes at every step, consolidated by one launch at the end of a task.
+RWalk (kind='rwalk', below SI) does the same with a Fisher moving average and path scores kept by that kernel."""
 import ctypes
 
 import torch
@@ -28,9 +29,9 @@ CHUNK = ops.CHUNK
 
 def _entries(model, kind):
     """(parameter, importance, optpar) of every consolidated (task, name) pair; kind 'ewc' reads reg_params['fisher'],
-    'mas' and 'si' read reg_params['importance']"""
-    if kind not in ('ewc', 'mas', 'si'):
-        raise ValueError("kind must be 'ewc', 'mas' or 'si', got %r" % (kind,))
+    'mas', 'si' and 'rwalk' read reg_params['importance']"""
+    if kind not in ('ewc', 'mas', 'si', 'rwalk'):
+        raise ValueError("kind must be 'ewc', 'mas', 'si' or 'rwalk', got %r" % (kind,))
     reg = getattr(model, 'reg_params', None) or {}
     key = 'fisher' if kind == 'ewc' else 'importance'
     if key not in reg or 'optpar' not in reg:
@@ -296,3 +297,138 @@ def on_task_si_update(model, optimizer=None, xi=SI_XI):
         _lib.check(_lib.load().vilco_si_consolidate(ctypes.byref(d), torch.cuda.current_stream().cuda_stream))
     reg['importance'], reg['optpar'] = [imp_d], [opt_d]
     return reg
+
+
+# ------------------------------------------------------------------------------------------------ RWalk
+# (Riemannian Walk: Chaudhry, Dokania, Ajanthan, Torr, ECCV 2018; the reference has no RWalk.)  Per element of every parameter
+# SI regularises (`_si_params`) four fp32 states, advanced by the optimizer's update kernel (FusedOptimizer.attach_rwalk ->
+# vilco_optim_step_rwalk) at every update:
+#     F <- F + alpha (gr^2 - F)              the diagonal empirical Fisher as a moving average of the squared gradient;
+#     w <- w - gr (p_new - p_old)            SI's path integral, over the interval since the last checkpoint;
+#   every delta_t iterations (a checkpoint):  s <- s + max(w, 0) / (0.5 F (p_new - theta_ck)^2 + eps),  w <- 0,  theta_ck <- p_new
+# gr = the clipped gradient the update consumes -- as for SI it includes the penalty gradient and excludes the weight decay.
+# F and s are kept across tasks, w and theta_ck are per task.  The end of a task needs NO pass over the data
+# (`on_task_rwalk_update`): the open interval is closed, importance = F / max F + s / max s goes under MAS's keys, s is halved.
+RWALK_ALPHA, RWALK_DELTA_T, RWALK_EPS = 0.9, 10, 1e-8      # alpha, delta_t: the paper's; eps: ours (core/config.py EXTRA_DEFAULTS)
+
+
+def rwalk_options(cl_cfg):
+    """the keyword arguments of `rwalk_begin_task` / `on_task_rwalk_update` that a cl_cfg asks for: cl_cfg['rwalk_alpha'] in
+    (0, 1], ['rwalk_delta_t'] an integer >= 1, ['rwalk_eps'] > 0 (all optional); a bad value raises ValueError here, before the
+    first task."""
+    alpha = float(cl_cfg.get('rwalk_alpha', RWALK_ALPHA))
+    delta_t = cl_cfg.get('rwalk_delta_t', RWALK_DELTA_T)
+    eps = float(cl_cfg.get('rwalk_eps', RWALK_EPS))
+    if not 0.0 < alpha <= 1.0:
+        raise ValueError("cl_cfg.rwalk_alpha must lie in (0, 1], got %r" % (alpha,))
+    if isinstance(delta_t, bool) or int(delta_t) != delta_t or int(delta_t) < 1:
+        raise ValueError("cl_cfg.rwalk_delta_t must be an integer >= 1, got %r" % (delta_t,))
+    if not eps > 0.0:
+        raise ValueError("cl_cfg.rwalk_eps must be positive, got %r" % (eps,))
+    return dict(alpha=alpha, delta_t=int(delta_t), eps=eps)
+
+
+def rwalk_begin_task(model, optimizer, alpha=RWALK_ALPHA, delta_t=RWALK_DELTA_T, eps=RWALK_EPS):
+    """Start of a task (after the class head has grown and the task's optimizer exists): model.rwalk_state = {name: {'fisher',
+    'score', 'omega', 'theta_ck'}} for every regularised parameter.  fisher and score of an earlier task (or of
+    `load_rwalk_state`) are carried on their flat prefix -- the rows a class head has gained since start from zero -- omega is
+    zeroed, theta_ck is a snapshot of the parameter, and the state is attached to the optimizer, which zeroes its iteration
+    word `rwalk_tick`.  A name that is no longer regularised is dropped.  A model without any regularised parameter gets an empty
+    state and an optimizer with nothing attached (the plain update).
+    Data parallel: nothing is exchanged; every rank steps with the averaged gradient and makes the same update (as SI)."""
+    old_state = getattr(model, 'rwalk_state', None) or {}
+    state = {}
+    for name, p in _si_params(model):
+        if not (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous()):
+            raise RuntimeError("RWalk needs contiguous fp32 parameters on the HIP device (%s)" % name)
+        st = {'omega': torch.zeros_like(p), 'theta_ck': p.detach().clone()}
+        old = old_state.get(name, {})
+        for key in ('fisher', 'score'):
+            prev = old.get(key)
+            if prev is not None and prev.shape == p.shape and prev.device == p.device and prev.is_contiguous():
+                st[key] = prev
+                continue
+            st[key] = torch.zeros_like(p)
+            if prev is not None:
+                if not (prev.numel() <= p.numel() and prev.shape[1:] == p.shape[1:]):
+                    raise RuntimeError("rwalk_state of %s (%s) is no prefix of the parameter (%s)" % (name, tuple(prev.shape), tuple(p.shape)))
+                st[key].view(-1)[:prev.numel()].copy_(prev.reshape(-1))
+        state[name] = st
+    model.rwalk_state = state
+    optimizer.attach_rwalk({p: state[name] for name, p in _si_params(model)}, alpha=alpha, delta_t=delta_t, eps=eps)
+    return state
+
+
+def on_task_rwalk_update(model, optimizer=None, eps=RWALK_EPS, return_max=False):
+    """End of a task: vilco_rwalk_consolidate -- three launches over all regularised tensors, nothing read by the host -- closes
+    the interval the last checkpoint left open, takes max F and max s over ALL tensors on the device and writes
+    importance = F / max F + s / max s (each term in [0, 1]; a term whose max is 0 contributes 0) and optpar = the CURRENT
+    parameters; then s <- s / 2 (the paper's averaging of old and new scores), theta_ck <- p, w = 0, and F is kept.
+    model.reg_params ends up holding ONE 'importance' / 'optpar' dictionary under MAS's keys; it is REPLACED, not accumulated:
+    F and s are running quantities that already contain the earlier tasks.  A name RWalk does not track is not carried.
+    Ordering (train_cl.run_episodes): as SI, after the task's training and before its best checkpoint is reloaded.
+    `optimizer` is not used (the signature mirrors on_task_si_update); an empty rwalk_state (no regularised parameter) leaves
+    one empty dictionary and launches nothing.  return_max: also return the device tensor {max F, max s}."""
+    if not eps > 0:
+        raise ValueError("rwalk_eps must be positive, got %r" % (eps,))
+    state = getattr(model, 'rwalk_state', None)
+    if state is None or any('omega' not in st for st in state.values()):
+        raise RuntimeError("on_task_rwalk_update without rwalk_begin_task: the model carries no rwalk_state of this task")
+    if not state:      # rwalk_begin_task found no regularised parameter: nothing was tracked, nothing is penalised
+        model.reg_params['importance'], model.reg_params['optpar'] = [{}], [{}]
+        return (model.reg_params, None) if return_max else model.reg_params
+    imp_d, opt_d, rows, outs, numel = {}, {}, [], [], []
+    for name, p in model.named_parameters():
+        st = state.get(name)
+        if st is None:
+            continue
+        if st['omega'].numel() != p.numel() or not p.is_contiguous():
+            raise RuntimeError("rwalk_state of %s does not fit the parameter: call rwalk_begin_task after the head has grown" % name)
+        imp_d[name], opt_d[name] = torch.empty_like(p), torch.empty_like(p)
+        rows.append((p.data_ptr(), st['fisher'].data_ptr(), st['score'].data_ptr(), st['omega'].data_ptr(), st['theta_ck'].data_ptr()))
+        outs.append((imp_d[name].data_ptr(), opt_d[name].data_ptr()))
+        numel.append(p.numel())
+    if not rows:
+        raise RuntimeError("on_task_rwalk_update: none of the %d names in model.rwalk_state is a parameter of the model"
+                           % len(state))
+    dev = next(iter(imp_d.values())).device
+    ptrs = torch.tensor([list(col) for col in zip(*rows)], dtype=torch.int64).to(dev)
+    out_ptrs = torch.tensor([list(col) for col in zip(*outs)], dtype=torch.int64).to(dev)
+    plan = ops.ChunkPlan(numel, dev)
+    partial = torch.empty(2 * max(plan.nchunks, 1), dtype=torch.float32, device=dev)
+    out = torch.zeros(2, dtype=torch.float32, device=dev)
+    d = _lib.RwalkDesc(table=plan.table(ptrs, 5), out_ptrs=out_ptrs.data_ptr(), partial=partial.data_ptr(), out=out.data_ptr(),
+                       eps=float(eps))
+    _lib.check(_lib.load().vilco_rwalk_consolidate(ctypes.byref(d), torch.cuda.current_stream().cuda_stream))
+    reg = model.reg_params
+    reg['importance'], reg['optpar'] = [imp_d], [opt_d]
+    return (reg, out) if return_max else reg
+
+
+def rwalk_state_dict(model):
+    """what outlives a task, on the host: {'fisher': {name: tensor}, 'score': {name: tensor}} (omega and theta_ck are per task)
+    and, once a task has been consolidated, its 'importance' / 'optpar' dictionary: the task's checkpoints were written before
+    the consolidation and do not hold it."""
+    state = getattr(model, 'rwalk_state', None) or {}
+    out = {key: {name: st[key].detach().cpu().clone() for name, st in state.items()} for key in ('fisher', 'score')}
+    reg = getattr(model, 'reg_params', None) or {}
+    if len(reg.get('importance', ())) == 1 and len(reg.get('optpar', ())) == 1:
+        for key in ('importance', 'optpar'):
+            out[key] = {name: t.detach().cpu().clone() for name, t in reg[key][0].items()}
+    return out
+
+
+def load_rwalk_state(model, sd, device=None):
+    """the inverse of `rwalk_state_dict`, for a resume at a task boundary: the next `rwalk_begin_task` carries fisher and score
+    on their flat prefix; an 'importance' / 'optpar' dictionary REPLACES model.reg_params -- also one the caller restored from a
+    checkpoint before (the file is newer than any checkpoint of the task it closes: those were written before the
+    consolidation).  `run_episodes(start_task > 0)` calls this."""
+    if not {'fisher', 'score'} <= set(sd) <= {'fisher', 'score', 'importance', 'optpar'} or set(sd['fisher']) != set(sd['score']):
+        raise ValueError("not an rwalk_state_dict: keys %s" % sorted(sd))
+    model.rwalk_state = {name: {'fisher': sd['fisher'][name].to(device=device).contiguous(),
+                                'score': sd['score'][name].to(device=device).contiguous()}
+                         for name in sd['fisher']}
+    if 'importance' in sd and 'optpar' in sd:
+        model.reg_params = {key: [{name: t.to(device=device).contiguous() for name, t in sd[key].items()}]
+                            for key in ('importance', 'optpar')}
+    return model.rwalk_state

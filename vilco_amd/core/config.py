@@ -130,7 +130,11 @@ DEFAULTS = {'init_rand_seed': 765421321,
 #   among (None: run_episodes fills it from the stream; a model built directly needs it).  cl_cfg.coda_ortho_mu: weight of the
 #   orthogonality penalty, 0.0 in the method's official configs (then the penalty is not computed at all).  cl_cfg.coda_seed:
 #   task t draws its components from a generator seeded with coda_seed + t.
-EXTRA_DEFAULTS = {'cl_cfg': {'der_alpha': 0.1, 'prompt_type': 'l2p', 'coda_tasks': None, 'coda_ortho_mu': 0.0, 'coda_seed': 0}}
+#   cl_cfg.rwalk_alpha / rwalk_delta_t / rwalk_eps (cl_cfg.name 'rwalk', cl_methods/regularizers.py): the weight of the new squared
+#   gradient in the Fisher moving average and the iterations between two checkpoints of the path score -- 0.9 and 10, the RWalk
+#   paper's -- and the constant in the score's denominator, for which the paper gives no value: 1e-8 is ours.
+EXTRA_DEFAULTS = {'cl_cfg': {'der_alpha': 0.1, 'prompt_type': 'l2p', 'coda_tasks': None, 'coda_ortho_mu': 0.0, 'coda_seed': 0,
+                             'rwalk_alpha': 0.9, 'rwalk_delta_t': 10, 'rwalk_eps': 1e-8}}
 
 
 def _merge(src, dst):

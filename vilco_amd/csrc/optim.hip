@@ -121,9 +121,65 @@ __device__ __forceinline__ void emit_chunk_amax(float mx, float* __restrict__ ch
 // parameter's element count, walked with the same chunk table), 0 = not regularised.  Old value, gradient and new value are in
 // registers here: the cost is one more read-modify-write stream, no launch, no atomics (every element has one owner thread).
 // SI = false never reads si_ptrs and is the kernel as it was.
-template <bool SI>
-__global__ __launch_bounds__(OPT_THREADS) void adamw_kernel(MultiArgs a, Hyper h, const float* __restrict__ coef,
-                                                            float* __restrict__ chunk_amax, const long* __restrict__ si_ptrs) {
+// RWalk (Riemannian Walk; Chaudhry, Dokania, Ajanthan, Torr, ECCV 2018): besides SI's path integral w (si_ptrs is its
+// table) the update keeps an exponential moving average of the squared gradient, the diagonal empirical Fisher F, and every
+// delta_t iterations closes the interval: the path score s gains max(w, 0) / (0.5 F d^2 + eps), d = p_new - theta_ck.
+// rw_ptrs [3][n] = addresses of fisher, score, theta_ck; tick = ONE device word, the iterations since the task began counted
+// after this one -- read from memory, so a replayed launch follows it.  The checkpoint branch is uniform over the grid; score and
+// theta_ck are neither loaded nor stored outside it.
+struct RwalkArgs {
+  const long* rw_ptrs;
+  const int* tick;
+  float alpha, eps;
+  int delta_t;
+};
+
+// what a tracked element keeps besides the optimizer state: TRACK 1 = SI (om), 2 = RWalk (all four)
+struct TrackPtrs {
+  float *om, *fi, *sc, *ck;
+  bool ckpt;
+};
+
+template <int TRACK>
+__device__ __forceinline__ TrackPtrs track_ptrs(const ChunkView& cv, const long* __restrict__ si_ptrs, const RwalkArgs& rw) {
+  TrackPtrs tp{nullptr, nullptr, nullptr, nullptr, false};
+  if constexpr (TRACK != 0) {
+    const long oa = si_ptrs[cv.t];
+    if (oa) tp.om = reinterpret_cast<float*>(oa) + cv.off;
+  }
+  if constexpr (TRACK == 2) {
+    if (tp.om) {
+      tp.fi = reinterpret_cast<float*>(rw.rw_ptrs[cv.t]) + cv.off;
+      tp.sc = reinterpret_cast<float*>(rw.rw_ptrs[cv.n + cv.t]) + cv.off;
+      tp.ck = reinterpret_cast<float*>(rw.rw_ptrs[2 * cv.n + cv.t]) + cv.off;
+    }
+    tp.ckpt = (*rw.tick % rw.delta_t) == 0;
+  }
+  return tp;
+}
+
+// RWalk's share of one element's update, after p_new is known.  fn = F + alpha (gr gr - F): four roundings, in this order (the
+// callers hold fp contract off).  The score's quotient and sum are formed in double and rounded once, as si_consolidate_kernel.
+__device__ __forceinline__ void rwalk_element(const TrackPtrs& tp, const RwalkArgs& rw, long i, float gr, float p0, float pv,
+                                              float ov, float fv, float sv, float kv) {
+#pragma clang fp contract(off)
+  const float fn = fv + rw.alpha * (gr * gr - fv);
+  const float wn = __fmaf_rn(-gr, pv - p0, ov);
+  tp.fi[i] = fn;
+  if (tp.ckpt) {
+    const double d = (double)pv - (double)kv;
+    const double q = (double)fmaxf(wn, 0.f) / (0.5 * (double)fn * d * d + (double)rw.eps);
+    tp.sc[i] = (float)((double)sv + q);
+    tp.om[i] = 0.f;
+    tp.ck[i] = pv;
+  } else {
+    tp.om[i] = wn;
+  }
+}
+
+template <int TRACK>
+__device__ __forceinline__ void adamw_body(const MultiArgs& a, const Hyper& h, const float* __restrict__ coef,
+                                           float* __restrict__ chunk_amax, const long* __restrict__ si_ptrs, const RwalkArgs& rw) {
   const ChunkView cv = chunk_view(a);
   const int t = cv.t;
   const long cnt = cv.cnt;
@@ -139,24 +195,27 @@ __global__ __launch_bounds__(OPT_THREADS) void adamw_kernel(MultiArgs a, Hyper h
   // ~100 roundings at steps 2..5), and half of that reaches the update through the square root
   const float step_size = lr / -expm1f(stp * h.log_beta1);
   const float rs2 = sqrtf(-expm1f(stp * h.log_beta2));
-  float* om = nullptr;
-  if constexpr (SI) {
-    const long oa = si_ptrs[t];
-    if (oa) om = reinterpret_cast<float*>(oa) + cv.off;
-  }
+  const TrackPtrs tp = track_ptrs<TRACK>(cv, si_ptrs, rw);
+  float* om = tp.om;
   float mx = 0.f;
   for (long i = threadIdx.x; i < cnt; i += OPT_THREADS) {
     const float keep = 1.f - lr * wd;
     {
       // every product and sum of the element's update is rounded on its own: that is how this loop has always been compiled
-      // (packed multiplies, no fused multiply-add), and the pragma holds both instantiations to it -- the path integral's extra
-      // uses of gr and pv must not change a bit of p, m or v
+      // (packed multiplies, no fused multiply-add), and the pragma holds every instantiation to it -- the path integral's and
+      // RWalk's extra uses of gr and pv must not change a bit of p, m or v
 #pragma clang fp contract(off)
       const float gr = g[i] * c;
       const float p0 = p[i];
-      float ov = 0.f;
-      if constexpr (SI) {
+      float ov = 0.f, fv = 0.f, sv = 0.f, kv = 0.f;
+      if constexpr (TRACK != 0) {
         if (om) ov = om[i];          // issued with the other loads, not behind the stores
+      }
+      if constexpr (TRACK == 2) {
+        if (om) {
+          fv = tp.fi[i];
+          if (tp.ckpt) { sv = tp.sc[i]; kv = tp.ck[i]; }
+        }
       }
       float pv = p0 * keep;
       const float mv = h.beta1 * m[i] + (1.f - h.beta1) * gr;
@@ -165,8 +224,11 @@ __global__ __launch_bounds__(OPT_THREADS) void adamw_kernel(MultiArgs a, Hyper h
       v[i] = vv;
       pv -= step_size * (mv / (sqrtf(vv) / rs2 + h.eps));
       p[i] = pv;
-      if constexpr (SI) {
+      if constexpr (TRACK == 1) {
         if (om) om[i] = __fmaf_rn(-gr, pv - p0, ov);
+      }
+      if constexpr (TRACK == 2) {
+        if (om) rwalk_element(tp, rw, i, gr, p0, pv, ov, fv, sv, kv);
       }
       mx = fmaxf(mx, fabsf(pv));
     }
@@ -174,11 +236,23 @@ __global__ __launch_bounds__(OPT_THREADS) void adamw_kernel(MultiArgs a, Hyper h
   if (chunk_amax) emit_chunk_amax(mx, chunk_amax);
 }
 
+template <bool SI>
+__global__ __launch_bounds__(OPT_THREADS) void adamw_kernel(MultiArgs a, Hyper h, const float* __restrict__ coef,
+                                                            float* __restrict__ chunk_amax, const long* __restrict__ si_ptrs) {
+  adamw_body<SI ? 1 : 0>(a, h, coef, chunk_amax, si_ptrs, RwalkArgs{});
+}
+
+__global__ __launch_bounds__(OPT_THREADS) void adamw_rwalk_kernel(MultiArgs a, Hyper h, const float* __restrict__ coef,
+                                                                  float* __restrict__ chunk_amax, const long* __restrict__ si_ptrs,
+                                                                  RwalkArgs rw) {
+  adamw_body<2>(a, h, coef, chunk_amax, si_ptrs, rw);
+}
+
 // torch.optim.SGD with momentum (no dampening / nesterov): g += wd*p ; buf = first ? g : mom*buf + g ; p -= lr*buf
 // SI: as in adamw_kernel; gr is the clipped gradient BEFORE wd * p is added to it
-template <bool SI>
-__global__ __launch_bounds__(OPT_THREADS) void sgd_kernel(MultiArgs a, Hyper h, const float* __restrict__ coef,
-                                                          float* __restrict__ chunk_amax, const long* __restrict__ si_ptrs) {
+template <int TRACK>
+__device__ __forceinline__ void sgd_body(const MultiArgs& a, const Hyper& h, const float* __restrict__ coef,
+                                         float* __restrict__ chunk_amax, const long* __restrict__ si_ptrs, const RwalkArgs& rw) {
   const ChunkView cv = chunk_view(a);
   const int t = cv.t;
   const long cnt = cv.cnt;
@@ -189,33 +263,51 @@ __global__ __launch_bounds__(OPT_THREADS) void sgd_kernel(MultiArgs a, Hyper h, 
   const float lr = h.lr_dev ? h.lr_dev[gi] : h.lr[gi], wd = h.wd[gi];
   const float c = coef ? coef[1] : 1.f;
   const bool first = h.tstep[t] <= 1.f;          // momentum buffer starts as the first gradient
-  float* om = nullptr;
-  if constexpr (SI) {
-    const long oa = si_ptrs[t];
-    if (oa) om = reinterpret_cast<float*>(oa) + cv.off;
-  }
+  const TrackPtrs tp = track_ptrs<TRACK>(cv, si_ptrs, rw);
+  float* om = tp.om;
   float mx = 0.f;
   for (long i = threadIdx.x; i < cnt; i += OPT_THREADS) {
-    // the roundings this loop has always been compiled to, spelled out so that both instantiations keep them whatever else uses
+    // the roundings this loop has always been compiled to, spelled out so that every instantiation keeps them whatever else uses
     // gc and pv: c g and wd p rounded on their own and added; momentum buf + d and p - lr buf fused
 #pragma clang fp contract(off)
     const float pv0 = p[i];
     const float gc = g[i] * c;
-    float ov = 0.f;
-    if constexpr (SI) {
+    float ov = 0.f, fv = 0.f, sv = 0.f, kv = 0.f;
+    if constexpr (TRACK != 0) {
       if (om) ov = om[i];
+    }
+    if constexpr (TRACK == 2) {
+      if (om) {
+        fv = tp.fi[i];
+        if (tp.ckpt) { sv = tp.sc[i]; kv = tp.ck[i]; }
+      }
     }
     float gr = gc + wd * pv0;
     const float b = first ? gr : __fmaf_rn(h.momentum, m[i], gr);
     m[i] = b;
     const float pv = __fmaf_rn(-lr, b, pv0);
     p[i] = pv;
-    if constexpr (SI) {
+    if constexpr (TRACK == 1) {
       if (om) om[i] = __fmaf_rn(-gc, pv - pv0, ov);
+    }
+    if constexpr (TRACK == 2) {
+      if (om) rwalk_element(tp, rw, i, gc, pv0, pv, ov, fv, sv, kv);
     }
     mx = fmaxf(mx, fabsf(pv));
   }
   if (chunk_amax) emit_chunk_amax(mx, chunk_amax);
+}
+
+template <bool SI>
+__global__ __launch_bounds__(OPT_THREADS) void sgd_kernel(MultiArgs a, Hyper h, const float* __restrict__ coef,
+                                                          float* __restrict__ chunk_amax, const long* __restrict__ si_ptrs) {
+  sgd_body<SI ? 1 : 0>(a, h, coef, chunk_amax, si_ptrs, RwalkArgs{});
+}
+
+__global__ __launch_bounds__(OPT_THREADS) void sgd_rwalk_kernel(MultiArgs a, Hyper h, const float* __restrict__ coef,
+                                                                float* __restrict__ chunk_amax, const long* __restrict__ si_ptrs,
+                                                                RwalkArgs rw) {
+  sgd_body<2>(a, h, coef, chunk_amax, si_ptrs, rw);
 }
 
 // EWC / MAS penalty (MQ/libs/cl_methods/EWC.py:6-22, MAS.py:5-21) over a chunk table of (parameter, importance,
@@ -316,6 +408,96 @@ __global__ __launch_bounds__(OPT_THREADS) void si_consolidate_kernel(MultiArgs a
     o[i] = pv;
     om[i] = 0.f;
     ts[i] = pv;
+  }
+}
+
+// End of a task under RWalk.  rows: param, fisher F, score s, omega w, theta_ck; out_ptrs [2][n] = importance, optpar.
+// Three launches, nothing read back by the host:
+//   flush   the interval the last checkpoint left open is closed as the update kernel closes one:
+//           s += max(w, 0) / (0.5 F d^2 + eps), d = p - theta_ck (double, rounded once) ; w = 0.
+//           partial[c] = max F, partial[nchunks + c] = max s over chunk c (cnt == 0: two zeros).
+//   finish  one block: out = {max F, max s} over the two runs of partials.
+//   apply   importance = F / maxF + s / maxS (double, rounded once; a term whose max is 0 contributes 0) ; optpar = p ;
+//           s = s / 2 ; theta_ck = p.  F is kept: its moving average runs on into the next task.
+// The maxima propagate a NaN (fmaxf would drop it): a poisoned F or s poisons every importance instead of vanishing.
+__device__ __forceinline__ float nan_max(float a, float b) { return (a > b || a != a) ? a : b; }
+
+// every thread gets the nan_max of the block's x
+__device__ __forceinline__ float block_nan_max(float x) {
+  __shared__ float red[OPT_THREADS];
+  red[threadIdx.x] = x;
+  __syncthreads();
+  for (int o = OPT_THREADS / 2; o > 0; o >>= 1) {
+    if (threadIdx.x < o) red[threadIdx.x] = nan_max(red[threadIdx.x], red[threadIdx.x + o]);
+    __syncthreads();
+  }
+  const float r = red[0];
+  __syncthreads();                               // red is reused by the next call
+  return r;
+}
+
+__global__ __launch_bounds__(OPT_THREADS) void rwalk_flush_kernel(MultiArgs a, float eps, float* __restrict__ partial,
+                                                                  int nchunks) {
+  const ChunkView c = chunk_view(a);
+  const float* p = c.row<const float>(0);
+  const float* f = c.row<const float>(1);
+  float* s = c.row<float>(2);
+  float* w = c.row<float>(3);
+  const float* ck = c.row<const float>(4);
+  float mf = 0.f, ms = 0.f;
+  for (long i = threadIdx.x; i < c.cnt; i += OPT_THREADS) {
+#pragma clang fp contract(off)
+    const float fv = f[i];
+    const double d = (double)p[i] - (double)ck[i];
+    const double q = (double)fmaxf(w[i], 0.f) / (0.5 * (double)fv * d * d + (double)eps);
+    const float sn = (float)((double)s[i] + q);
+    s[i] = sn;
+    w[i] = 0.f;
+    mf = nan_max(mf, fv);
+    ms = nan_max(ms, sn);
+  }
+  mf = block_nan_max(mf);
+  ms = block_nan_max(ms);
+  if (threadIdx.x == 0) {
+    partial[blockIdx.x] = mf;
+    partial[nchunks + blockIdx.x] = ms;
+  }
+}
+
+__global__ __launch_bounds__(OPT_THREADS) void rwalk_finish_kernel(const float* __restrict__ partial, int nchunks,
+                                                                   float* __restrict__ out) {
+  float mf = 0.f, ms = 0.f;
+  for (int i = threadIdx.x; i < nchunks; i += OPT_THREADS) {
+    mf = nan_max(mf, partial[i]);
+    ms = nan_max(ms, partial[nchunks + i]);
+  }
+  mf = block_nan_max(mf);
+  ms = block_nan_max(ms);
+  if (threadIdx.x == 0) {
+    out[0] = mf;
+    out[1] = ms;
+  }
+}
+
+__global__ __launch_bounds__(OPT_THREADS) void rwalk_apply_kernel(MultiArgs a, const long* __restrict__ out_ptrs,
+                                                                  const float* __restrict__ out) {
+  const ChunkView c = chunk_view(a);
+  const float* p = c.row<const float>(0);
+  const float* f = c.row<const float>(1);
+  float* s = c.row<float>(2);
+  float* ck = c.row<float>(4);
+  float* imp = reinterpret_cast<float*>(out_ptrs[c.t]) + c.off;
+  float* opt = reinterpret_cast<float*>(out_ptrs[c.n + c.t]) + c.off;
+  const float mf = out[0], ms = out[1];
+  for (long i = threadIdx.x; i < c.cnt; i += OPT_THREADS) {
+#pragma clang fp contract(off)
+    const float pv = p[i], sv = s[i];
+    const double tf = mf == 0.f ? 0.0 : (double)f[i] / (double)mf;      // (a NaN max is not 0: it reaches the quotient)
+    const double tsc = ms == 0.f ? 0.0 : (double)sv / (double)ms;
+    imp[i] = (float)(tf + tsc);
+    opt[i] = pv;
+    s[i] = 0.5f * sv;
+    ck[i] = pv;
   }
 }
 
@@ -466,8 +648,8 @@ extern "C" int vilco_agem_project(const vilco_chunk_table* table, float* partial
   return vilco_launch_status();
 }
 
-extern "C" int vilco_optim_step(const vilco_optim_desc* d, void* stream) {
-  if (!d) return VILCO_ERR_BADARG;
+// the update launch of vilco_optim_step (rw null) and vilco_optim_step_rwalk
+static int optim_launch(const vilco_optim_desc* d, const RwalkArgs* rw, void* stream) {
   const int32_t kind = d->kind, ngroups = d->ngroups;
   MultiArgs a;
   if (!table_args(&d->table, kind == 1 ? 3 : 4, d->group, &a) || !d->group || !d->lr || !d->wd) return VILCO_ERR_BADARG;
@@ -483,10 +665,40 @@ extern "C" int vilco_optim_step(const vilco_optim_desc* d, void* stream) {
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const long* si = reinterpret_cast<const long*>(d->si_ptrs);
   const dim3 grid(d->table.nchunks), block(OPT_THREADS);
-  if (kind == 0 && si) hipLaunchKernelGGL(adamw_kernel<true>, grid, block, 0, s, a, h, d->norm_coef, d->chunk_amax, si);
+  if (rw && kind == 0) hipLaunchKernelGGL(adamw_rwalk_kernel, grid, block, 0, s, a, h, d->norm_coef, d->chunk_amax, si, *rw);
+  else if (rw) hipLaunchKernelGGL(sgd_rwalk_kernel, grid, block, 0, s, a, h, d->norm_coef, d->chunk_amax, si, *rw);
+  else if (kind == 0 && si) hipLaunchKernelGGL(adamw_kernel<true>, grid, block, 0, s, a, h, d->norm_coef, d->chunk_amax, si);
   else if (kind == 0) hipLaunchKernelGGL(adamw_kernel<false>, grid, block, 0, s, a, h, d->norm_coef, d->chunk_amax, si);
   else if (si) hipLaunchKernelGGL(sgd_kernel<true>, grid, block, 0, s, a, h, d->norm_coef, d->chunk_amax, si);
   else hipLaunchKernelGGL(sgd_kernel<false>, grid, block, 0, s, a, h, d->norm_coef, d->chunk_amax, si);
+  return vilco_launch_status();
+}
+
+extern "C" int vilco_optim_step(const vilco_optim_desc* d, void* stream) {
+  if (!d) return VILCO_ERR_BADARG;
+  return optim_launch(d, nullptr, stream);
+}
+
+extern "C" int vilco_optim_step_rwalk(const vilco_rwalk_step_desc* d, void* stream) {
+  if (!d) return VILCO_ERR_BADARG;
+  if (!d->optim.si_ptrs || !d->rw_ptrs || !d->tick) return VILCO_ERR_BADARG;
+  if (!(d->alpha > 0.f && d->alpha <= 1.f) || !(d->eps > 0.f) || d->delta_t < 1) return VILCO_ERR_BADARG;
+  const RwalkArgs rw{reinterpret_cast<const long*>(d->rw_ptrs), d->tick, d->alpha, d->eps, d->delta_t};
+  return optim_launch(&d->optim, &rw, stream);
+}
+
+extern "C" int vilco_rwalk_consolidate(const vilco_rwalk_desc* d, void* stream) {
+  if (!d) return VILCO_ERR_BADARG;
+  MultiArgs a;
+  if (!table_args(&d->table, 5, nullptr, &a) || d->table.n <= 0 || !d->out_ptrs || !d->partial || !d->out) return VILCO_ERR_BADARG;
+  if (!(d->eps > 0.f)) return VILCO_ERR_BADARG;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const int nchunks = d->table.nchunks;
+  if (nchunks == 0) return VILCO_OK;             // no element: no state to flush, no importance to write
+  const dim3 grid(nchunks), block(OPT_THREADS);
+  hipLaunchKernelGGL(rwalk_flush_kernel, grid, block, 0, s, a, d->eps, d->partial, nchunks);
+  hipLaunchKernelGGL(rwalk_finish_kernel, dim3(1), block, 0, s, d->partial, nchunks, d->out);
+  hipLaunchKernelGGL(rwalk_apply_kernel, grid, block, 0, s, a, reinterpret_cast<const long*>(d->out_ptrs), d->out);
   return vilco_launch_status();
 }
 

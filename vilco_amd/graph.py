@@ -22,10 +22,11 @@ through a table of the layers' addresses: stage 2 writes them after the capture)
 counts and learning rates (vilco_optim_desc.lr_dev), the narration memory bank and its ring word (csrc/ssl.hip: the update
 advances the word on the device by the number of narrated clips, which differs from batch to batch), and -- under Synaptic
 Intelligence -- the path integrals `omega`, which the captured update advances on every replay through its table of their
-addresses (vilco_optim_desc.si_ptrs; table and omegas are kept alive by the optimizer).
+addresses (vilco_optim_desc.si_ptrs; table and omegas are kept alive by the optimizer), or under RWalk its four states and the
+iteration word `rwalk_tick`, which the captured step advances and the update kernel reads (vilco_rwalk_step_desc).
 
 What is captured is what ran: graphs are keyed by the input shapes, task id, the identity / requires_grad of every
-parameter, the continual-learning method and BiC's split table with the addresses of its layers, and dropped when parameters were written from outside (load_state_dict, an eager optimizer step) or Synaptic Intelligence was attached / re-attached to the optimizer (a new task's omegas) -- cached
+parameter, the continual-learning method and BiC's split table with the addresses of its layers, and dropped when parameters were written from outside (load_state_dict, an eager optimizer step) or Synaptic Intelligence or RWalk was attached / re-attached to the optimizer (a new task's omegas; `si_gen` / `rwalk_gen`) -- cached
 operand planes and max|w| partials would be stale otherwise.  Steps the device half cannot run alone (distillation
 against host-side NumPy targets or in a batch without a cached clip, a BiC model whose split table the correction kernel
 does not take, narration SSL with its fused path switched off by VILCO_FUSED_SSL=0) fall back to the eager path.
@@ -245,8 +246,10 @@ class GraphedStep:
                                                           # captured forward reads operand planes packed before it
         # (a captured update re-packs its weights inside graph 1.)  The captured update launch holds the plan's tables, the
         # Synaptic-Intelligence table among them (or its absence): FusedOptimizer.attach_si drops the plans and advances si_gen,
-        # so a graph captured without SI is never replayed with it, nor with another task's omegas, nor the other way round
-        return ent['plans'] is self.optimizer._plans and ent['si_gen'] == self.optimizer.si_gen
+        # so a graph captured without SI is never replayed with it, nor with another task's omegas, nor the other way round.
+        # RWalk's tables and its tick word likewise: attach_rwalk advances rwalk_gen
+        opt = self.optimizer
+        return ent['plans'] is opt._plans and ent['si_gen'] == opt.si_gen and ent['rwalk_gen'] == opt.rwalk_gen
 
     # ------------------------------------------------------------------ capture
     def _capture(self, ent, inp, task_id):
@@ -367,7 +370,7 @@ class GraphedStep:
                 opt.step(clip_grad_l2norm=self.clip, lr_dev=self._lr_dev)
             for pl in opt._plans:            # the capture counted an update that did not run
                 pl['count'] -= 1
-            ent.update(opt_graph=g2, plans=opt._plans, si_gen=opt.si_gen)
+            ent.update(opt_graph=g2, plans=opt._plans, si_gen=opt.si_gen, rwalk_gen=opt.rwalk_gen)
         # the parameters the captured step reads: those that got a gradient, and frozen ones (the adapters' EMA copies are
         # neither: they are written in place after every iteration and only read at inference)
         ent['tracked'] = [p for p, g in zip(self.params, ent['grads']) if g is not None or not p.requires_grad]

@@ -12,6 +12,7 @@ reference driver MQ/train_cl.py:206-389 (+ load_best_checkpoint :31-40), written
       if another task follows: augment_classification(num_next_classes), EWC / MAS consolidation, NEW optimizer
           and scheduler                                             (:373-389)
       [cl_cfg.name 'si' (ours): si_begin_task before the epochs, consolidation right after them, before the reload]
+      [cl_cfg.name 'rwalk' (ours): rwalk_begin_task / consolidation where SI's are; rwalk_state.pt next to the memory pickle]
       [cl_cfg.name 'agem' (ours): once the memory holds clips, a reference gradient per iteration and the projection]
       [cl_cfg.name 'der' (ours): after the reload the new memory clips' logits are recorded; later steps replay them]
 
@@ -33,6 +34,7 @@ from .utils.train_utils import make_optimizer, make_scheduler, save_checkpoint, 
 
 
 DER_BANK_FILE = 'der_bank.pt'      # cl_cfg.name 'der': DERBank.state_dict(), written next to the memory pickle
+RWALK_STATE_FILE = 'rwalk_state.pt'      # cl_cfg.name 'rwalk': regularizers.rwalk_state_dict(), written next to the memory pickle
 
 
 def load_best_checkpoint(model, file_folder, file_name, current_task, gpu_id):
@@ -135,6 +137,34 @@ def _si_consolidate(cfg, model, optimizer):
     return {k: list(v) for k, v in reg.items()}
 
 
+def _rwalk_check(cfg, start_epoch, model=None, start_task=0, ckpt_folder=None):
+    """cl_cfg.name == 'rwalk' -> its options (regularizers.rwalk_options, validated here), else None.  A resume inside a task is
+    refused as for SI: omega and theta_ck are per-task state that checkpoints do not carry.  The Fisher average and the scores
+    outlive a task: a resume at task k > 0 reads them from RWALK_STATE_FILE in `ckpt_folder` -- or raises."""
+    if cfg['cl_cfg']['name'] != 'rwalk':
+        return None
+    opts = regularizers.rwalk_options(cfg['cl_cfg'])
+    if start_epoch > 0:
+        raise ValueError("cl_cfg.name 'rwalk' cannot resume inside a task (start_epoch = %d): the path integral of the epochs "
+                         "already trained is not checkpointed; resume at a task boundary" % start_epoch)
+    if start_task > 0:
+        path = None if ckpt_folder is None else os.path.join(ckpt_folder, RWALK_STATE_FILE)
+        if path is None or not os.path.exists(path):
+            raise ValueError("cl_cfg.name 'rwalk' resumed at task %d needs the Fisher average and the path scores of the earlier "
+                             "tasks (%s, written next to the memory pickle after every task): none found"
+                             % (start_task, path or RWALK_STATE_FILE))
+        regularizers.load_rwalk_state(model, torch.load(path, map_location='cpu', weights_only=False), device=model.device)
+    return opts
+
+
+def _rwalk_consolidate(cfg, model, optimizer, opts):
+    """RWalk's consolidation, where SI's runs: at the end of the task's training, before the best checkpoint is reloaded, with
+    no pass over the data.  The caller installs the returned dictionary after the reload.  (`cfg` is not read: the signature
+    is _si_consolidate's.)"""
+    reg = regularizers.on_task_rwalk_update(model, optimizer, eps=opts['eps'])
+    return {k: list(v) for k, v in reg.items()}
+
+
 def _coda_begin(cfg, model, train_stream, start_task, reducer):
     """CODA-Prompt at the start of run_episodes -> whether the run uses it.  cl_cfg['coda_tasks'] None is filled from the stream;
     a model that holds a CodaPrompt must divide its pool among as many tasks as the stream has; the first task's components
@@ -180,6 +210,12 @@ def run_episodes(cfg, model, train_stream, validate=None, ckpt_folder=None, gpu_
     with train_enable=True gives DER++ (the memory clips' labels are in the detection loss); with train_enable=False no
     memory clip reaches a batch and the term is zero.  With ckpt_folder the bank is written next to the memory pickle
     (DER_BANK_FILE) and start_task > 0 reads it back -- or raises.  Not with a reducer, nor with type_sampling 'icarl'.
+    cl_cfg.name 'rwalk' (ours; cl_methods/regularizers.py): `rwalk_begin_task` before every task's epochs (where SI's is), the
+    consolidation right after them, before the best checkpoint is reloaded.  The Fisher average and the path scores outlive a
+    task: with ckpt_folder they are written next to the memory pickle at every task boundary (RWALK_STATE_FILE, with the
+    importance dictionary the task's checkpoints predate) and start_task > 0 reads them back -- or raises; start_epoch > 0
+    raises as for 'si'.  Reading the file REPLACES model.reg_params, also a dictionary the caller restored from a checkpoint
+    before the call.
     cl_cfg.prompt_type 'coda' (ours; cl_methods/coda.py): cl_cfg['coda_tasks'] None is filled from the stream's task count
     before the model is used, and `model.prompt.set_task(j)` runs at the start of task j -- after the previous task's checkpoint
     reload and head growth, before task j's optimizer is built (its rows are new values: their moments start at zero).  Not
@@ -190,6 +226,7 @@ def run_episodes(cfg, model, train_stream, validate=None, ckpt_folder=None, gpu_
     is_main = int(os.environ.get("LOCAL_RANK", "0")) == 0
     imp_opts = regularizers.importance_options(cfg['cl_cfg'])      # a bad value fails here, not after the first task
     use_si = _si_check(cfg, start_epoch)
+    rwalk = _rwalk_check(cfg, start_epoch, model, start_task, ckpt_folder)
     use_agem = agem_mod.check_supported(cfg['cl_cfg']['name'], reducer)
     use_der = der_mod.check_supported(cfg['cl_cfg']['name'], reducer, type_sampling=cfg['cl_cfg'].get('type_sampling'))
     if use_der:
@@ -230,6 +267,8 @@ def run_episodes(cfg, model, train_stream, validate=None, ckpt_folder=None, gpu_
         ck_name = 'best_task_{:03d}_performance.pth.tar'.format(j)
         if use_si:
             regularizers.si_begin_task(model, optimizer)      # the head has grown, this task's optimizer exists
+        if rwalk is not None:
+            regularizers.rwalk_begin_task(model, optimizer, **rwalk)      # F and s carried on their prefix, tick = 0
         agem = None
         if use_agem and train_stream.memory:
             mem_sampler = agem_mod.MemorySampler(train_stream.memory, cfg['cl_cfg'].get('agem_batch', loader.batch_size),
@@ -266,6 +305,8 @@ def run_episodes(cfg, model, train_stream, validate=None, ckpt_folder=None, gpu_
                                        # validates and writes the checkpoint
         entry['best_metric'], entry['best_epoch'] = best, best_epoch
         si_reg = _si_consolidate(cfg, model, optimizer) if use_si and num_next is not None else None
+        if rwalk is not None and num_next is not None:
+            si_reg = _rwalk_consolidate(cfg, model, optimizer, rwalk)
 
         # replay memory for the next task (train_cl.py:343-361)
         n_cls = model.cls_head.cls_head.conv.out_channels
@@ -278,6 +319,8 @@ def run_episodes(cfg, model, train_stream, validate=None, ckpt_folder=None, gpu_
                 os.makedirs(ckpt_folder, exist_ok=True)
                 with open(os.path.join(ckpt_folder, cfg['cl_cfg']['path_memory']), 'wb') as h:
                     pickle.dump(model.memory, h)
+                if rwalk is not None and num_next is not None:      # F and the halved s: what task j + 1 starts from
+                    torch.save(regularizers.rwalk_state_dict(model), os.path.join(ckpt_folder, RWALK_STATE_FILE))
             _barrier(reducer)          # the checkpoint rank 0 wrote is complete before anybody reads it
             # EVERY rank reloads the task's best state (train_cl.py:363 runs on every rank): replicas that kept their
             # last-epoch weights would never meet the others again -- the gradient average does not re-align weights
@@ -302,7 +345,7 @@ def run_episodes(cfg, model, train_stream, validate=None, ckpt_folder=None, gpu_
             elif cfg['cl_cfg']['name'] == 'mas':
                 model.reg_params = regularizers.on_task_update(loader, gpu_id, optimizer, model, kind='mas', group=getattr(reducer, 'group', None), data_parallel=reducer is not None,
                                                                **imp_opts)
-            elif use_si:
+            elif use_si or rwalk is not None:
                 model.reg_params = si_reg      # (the reload above put the checkpoint's older dictionary back)
             if use_coda:
                 model.prompt.set_task(j + 1)   # the next task's components, before its optimizer exists
@@ -347,6 +390,9 @@ def run_episodes_bic(cfg, model, train_stream, validate=None, ckpt_folder=None, 
     from .cl_methods import coda as coda_mod
     if cfg['cl_cfg'].get('prompt_pool'):
         coda_mod.check_supported(cfg['cl_cfg'].get('prompt_type', 'l2p'), driver='run_episodes_bic')      # CODA-Prompt: run_episodes only
+    if cfg['cl_cfg']['name'] == 'rwalk':
+        raise ValueError("cl_cfg.name 'rwalk' is not supported by run_episodes_bic: only run_episodes and run_episodes_nlq keep "
+                         "its state and consolidate it")
     optimizer = make_optimizer(model, cfg['opt'])
 
     def make_graph(opt):
@@ -501,6 +547,7 @@ def run_episodes_nlq(cfg, model, train_stream, val_stream, evaluator, ckpt_folde
     is_main = int(os.environ.get("LOCAL_RANK", "0")) == 0
     imp_opts = regularizers.importance_options(cfg['cl_cfg'])
     use_si = _si_check(cfg, start_epoch)
+    rwalk = _rwalk_check(cfg, start_epoch, model, start_task, ckpt_folder)
     hb = cfg['opt']["backbone_lr_weight"] != 1
 
     def new_optimizer():
@@ -543,6 +590,8 @@ def run_episodes_nlq(cfg, model, train_stream, val_stream, evaluator, ckpt_folde
         ck_name = 'Best_task_{:02d}.pth.tar'.format(j)
         if use_si:
             regularizers.si_begin_task(model, optimizer)      # a new optimizer per task: attached again
+        if rwalk is not None:
+            regularizers.rwalk_begin_task(model, optimizer, **rwalk)
         for epoch in range(start_epoch, max_epochs):
             sampler = getattr(loader, 'sampler', None)
             if sampler is not None and hasattr(sampler, 'set_epoch'):
@@ -575,6 +624,8 @@ def run_episodes_nlq(cfg, model, train_stream, val_stream, evaluator, ckpt_folde
                 _barrier(reducer)
         entry['best_R1'], entry['best_epoch'] = tracker.best, tracker.best_epoch
         si_reg = _si_consolidate(cfg, model, optimizer) if use_si and num_next is not None else None
+        if rwalk is not None and num_next is not None:
+            si_reg = _rwalk_consolidate(cfg, model, optimizer, rwalk)
         if memory_size != 0:
             model.add_samples_to_mem(val_stream, data, 'ALL' if memory_size == 'ALL' else memory_size // 13)
         train_stream.memory = model.memory
@@ -584,6 +635,8 @@ def run_episodes_nlq(cfg, model, train_stream, val_stream, evaluator, ckpt_folde
                 os.makedirs(ckpt_folder, exist_ok=True)
                 with open(os.path.join(ckpt_folder, cfg['cl_cfg']['path_memory']), 'wb') as h:
                     pickle.dump(model.memory, h)
+                if rwalk is not None and num_next is not None:
+                    torch.save(regularizers.rwalk_state_dict(model), os.path.join(ckpt_folder, RWALK_STATE_FILE))
             _barrier(reducer)
             model = load_best_checkpoint(model, ckpt_folder, ck_name, j, gpu_id)
         entry['final_R1'] = validate('final', j, max_epochs - 1)
@@ -593,7 +646,7 @@ def run_episodes_nlq(cfg, model, train_stream, val_stream, evaluator, ckpt_folde
                 model.reg_params = regularizers.on_task_update(loader, gpu_id, optimizer, model, kind=cfg['cl_cfg']['name'],
                                                                group=getattr(reducer, 'group', None), data_parallel=reducer is not None,
                                                                **imp_opts)
-            elif use_si:
+            elif use_si or rwalk is not None:
                 model.reg_params = si_reg
             optimizer = new_optimizer()
             scheduler = tu.make_scheduler(optimizer, cfg['opt'], iters_per_epoch)

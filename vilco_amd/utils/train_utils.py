@@ -91,6 +91,9 @@ class FusedOptimizer(optim.Optimizer):
         self.last_grad_norm = None      # device tensor [norm, clip coef] of the last step
         self._si = None                 # {id(param): (param, omega)} while Synaptic Intelligence is attached
         self.si_gen = 0                 # advanced by every attach_si(): a captured step holds the table of ONE attachment
+        self._rwalk = None              # {'states': {id(param): (param, state dict)}, 'alpha', 'delta_t', 'eps'} while RWalk is attached
+        self.rwalk_tick = None          # device int32 [1]: iterations since attach_rwalk()
+        self.rwalk_gen = 0              # advanced by every attach_rwalk()
 
     def attach_si(self, omegas):
         """Synaptic Intelligence (cl_methods/regularizers.py): from now on every update also advances the path integral
@@ -103,9 +106,47 @@ class FusedOptimizer(optim.Optimizer):
             for q, om in omegas.items():
                 if not (om.is_cuda and om.dtype == torch.float32 and om.is_contiguous() and om.numel() == q.numel()):
                     raise RuntimeError("attach_si: omega must be a contiguous fp32 device tensor with the parameter's element count")
+        if omegas is not None and self._rwalk is not None:
+            raise RuntimeError("attach_si: RWalk is attached to this optimizer; the update kernel tracks one of the two")
         self._flush_steps()
         self._si = None if omegas is None else {id(q): (q, om) for q, om in omegas.items()}
         self.si_gen += 1
+
+    def attach_rwalk(self, states, alpha=0.9, delta_t=10, eps=1e-8):
+        """RWalk (cl_methods/regularizers.py): from now on every update of the parameters in `states` ({param: {'fisher',
+        'score', 'omega', 'theta_ck'}}, fp32 tensors of the parameter's element count) also advances the Fisher moving average
+        and the path integral, and every `delta_t` iterations closes the interval into the score, inside the update kernel
+        (vilco_optim_step_rwalk).  None, or an empty dictionary (nothing to track), detaches.  `rwalk_tick` -- ONE device word, the iterations since this attachment -- starts
+        at zero; step() advances it once per iteration with a device add that a captured step replays.  As attach_si: the address
+        tables are built with the step plan, one per pass (a parameter listed k times takes every update k times), cached plans
+        are dropped, `rwalk_gen` advances so that a GraphedStep recaptures, the optimizer keeps the states alive and state_dict()
+        does not hold them.  Not together with attach_si."""
+        if states is not None:
+            if self._si is not None:
+                raise RuntimeError("attach_rwalk: Synaptic Intelligence is attached to this optimizer; the update kernel tracks one of the two")
+            if not (0.0 < float(alpha) <= 1.0) or not float(eps) > 0.0 or int(delta_t) != delta_t or int(delta_t) < 1:
+                raise ValueError("attach_rwalk: alpha in (0, 1], eps > 0 and an integer delta_t >= 1, got %r, %r, %r" % (alpha, eps, delta_t))
+            for q, st in states.items():
+                for key in ('fisher', 'score', 'omega', 'theta_ck'):
+                    t = st[key]
+                    if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == q.numel()):
+                        raise RuntimeError("attach_rwalk: %s must be a contiguous fp32 device tensor with the parameter's element count" % key)
+                    if t.device != q.device:
+                        raise RuntimeError("attach_rwalk: %s lives on %s, its parameter on %s" % (key, t.device, q.device))
+            if len({q.device for q in states}) > 1:
+                raise RuntimeError("attach_rwalk: the tracked parameters live on more than one device; the tick is one word on one of them")
+        self._flush_steps()
+        self.rwalk_gen += 1
+        if not states:
+            # None, or nothing to track: detached.  The update kernel reads the tick word in every block, tracked tensor or not,
+            # so an attachment always owns a DEVICE word; with no state tensor there is no device to put one on, and nothing
+            # to advance -- the plain update runs
+            self._rwalk, self.rwalk_tick = None, None
+            return
+        dev = next(iter(states.values()))['omega'].device      # a HIP device: checked above
+        self.rwalk_tick = torch.zeros(1, dtype=torch.int32, device=dev)
+        self._rwalk = dict(states={id(q): (q, st) for q, st in states.items()}, alpha=float(alpha), delta_t=int(delta_t), eps=float(eps))
+
     def _passes(self):
         """[(param, group index)] lists; a parameter listed k times (the adapter aliases of train_utils.py:108-113)
         is stepped k times per iteration like torch.optim would: k-th occurrences go to pass k."""
@@ -136,10 +177,16 @@ class FusedOptimizer(optim.Optimizer):
         if self._si is not None:        # address of every tensor's omega in plan order, 0 = not regularised
             si = torch.tensor([self._si[id(p)][1].data_ptr() if id(p) in self._si else 0 for p, _ in items],
                               dtype=torch.int64, device=dev)
+        rw = None
+        if self._rwalk is not None:     # omega's addresses in si's place, and the [3, n] table of fisher, score, theta_ck
+            sts = [self._rwalk['states'].get(id(p), (None, None))[1] for p, _ in items]
+            si = torch.tensor([0 if st is None else st['omega'].data_ptr() for st in sts], dtype=torch.int64, device=dev)
+            rw = torch.tensor([[0 if st is None else st[key].data_ptr() for st in sts] for key in ('fisher', 'score', 'theta_ck')],
+                              dtype=torch.int64, device=dev)
         chunks = ops.ChunkPlan([p.numel() for p, _ in items], dev)
         first = chunks.first
         amax = torch.empty(max(chunks.nchunks, 1), dtype=torch.float32, device=dev)
-        return dict(items=items, chunks=chunks, first=first, amax=amax, si=si,
+        return dict(items=items, chunks=chunks, first=first, amax=amax, si=si, rw=rw,
                     amax_views=[amax[first[i]:first[i + 1]] for i in range(len(items))],
                     group=torch.tensor([gi for _, gi in items], dtype=torch.int32, device=dev),
                     partial=torch.empty(max(chunks.nchunks, 1), dtype=torch.float32, device=dev),
@@ -243,6 +290,8 @@ class FusedOptimizer(optim.Optimizer):
         emitted = {}     # id(p) -> (p, partials view, count) of the LAST pass that wrote p
         coef = None      # clip coefficient of pass 0, reused by every pass: clip_grad_norm_ scales p.grad in place
                          # (train_utils.py:343-347), so a parameter listed twice is stepped twice with the CLIPPED gradient
+        if self._rwalk is not None and self._plans:
+            self.rwalk_tick.add_(1)    # once per iteration, whatever the number of passes; captured with the step like tstep's add
         for k, (plan, ptrs) in enumerate(zip(self._plans, tables)):
             items = plan['items']
             table = plan['chunks'].table(ptrs, 4)
@@ -266,7 +315,16 @@ class FusedOptimizer(optim.Optimizer):
                                chunk_amax=plan['amax'].data_ptr() if OPT_AMAX else None,
                                lr_dev=None if lr_dev is None else lr_dev.data_ptr(),
                                si_ptrs=None if plan['si'] is None else plan['si'].data_ptr())
-            _lib.check(lib.vilco_optim_step(C.byref(d), stream))
+            if plan['rw'] is None:
+                _lib.check(lib.vilco_optim_step(C.byref(d), stream))
+            else:
+                rwk = self._rwalk
+                if self.rwalk_tick.device != items[0][0].device:      # every block of the launch dereferences it
+                    raise RuntimeError("FusedOptimizer: the RWalk tick lives on %s, the stepped parameters on %s"
+                                       % (self.rwalk_tick.device, items[0][0].device))
+                rd = _lib.RwalkStepDesc(optim=d, rw_ptrs=plan['rw'].data_ptr(), tick=self.rwalk_tick.data_ptr(), alpha=rwk['alpha'],
+                                        eps=rwk['eps'], delta_t=rwk['delta_t'])
+                _lib.check(lib.vilco_optim_step_rwalk(C.byref(rd), stream))
             first = plan['first']
             for i, (p, _) in enumerate(items):
                 if p.dim() >= 2 and OPT_AMAX:    # matrices: the tensors that get packed
@@ -394,7 +452,7 @@ def train_one_epoch(train_loader, model, optimizer, scheduler, curr_epoch, n_gpu
         # loss + lambda * sum_i sum_p F_i (theta*_i - theta)^2 (EWC.py:6-22 / MAS.py:5-21): value added to the
         # reported loss, gradient added straight into p.grad.  The penalty is the same on every rank, so adding it
         # after the gradient average equals averaging it.
-        last_pen[0] = regularizers.apply_penalty(model, reg_lambda, kind=cl_name) if cl_name in ('ewc', 'mas', 'si') else None
+        last_pen[0] = regularizers.apply_penalty(model, reg_lambda, kind=cl_name) if cl_name in ('ewc', 'mas', 'si', 'rwalk') else None
 
     def project_and_penalty():
         agem.project()          # the task batch's gradient against the memory batch's, on the pointers p.grad holds now
