@@ -275,18 +275,29 @@ def test_a_model_without_regularised_parameters_attaches_nothing():
 
 def test_driver_refuses_the_resumes_it_cannot_serve(tmp_path):
     from vilco_amd import train_cl
+    from vilco_amd.cl_methods import hooks
+
+    def rwalk_check(cfg, start_epoch, model=None, start_task=0, ckpt_folder=None):
+        """RWalk's hook through begin_run -> its options; None when cl_cfg names another method"""
+        if cfg['cl_cfg']['name'] != 'rwalk':
+            return None
+        hook = hooks.RWalk(cfg)
+        hook.begin_run(model, None, start_task, start_epoch, ckpt_folder)
+        return hook.opts
     cfg = {'cl_cfg': {'name': 'rwalk'}}
-    assert train_cl._rwalk_check(cfg, 0) == dict(alpha=0.9, delta_t=10, eps=1e-8)
-    assert train_cl._rwalk_check({'cl_cfg': {'name': 'si'}}, 3) is None
+    assert [type(h) for h in hooks.make_hooks(cfg, 'run_episodes')] == [hooks.RWalk]
+    assert rwalk_check(cfg, 0) == dict(alpha=0.9, delta_t=10, eps=1e-8)
+    assert rwalk_check({'cl_cfg': {'name': 'si'}}, 3) is None
+    assert not any(isinstance(h, hooks.RWalk) for h in hooks.make_hooks({'cl_cfg': {'name': 'si'}}, 'run_episodes'))
     with pytest.raises(ValueError, match="start_epoch"):
-        train_cl._rwalk_check(cfg, 1)
+        rwalk_check(cfg, 1)
     with pytest.raises(ValueError, match="rwalk_delta_t"):
-        train_cl._rwalk_check({'cl_cfg': {'name': 'rwalk', 'rwalk_delta_t': 0}}, 0)
+        rwalk_check({'cl_cfg': {'name': 'rwalk', 'rwalk_delta_t': 0}}, 0)
     # a resume at a later task needs the Fisher average and the scores of the earlier ones
     assert train_cl.RWALK_STATE_FILE == 'rwalk_state.pt'
     for folder in (None, str(tmp_path)):
         with pytest.raises(ValueError, match="rwalk_state.pt"):
-            train_cl._rwalk_check(cfg, 0, model=_Stub(), start_task=1, ckpt_folder=folder)
+            rwalk_check(cfg, 0, model=_Stub(), start_task=1, ckpt_folder=folder)
     with pytest.raises(ValueError, match="rwalk_state.pt"):
         train_cl.run_episodes(cfg, _Stub(), None, ckpt_folder=str(tmp_path), start_task=1)
     with pytest.raises(ValueError, match="start_epoch"):
@@ -303,7 +314,7 @@ def test_driver_refuses_the_resumes_it_cannot_serve(tmp_path):
     torch.save(sd, os.path.join(str(tmp_path), 'rwalk_state.pt'))
     m2 = _Stub()
     m2.device = torch.device('cpu')
-    assert train_cl._rwalk_check(cfg, 0, model=m2, start_task=1, ckpt_folder=str(tmp_path))['delta_t'] == 10
+    assert rwalk_check(cfg, 0, model=m2, start_task=1, ckpt_folder=str(tmp_path))['delta_t'] == 10
     assert torch.equal(m2.rwalk_state['body.weight']['fisher'], m.rwalk_state['body.weight']['fisher'])
     assert torch.equal(m2.rwalk_state['body.weight']['score'], m.rwalk_state['body.weight']['score'])
     with pytest.raises(ValueError):

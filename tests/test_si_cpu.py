@@ -108,11 +108,17 @@ def test_si_is_not_in_the_config_defaults():
 
 
 def test_resume_inside_a_task_is_refused():
-    from vilco_amd import train_cl
+    from vilco_amd.cl_methods import hooks
+
+    def si_check(cfg, start_epoch):
+        """the run's hooks through begin_run (no model, no stream) -> does the run use SI's?"""
+        made = hooks.make_hooks(cfg, 'run_episodes')
+        hooks.each(made, 'begin_run', None, None, 0, start_epoch)
+        return any(type(h) is hooks.SI for h in made)
     cfg = {'cl_cfg': {'name': 'si'}}
-    assert train_cl._si_check(cfg, 0) is True and train_cl._si_check({'cl_cfg': {'name': 'mas'}}, 3) is False
+    assert si_check(cfg, 0) is True and si_check({'cl_cfg': {'name': 'mas'}}, 3) is False
     with pytest.raises(ValueError, match="start_epoch"):
-        train_cl._si_check(cfg, 1)
+        si_check(cfg, 1)
 
 
 # ------------------------------------------------------------------------------------------------------- C ABI

@@ -25,6 +25,7 @@ import random
 import torch
 
 from .. import ops
+from . import hooks      # (which imports this module: both use the other's names in calls only)
 
 
 class MemorySampler:
@@ -107,13 +108,14 @@ class AGEM:
 
 
 def check_supported(cl_name, reducer=None, driver='run_episodes'):
-    """the combinations this implementation refuses, by name: data parallelism (each of the two backward passes of an
+    """the combinations this implementation refuses (hooks.SUPPORT), by name: data parallelism (each of the two backward passes of an
     iteration would need a gradient exchange of its own, and no multi-GPU node has run it) and the BiC / NLQ drivers"""
     if cl_name != 'agem':
         return False
-    if driver != 'run_episodes':
+    drivers, takes_reducer = hooks.SUPPORT['agem']
+    if driver not in drivers:
         raise ValueError("cl_cfg.name 'agem' is not supported by %s: only run_episodes projects gradients" % driver)
-    if reducer is not None:
+    if reducer is not None and not takes_reducer:
         raise ValueError("cl_cfg.name 'agem' does not support data parallelism (reducer is not None): the reference pass "
                          "and the task step would each need their own gradient exchange")
     return True

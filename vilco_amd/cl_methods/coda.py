@@ -18,6 +18,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import ops
+from . import hooks      # (which imports this module: both use the other's names in calls only)
 
 
 def check_supported(prompt_type, reducer=None, driver='run_episodes'):
@@ -25,9 +26,10 @@ def check_supported(prompt_type, reducer=None, driver='run_episodes'):
     (`set_task`) is called by `run_episodes` only, and no multi-GPU node has run it."""
     if prompt_type != 'coda':
         return False
-    if driver != 'run_episodes':
+    drivers, takes_reducer = hooks.SUPPORT['coda']
+    if driver not in drivers:
         raise ValueError("cl_cfg.prompt_type 'coda' is not wired into %s: only run_episodes moves the prompt's task window" % driver)
-    if reducer is not None:
+    if reducer is not None and not takes_reducer:
         raise ValueError("cl_cfg.prompt_type 'coda' has not been run with a reducer (data parallel): refused")
     return True
 

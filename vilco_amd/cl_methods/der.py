@@ -19,6 +19,8 @@ dropped from the memory loses it.  A batch row has no record -- address 0 in the
 or its length in this step differs from the recorded one (a re-cropped long clip: counted in `DERBank.skipped`)."""
 import torch
 
+from . import hooks      # (which imports this module: both use the other's names in calls only)
+
 
 def clip_key(video):
     return video['video_id']
@@ -176,13 +178,14 @@ def der_term(logits, level_row, level_T, valid_lens, records, alpha):
 
 
 def check_supported(cl_name, reducer=None, driver='run_episodes', type_sampling=None):
-    """the combinations this implementation refuses, by name: the BiC / NLQ drivers, data parallelism, and iCaRL's target
+    """the combinations this implementation refuses, by name: the BiC / NLQ drivers and data parallelism (hooks.SUPPORT), and iCaRL's target
     cache (type_sampling 'icarl' hands every step the previous model's outputs, which a 'der' step has no term for)"""
     if cl_name != 'der':
         return False
-    if driver != 'run_episodes':
+    drivers, takes_reducer = hooks.SUPPORT['der']
+    if driver not in drivers:
         raise ValueError("cl_cfg.name 'der' is not supported by %s: only run_episodes records the memory's logits" % driver)
-    if reducer is not None:
+    if reducer is not None and not takes_reducer:
         raise ValueError("cl_cfg.name 'der' does not support data parallelism (reducer is not None): the records live on one "
                          "rank's device and no multi-GPU node has run it")
     if type_sampling == 'icarl':

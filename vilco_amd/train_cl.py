@@ -11,10 +11,10 @@ reference driver MQ/train_cl.py:206-389 (+ load_best_checkpoint :31-40), written
       reload the task's best checkpoint, final validation           (:363-365)
       if another task follows: augment_classification(num_next_classes), EWC / MAS consolidation, NEW optimizer
           and scheduler                                             (:373-389)
-      [cl_cfg.name 'si' (ours): si_begin_task before the epochs, consolidation right after them, before the reload]
-      [cl_cfg.name 'rwalk' (ours): rwalk_begin_task / consolidation where SI's are; rwalk_state.pt next to the memory pickle]
-      [cl_cfg.name 'agem' (ours): once the memory holds clips, a reference gradient per iteration and the projection]
-      [cl_cfg.name 'der' (ours): after the reload the new memory clips' logits are recorded; later steps replay them]
+
+A continual-learning method acts at six points of that loop -- begin_run, begin_task, end_training, save_state, after_reload,
+before_next_task: cl_methods/hooks.py names them, holds one class per method (EWC / MAS, SI, RWalk, A-GEM, DER, the CODA task
+switch) and the table of which method runs in which driver (hooks.SUPPORT).  The drivers call the points and know no method.
 
 What is ours rather than the reference's: the stream is any iterable with QILSetTask's contract
 (`(data, loader, num_next_classes)` per task, a `.memory` attribute; utils/cl_stream.py has an in-memory one --
@@ -29,12 +29,8 @@ import pickle
 import numpy as np
 import torch
 
-from .cl_methods import regularizers
+from .cl_methods.hooks import DER_BANK_FILE, RWALK_STATE_FILE, each, make_hooks  # noqa: F401
 from .utils.train_utils import make_optimizer, make_scheduler, save_checkpoint, train_one_epoch
-
-
-DER_BANK_FILE = 'der_bank.pt'      # cl_cfg.name 'der': DERBank.state_dict(), written next to the memory pickle
-RWALK_STATE_FILE = 'rwalk_state.pt'      # cl_cfg.name 'rwalk': regularizers.rwalk_state_dict(), written next to the memory pickle
 
 
 def load_best_checkpoint(model, file_folder, file_name, current_task, gpu_id):
@@ -117,73 +113,27 @@ def make_mq_validate(cfg, val_stream, evaluator, retrieval_eval=None, idx_classe
     return validate
 
 
-def _si_check(cfg, start_epoch):
-    """cl_cfg.name == 'si'?  A resume inside a task is refused: the path integral of the epochs already trained is per-task
-    state (model.si_state) that checkpoints do not carry."""
-    use_si = cfg['cl_cfg']['name'] == 'si'
-    if use_si:
-        regularizers.si_xi(cfg['cl_cfg'])
-        if start_epoch > 0:
-            raise ValueError("cl_cfg.name 'si' cannot resume inside a task (start_epoch = %d): the path integral of the epochs "
-                             "already trained is not checkpointed; resume at a task boundary" % start_epoch)
-    return use_si
-
-
-def _si_consolidate(cfg, model, optimizer):
-    """Synaptic Intelligence's consolidation, called where the task's training ends: from the state the path integral led
-    to, BEFORE the best checkpoint is reloaded, without a pass over the data (EWC / MAS consolidate after the reload, over
-    the task's loader).  The caller installs the returned dictionary after the reload, which restores the checkpoint's."""
-    reg = regularizers.on_task_si_update(model, optimizer, xi=regularizers.si_xi(cfg['cl_cfg']))
-    return {k: list(v) for k, v in reg.items()}
-
-
-def _rwalk_check(cfg, start_epoch, model=None, start_task=0, ckpt_folder=None):
-    """cl_cfg.name == 'rwalk' -> its options (regularizers.rwalk_options, validated here), else None.  A resume inside a task is
-    refused as for SI: omega and theta_ck are per-task state that checkpoints do not carry.  The Fisher average and the scores
-    outlive a task: a resume at task k > 0 reads them from RWALK_STATE_FILE in `ckpt_folder` -- or raises."""
-    if cfg['cl_cfg']['name'] != 'rwalk':
+def _make_graph(use_graph, cfg, model, optimizer, reducer=None):
+    """a fresh GraphedStep for `optimizer` (new parameters, new optimizer: an old task's graphs are dropped), or None"""
+    if not use_graph:
         return None
-    opts = regularizers.rwalk_options(cfg['cl_cfg'])
-    if start_epoch > 0:
-        raise ValueError("cl_cfg.name 'rwalk' cannot resume inside a task (start_epoch = %d): the path integral of the epochs "
-                         "already trained is not checkpointed; resume at a task boundary" % start_epoch)
-    if start_task > 0:
-        path = None if ckpt_folder is None else os.path.join(ckpt_folder, RWALK_STATE_FILE)
-        if path is None or not os.path.exists(path):
-            raise ValueError("cl_cfg.name 'rwalk' resumed at task %d needs the Fisher average and the path scores of the earlier "
-                             "tasks (%s, written next to the memory pickle after every task): none found"
-                             % (start_task, path or RWALK_STATE_FILE))
-        regularizers.load_rwalk_state(model, torch.load(path, map_location='cpu', weights_only=False), device=model.device)
-    return opts
+    from .graph import GraphedStep
+    return GraphedStep(model, optimizer, clip_grad_l2norm=cfg['train_cfg']['clip_grad_l2norm'], reducer=reducer)
 
 
-def _rwalk_consolidate(cfg, model, optimizer, opts):
-    """RWalk's consolidation, where SI's runs: at the end of the task's training, before the best checkpoint is reloaded, with
-    no pass over the data.  The caller installs the returned dictionary after the reload.  (`cfg` is not read: the signature
-    is _si_consolidate's.)"""
-    reg = regularizers.on_task_rwalk_update(model, optimizer, eps=opts['eps'])
-    return {k: list(v) for k, v in reg.items()}
-
-
-def _coda_begin(cfg, model, train_stream, start_task, reducer):
-    """CODA-Prompt at the start of run_episodes -> whether the run uses it.  cl_cfg['coda_tasks'] None is filled from the stream;
-    a model that holds a CodaPrompt must divide its pool among as many tasks as the stream has; the first task's components
-    are (re)drawn -- `set_task(start_task)`, which for task 0 repeats what construction did, bit for bit."""
-    from .cl_methods import coda as coda_mod
-    cl_cfg = cfg['cl_cfg']
-    if not (cl_cfg.get('prompt_pool') and coda_mod.check_supported(cl_cfg.get('prompt_type', 'l2p'), reducer)):
-        return False
-    if cl_cfg.get('coda_tasks') is None:
-        cl_cfg['coda_tasks'] = int(train_stream.num_tasks)
-    prompt = getattr(model, 'prompt', None)
-    if not isinstance(prompt, coda_mod.CodaPrompt):
-        raise ValueError("cl_cfg.prompt_type 'coda': the model holds no CodaPrompt (build it with cl_cfg.coda_tasks = %d)"
-                         % cl_cfg['coda_tasks'])
-    if prompt.n_tasks < train_stream.num_tasks:
-        raise ValueError("cl_cfg.prompt_type 'coda': the pool is divided among %d tasks, the stream has %d"
-                         % (prompt.n_tasks, train_stream.num_tasks))
-    prompt.set_task(start_task)
-    return True
+def _save_memory_and_reload(cfg, model, hooks, j, ckpt_folder, ck_name, gpu_id, is_main=True, reducer=None):
+    """With a folder: the main rank pickles the replay memory and lets the methods write their state next to it (save_state),
+    then EVERY rank reloads the task's best state (train_cl.py:363 runs on every rank): replicas that kept their last-epoch
+    weights would never meet the others again -- the gradient average does not re-align weights.  -> the model"""
+    if ckpt_folder is None:
+        return model
+    if is_main:
+        os.makedirs(ckpt_folder, exist_ok=True)
+        with open(os.path.join(ckpt_folder, cfg['cl_cfg']['path_memory']), 'wb') as h:
+            pickle.dump(model.memory, h)
+        each(hooks, 'save_state', j, model, ckpt_folder)
+    _barrier(reducer)          # the checkpoint rank 0 wrote is complete before anybody reads it
+    return load_best_checkpoint(model, ckpt_folder, ck_name, j, gpu_id)
 
 
 def run_episodes(cfg, model, train_stream, validate=None, ckpt_folder=None, gpu_id=0, start_task=0, start_epoch=0,
@@ -195,59 +145,15 @@ def run_episodes(cfg, model, train_stream, validate=None, ckpt_folder=None, gpu_
     collectives): inside the epoch loop only the main rank calls it (train_cl.py:283), the others wait at a barrier.
     use_graph: replay the iterations as hipGraphs (vilco_amd/graph.py; a fresh GraphedStep per optimizer, i.e. per task).
     keep_history: keep every iteration's loss dict (device scalars) in the log; off for long runs.
-    cl_cfg.name 'agem' (ours; cl_methods/agem.py): from the first task that finds `train_stream.memory` non-empty, every
-    iteration takes a reference gradient on a batch of cl_cfg['agem_batch'] (default: the loader's batch size) memory clips
-    -- drawn by a MemorySampler seeded with cl_cfg['agem_seed'] (default: the stream's seed) -- and projects the task
-    batch's gradient against it before the clip and the update; before that, training is plain.  A fresh AGEM per task;
-    with keep_history the task's log entry gets 'agem' = [out, ...], one device tensor {g.r, r.r, alpha} per iteration.
-    A-GEM proper wants a stream built with train_enable=False, whose task loader does not mix the memory in; with
-    train_enable=True the method is replay plus projection.  With use_graph the task batch's step replays as usual and
-    the reference pass stays eager between the replays.  Not with a reducer (ValueError).
-    cl_cfg.name 'der' (ours; cl_methods/der.py): at the end of every task -- memory updated, best checkpoint reloaded, head not
-    yet grown -- the clips that entered the memory get their logits recorded in `model.der_bank` and evicted clips lose their
-    record; from the next task on every step adds cl_cfg['der_alpha'] times the mean squared distance between the memory
-    clips' logits and their records ('der_loss' in the loss dict; ops.der_replay, part of a replayed step).  A stream built
-    with train_enable=True gives DER++ (the memory clips' labels are in the detection loss); with train_enable=False no
-    memory clip reaches a batch and the term is zero.  With ckpt_folder the bank is written next to the memory pickle
-    (DER_BANK_FILE) and start_task > 0 reads it back -- or raises.  Not with a reducer, nor with type_sampling 'icarl'.
-    cl_cfg.name 'rwalk' (ours; cl_methods/regularizers.py): `rwalk_begin_task` before every task's epochs (where SI's is), the
-    consolidation right after them, before the best checkpoint is reloaded.  The Fisher average and the path scores outlive a
-    task: with ckpt_folder they are written next to the memory pickle at every task boundary (RWALK_STATE_FILE, with the
-    importance dictionary the task's checkpoints predate) and start_task > 0 reads them back -- or raises; start_epoch > 0
-    raises as for 'si'.  Reading the file REPLACES model.reg_params, also a dictionary the caller restored from a checkpoint
-    before the call.
-    cl_cfg.prompt_type 'coda' (ours; cl_methods/coda.py): cl_cfg['coda_tasks'] None is filled from the stream's task count
-    before the model is used, and `model.prompt.set_task(j)` runs at the start of task j -- after the previous task's checkpoint
-    reload and head growth, before task j's optimizer is built (its rows are new values: their moments start at zero).  Not
-    with a reducer (ValueError).
+    cfg['cl_cfg'] names the continual-learning method; what it does and where is in cl_methods/hooks.py (which methods this
+    driver runs, and which with a reducer: hooks.SUPPORT).  Every method's options are validated, and resume state read, before
+    the model or the stream is used for anything else.
     Returns (model, optimizer, scheduler, log) with log = list of per-task dicts."""
-    from .cl_methods import agem as agem_mod
-    from .cl_methods import der as der_mod
     is_main = int(os.environ.get("LOCAL_RANK", "0")) == 0
-    imp_opts = regularizers.importance_options(cfg['cl_cfg'])      # a bad value fails here, not after the first task
-    use_si = _si_check(cfg, start_epoch)
-    rwalk = _rwalk_check(cfg, start_epoch, model, start_task, ckpt_folder)
-    use_agem = agem_mod.check_supported(cfg['cl_cfg']['name'], reducer)
-    use_der = der_mod.check_supported(cfg['cl_cfg']['name'], reducer, type_sampling=cfg['cl_cfg'].get('type_sampling'))
-    if use_der:
-        model.der_alpha = float(cfg['cl_cfg'].get('der_alpha', model.der_alpha))
-        if getattr(model, 'der_bank', None) is None:
-            model.der_bank = der_mod.DERBank()
-        if start_task > 0:
-            path = None if ckpt_folder is None else os.path.join(ckpt_folder, DER_BANK_FILE)
-            if path is None or not os.path.exists(path):
-                raise ValueError("cl_cfg.name 'der' resumed at task %d needs the recorded logits of the memory (%s, written next "
-                                 "to the memory pickle after every task): none found" % (start_task, path or DER_BANK_FILE))
-            model.der_bank.load_state_dict(torch.load(path, map_location='cpu', weights_only=False), device=model.device)
-    use_coda = _coda_begin(cfg, model, train_stream, start_task, reducer)
+    hooks = make_hooks(cfg, 'run_episodes', reducer)
+    each(hooks, 'begin_run', model, train_stream, start_task, start_epoch, ckpt_folder)
     optimizer = make_optimizer(model, cfg['opt'])
-
-    def make_graph(opt):
-        if not use_graph:
-            return None
-        from .graph import GraphedStep
-        return GraphedStep(model, opt, clip_grad_l2norm=cfg['train_cfg']['clip_grad_l2norm'], reducer=reducer)
-    graph = make_graph(optimizer)
+    graph = _make_graph(use_graph, cfg, model, optimizer, reducer)
     it = iter(train_stream)
     num_tasks = train_stream.num_tasks
     data, loader, num_next = next(it)
@@ -265,17 +171,9 @@ def run_episodes(cfg, model, train_stream, validate=None, ckpt_folder=None, gpu_
         best, best_epoch = -10000.0, -1
         prev_logits = cache_prev_logits(model, loader, j) if model.type_sampling == 'icarl' else {}
         ck_name = 'best_task_{:03d}_performance.pth.tar'.format(j)
-        if use_si:
-            regularizers.si_begin_task(model, optimizer)      # the head has grown, this task's optimizer exists
-        if rwalk is not None:
-            regularizers.rwalk_begin_task(model, optimizer, **rwalk)      # F and s carried on their prefix, tick = 0
-        agem = None
-        if use_agem and train_stream.memory:
-            mem_sampler = agem_mod.MemorySampler(train_stream.memory, cfg['cl_cfg'].get('agem_batch', loader.batch_size),
-                                             cfg['cl_cfg'].get('agem_seed', getattr(train_stream, 'seed', 0)))
-            agem = agem_mod.AGEM(model, mem_sampler, trace=[] if keep_history else None)
-            if keep_history:
-                entry['agem'] = agem.trace
+        extra = {}          # what a method adds to train_one_epoch's arguments (A-GEM: agem=)
+        for kw in each(hooks, 'begin_task', j, model, optimizer, loader, entry, keep_history):
+            extra.update(kw or {})
         for epoch in range(start_epoch, max_epochs):
             sampler = getattr(loader, 'sampler', None)
             if sampler is not None and hasattr(sampler, 'set_epoch'):
@@ -286,7 +184,7 @@ def run_episodes(cfg, model, train_stream, validate=None, ckpt_folder=None, gpu_
                                    clip_grad_l2norm=cfg['train_cfg']['clip_grad_l2norm'], print_freq=print_freq,
                                    logger=logger, cl_name=cfg['cl_cfg']['name'], reg_lambda=cfg['cl_cfg']['reg_lambda'],
                                    prev_out_cls_logits_dict=prev_logits, current_task_id=j, reducer=reducer, graph=graph,
-                                   keep_history=keep_history or on_step_history is not None, agem=agem)
+                                   keep_history=keep_history or on_step_history is not None, **extra)
             if keep_history:
                 entry['history'].append(hist)
             if on_step_history is not None:
@@ -304,56 +202,27 @@ def run_episodes(cfg, model, train_stream, validate=None, ckpt_folder=None, gpu_
             _barrier(reducer)          # the other ranks do not run ahead into the next epoch's collectives while rank 0
                                        # validates and writes the checkpoint
         entry['best_metric'], entry['best_epoch'] = best, best_epoch
-        si_reg = _si_consolidate(cfg, model, optimizer) if use_si and num_next is not None else None
-        if rwalk is not None and num_next is not None:
-            si_reg = _rwalk_consolidate(cfg, model, optimizer, rwalk)
+        each(hooks, 'end_training', j, model, optimizer, num_next is not None)
 
         # replay memory for the next task (train_cl.py:343-361)
-        n_cls = model.cls_head.cls_head.conv.out_channels
         if memory_size != 0:
-            model.add_samples_to_mem(train_stream, data, memory_quota(memory_size, n_cls))
+            model.add_samples_to_mem(train_stream, data, memory_quota(memory_size, model.cls_head.cls_head.conv.out_channels))
         train_stream.memory = model.memory
         model.n_known = len(model.memory)
-        if ckpt_folder is not None:
-            if is_main:
-                os.makedirs(ckpt_folder, exist_ok=True)
-                with open(os.path.join(ckpt_folder, cfg['cl_cfg']['path_memory']), 'wb') as h:
-                    pickle.dump(model.memory, h)
-                if rwalk is not None and num_next is not None:      # F and the halved s: what task j + 1 starts from
-                    torch.save(regularizers.rwalk_state_dict(model), os.path.join(ckpt_folder, RWALK_STATE_FILE))
-            _barrier(reducer)          # the checkpoint rank 0 wrote is complete before anybody reads it
-            # EVERY rank reloads the task's best state (train_cl.py:363 runs on every rank): replicas that kept their
-            # last-epoch weights would never meet the others again -- the gradient average does not re-align weights
-            model = load_best_checkpoint(model, ckpt_folder, ck_name, j, gpu_id)
-        if use_der:
-            # the memory is final for this task and the model is the one the next task starts from, its head not yet grown:
-            # clips that entered the memory now get their record, evicted clips lose theirs, older records stay as they are
-            bank = model.der_bank
-            entry['der_dropped'] = bank.drop_missing(model.memory)
-            entry['der_recorded'] = der_mod.record_memory(model, bank, model.memory, j)
-            if ckpt_folder is not None and is_main:
-                torch.save(bank.state_dict(), os.path.join(ckpt_folder, DER_BANK_FILE))
+        model = _save_memory_and_reload(cfg, model, hooks, j, ckpt_folder, ck_name, gpu_id, is_main, reducer)
+        each(hooks, 'after_reload', j, model, entry)
         if validate is not None:
             entry['final_metric'] = validate(model, max_epochs - 1, j)
         log.append(entry)
 
         if num_next is not None:
             model.augment_classification(num_next, torch.device('cuda', gpu_id))
-            if cfg['cl_cfg']['name'] == 'ewc':
-                model.reg_params = regularizers.on_task_update(loader, gpu_id, optimizer, model, kind='ewc', group=getattr(reducer, 'group', None), data_parallel=reducer is not None,
-                                                               **imp_opts)
-            elif cfg['cl_cfg']['name'] == 'mas':
-                model.reg_params = regularizers.on_task_update(loader, gpu_id, optimizer, model, kind='mas', group=getattr(reducer, 'group', None), data_parallel=reducer is not None,
-                                                               **imp_opts)
-            elif use_si or rwalk is not None:
-                model.reg_params = si_reg      # (the reload above put the checkpoint's older dictionary back)
-            if use_coda:
-                model.prompt.set_task(j + 1)   # the next task's components, before its optimizer exists
+            each(hooks, 'before_next_task', j, model, optimizer, loader, gpu_id)
             optimizer = make_optimizer(model, cfg['opt'])
             scheduler = make_scheduler(optimizer, cfg['opt'], iters_per_epoch)
             if reducer is not None:
                 reducer.rebuild()          # the class head and the gaussian parameters are new tensors
-            graph = make_graph(optimizer)  # new parameters, new optimizer: the old task's graphs are dropped
+            graph = _make_graph(use_graph, cfg, model, optimizer, reducer)
     return model, optimizer, scheduler, log
 
 
@@ -380,27 +249,12 @@ def run_episodes_bic(cfg, model, train_stream, validate=None, ckpt_folder=None, 
     i.e. per task; from the second task on the captured step holds the bias correction, ops.bic_correct, which reads alpha /
     beta from the layers' memory).  Single process (the reference's stage 2 is not data parallel either).  Returns (model, optimizer, scheduler,
     log); a task's log entry has 'bic' = {'alpha', 'beta', 'before', 'after', 'losses'} after a stage 2.
-    cl_cfg.name 'agem' is refused (ValueError): only `run_episodes` projects gradients."""
-    from .cl_methods import agem as agem_mod
+    The methods this driver refuses (ValueError), and those it runs without their hooks: cl_methods/hooks.py, SUPPORT."""
     from .cl_methods.bic import BiCCache, fit_bias_layer, newest_split
     from .utils.cl_stream import DistributedBatchLoader
-    agem_mod.check_supported(cfg['cl_cfg']['name'], driver='run_episodes_bic')
-    from .cl_methods import der as der_mod
-    der_mod.check_supported(cfg['cl_cfg']['name'], driver='run_episodes_bic')      # 'der': run_episodes only, as 'agem'
-    from .cl_methods import coda as coda_mod
-    if cfg['cl_cfg'].get('prompt_pool'):
-        coda_mod.check_supported(cfg['cl_cfg'].get('prompt_type', 'l2p'), driver='run_episodes_bic')      # CODA-Prompt: run_episodes only
-    if cfg['cl_cfg']['name'] == 'rwalk':
-        raise ValueError("cl_cfg.name 'rwalk' is not supported by run_episodes_bic: only run_episodes and run_episodes_nlq keep "
-                         "its state and consolidate it")
+    hooks = make_hooks(cfg, 'run_episodes_bic')          # refuses what SUPPORT does; no method has hooks in this driver
     optimizer = make_optimizer(model, cfg['opt'])
-
-    def make_graph(opt):
-        if not use_graph:
-            return None
-        from .graph import GraphedStep
-        return GraphedStep(model, opt, clip_grad_l2norm=cfg['train_cfg']['clip_grad_l2norm'])
-    graph = make_graph(optimizer)
+    graph = _make_graph(use_graph, cfg, model, optimizer)
     it = iter(train_stream)
     num_tasks = train_stream.num_tasks
     max_epochs = cfg['opt'].get('early_stop_epochs', cfg['opt']['epochs'] + cfg['opt']['warmup_epochs'])
@@ -449,16 +303,11 @@ def run_episodes_bic(cfg, model, train_stream, validate=None, ckpt_folder=None, 
                     checkpoint(j, epoch, ck_name)
         entry['best_metric'], entry['best_epoch'] = best, best_epoch
 
-        n_cls = model.cls_head.cls_head.conv.out_channels
         if memory_size != 0:
-            model.add_samples_to_mem(train_stream, data, memory_quota(memory_size, n_cls))
+            model.add_samples_to_mem(train_stream, data, memory_quota(memory_size, model.cls_head.cls_head.conv.out_channels))
         train_stream.memory = model.memory
         model.n_known = len(model.memory)
-        if ckpt_folder is not None:
-            os.makedirs(ckpt_folder, exist_ok=True)
-            with open(os.path.join(ckpt_folder, cfg['cl_cfg']['path_memory']), 'wb') as h:
-                pickle.dump(model.memory, h)
-            model = load_best_checkpoint(model, ckpt_folder, ck_name, j, gpu_id)
+        model = _save_memory_and_reload(cfg, model, hooks, j, ckpt_folder, ck_name, gpu_id)
         if validate is not None:
             entry['final_metric'] = validate(model, max_epochs - 1, j)
 
@@ -486,7 +335,7 @@ def run_episodes_bic(cfg, model, train_stream, validate=None, ckpt_folder=None, 
             model.augment_classification(num_next, torch.device('cuda', gpu_id))
             optimizer = make_optimizer(model, cfg['opt'])
             scheduler = make_scheduler(optimizer, cfg['opt'], len(loader))
-            graph = make_graph(optimizer)          # new parameters, new optimizer: the old task's graphs are dropped
+            graph = _make_graph(use_graph, cfg, model, optimizer)
     return model, optimizer, scheduler, log
 
 
@@ -534,32 +383,18 @@ def run_episodes_nlq(cfg, model, train_stream, val_stream, evaluator, ckpt_folde
     val_stream: `get_valSet_by_taskNum(n)` -> [(loader with batch size 1, #templates), ...] (cl_benchmark.py:60-74);
     evaluator: `.dataset`, `.evaluate(records, verbose) -> (performance[[R@1, ...]], str)` (libs/utils/metrics.py
     ReferringRecall; outside the hot path).  on_validate(kind, task, epoch, r1) is called after every validation.
-    cl_cfg.name 'agem' is refused (ValueError): only `run_episodes` projects gradients.
+    The methods this driver runs and those it refuses (ValueError): cl_methods/hooks.py, SUPPORT.
     Returns (model, optimizer, scheduler, log)."""
-    from .cl_methods import agem as agem_mod
     from .utils import train_utils_nlq as tu
-    agem_mod.check_supported(cfg['cl_cfg']['name'], driver='run_episodes_nlq')
-    from .cl_methods import der as der_mod
-    der_mod.check_supported(cfg['cl_cfg']['name'], driver='run_episodes_nlq')      # 'der': run_episodes only, as 'agem'
-    from .cl_methods import coda as coda_mod
-    if cfg['cl_cfg'].get('prompt_pool'):
-        coda_mod.check_supported(cfg['cl_cfg'].get('prompt_type', 'l2p'), driver='run_episodes_nlq')      # CODA-Prompt: run_episodes only
     is_main = int(os.environ.get("LOCAL_RANK", "0")) == 0
-    imp_opts = regularizers.importance_options(cfg['cl_cfg'])
-    use_si = _si_check(cfg, start_epoch)
-    rwalk = _rwalk_check(cfg, start_epoch, model, start_task, ckpt_folder)
-    hb = cfg['opt']["backbone_lr_weight"] != 1
+    hooks = make_hooks(cfg, 'run_episodes_nlq', reducer)
+    each(hooks, 'begin_run', model, train_stream, start_task, start_epoch, ckpt_folder)
 
     def new_optimizer():
-        return tu.make_optimizer(model, cfg['opt'], head_backbone_group=hb)
+        return tu.make_optimizer(model, cfg['opt'], head_backbone_group=cfg['opt']["backbone_lr_weight"] != 1)
 
-    def make_graph(opt):
-        if not use_graph:
-            return None
-        from .graph import GraphedStep
-        return GraphedStep(model, opt, clip_grad_l2norm=cfg['train_cfg']['clip_grad_l2norm'], reducer=reducer)
     optimizer = new_optimizer()
-    graph = make_graph(optimizer)
+    graph = _make_graph(use_graph, cfg, model, optimizer, reducer)
     it = iter(train_stream)
     num_tasks = train_stream.num_tasks
     data, loader, num_next = next(it)
@@ -588,10 +423,7 @@ def run_episodes_nlq(cfg, model, train_stream, val_stream, evaluator, ckpt_folde
         tracker.new_task(entry['init_R1'])
         prev_logits = cache_prev_logits(model, loader, j, as_numpy=True) if model.type_sampling == 'icarl' else {}
         ck_name = 'Best_task_{:02d}.pth.tar'.format(j)
-        if use_si:
-            regularizers.si_begin_task(model, optimizer)      # a new optimizer per task: attached again
-        if rwalk is not None:
-            regularizers.rwalk_begin_task(model, optimizer, **rwalk)
+        each(hooks, 'begin_task', j, model, optimizer, loader, entry, keep_history)      # a new optimizer per task: attached again
         for epoch in range(start_epoch, max_epochs):
             sampler = getattr(loader, 'sampler', None)
             if sampler is not None and hasattr(sampler, 'set_epoch'):
@@ -623,32 +455,18 @@ def run_episodes_nlq(cfg, model, train_stream, val_stream, evaluator, ckpt_folde
             if validated or is_best:
                 _barrier(reducer)
         entry['best_R1'], entry['best_epoch'] = tracker.best, tracker.best_epoch
-        si_reg = _si_consolidate(cfg, model, optimizer) if use_si and num_next is not None else None
-        if rwalk is not None and num_next is not None:
-            si_reg = _rwalk_consolidate(cfg, model, optimizer, rwalk)
+        each(hooks, 'end_training', j, model, optimizer, num_next is not None)
         if memory_size != 0:
             model.add_samples_to_mem(val_stream, data, 'ALL' if memory_size == 'ALL' else memory_size // 13)
         train_stream.memory = model.memory
         model.n_known = j + 1
-        if ckpt_folder is not None:
-            if is_main:
-                os.makedirs(ckpt_folder, exist_ok=True)
-                with open(os.path.join(ckpt_folder, cfg['cl_cfg']['path_memory']), 'wb') as h:
-                    pickle.dump(model.memory, h)
-                if rwalk is not None and num_next is not None:
-                    torch.save(regularizers.rwalk_state_dict(model), os.path.join(ckpt_folder, RWALK_STATE_FILE))
-            _barrier(reducer)
-            model = load_best_checkpoint(model, ckpt_folder, ck_name, j, gpu_id)
+        model = _save_memory_and_reload(cfg, model, hooks, j, ckpt_folder, ck_name, gpu_id, is_main, reducer)
+        each(hooks, 'after_reload', j, model, entry)
         entry['final_R1'] = validate('final', j, max_epochs - 1)
         log.append(entry)
         if num_next is not None:
-            if cfg['cl_cfg']['name'] in ('ewc', 'mas'):
-                model.reg_params = regularizers.on_task_update(loader, gpu_id, optimizer, model, kind=cfg['cl_cfg']['name'],
-                                                               group=getattr(reducer, 'group', None), data_parallel=reducer is not None,
-                                                               **imp_opts)
-            elif use_si or rwalk is not None:
-                model.reg_params = si_reg
+            each(hooks, 'before_next_task', j, model, optimizer, loader, gpu_id)
             optimizer = new_optimizer()
             scheduler = tu.make_scheduler(optimizer, cfg['opt'], iters_per_epoch)
-            graph = make_graph(optimizer)
+            graph = _make_graph(use_graph, cfg, model, optimizer, reducer)
     return model, optimizer, scheduler, log
