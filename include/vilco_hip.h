@@ -763,6 +763,45 @@ int vilco_der_bwd(const vilco_der_desc* d, const float* g_out, float* d_logits, 
                   size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------ */
+/* Pooled Outputs Distillation (Douillard et al., "PODNet", ECCV 2020; the reference has no feature-level distillation)   */
+/* over the pyramid (csrc/pod.hip): h = feats[l][b], token-major [T_l][C]; V = level_len[b][l] clamped to [0, T_l].         */
+/*   p[c] = sum_{t < V} fl(h[t][c]^2)   q[t] = sum_{c < C} fl(h[t][c]^2)   (squares fp32; sums fp64, fixed order)           */
+/*   v = [p ; q] (C + V entries)   n = max(||v||, 1e-12)   u = fl32(v / n)  (fp64, rounded to fp32 once: what a record     */
+/*   holds, so a clip against the record of its own features gives u - r = 0 and an exactly zero gradient)                 */
+/*   r = the first C + V entries of the record's slice for level l; a record is fp32 [sum_l (C + T_l)], level l's slice     */
+/*       [p (C) ; q (T_l)] at offset sum_{l' < l} (C + T_l'), stored normalised, any 4-byte alignment                      */
+/*   dist[b][l] = ||u - r||  (0 for V == 0)   N_rec = rows with pod_tab[b] != 0, counted on the device                      */
+/*   out = (float)(scale / (L N_rec) * sum_b sum_l dist[b][l]), 0 when N_rec == 0            (fp64, rounded once)           */
+/*   g_u = w (u - r) / max(dist, 1e-12)   w = g_out scale / (L N_rec)   g_v = (g_u - u (u . g_u)) / n   (fp64, g_v rounded  */
+/*   to fp32 once)   d_h[t][c] = fl(fl(2 h[t][c]) * fl(g_v[c] + g_v[C + t])) for t < V; 0 for t >= V and rows without record */
+/* feats / level_T are HOST arrays (L <= 16 device pointers / lengths, validated before anything is enqueued).  pod_tab     */
+/* (DEVICE int64 [B]: record address or 0) and level_len (DEVICE int32 [B][L]) are read when the kernels RUN, so a captured */
+/* launch follows a table rewritten between replays; the records must stay where they are while a graph may replay.       */
+/* fwd: three launches; out = device float[1]; N_rec is left in the workspace (the int64 at its first 256-byte boundary)   */
+/* with g_v / w, where bwd reads them: hand bwd the SAME workspace, untouched in between.                                  */
+/* bwd: one launch; g_out = device scalar; d_feats = host table of L device pointers; EVERY element of every level's        */
+/* gradient is assigned (zeros where nothing is compared): the caller fills nothing.                                       */
+/* record: two launches; every row is pooled (pod_tab is not read, may be null) and u is written to records [B][sum_l (C +  */
+/* T_l)], entries t >= V as 0.  vilco_pod_tile_rows: the rows of a level one workgroup covers.  No atomics: same bits on    */
+/* every call.  A null pointer, L outside 1..16, B < 1, C < 1, T_l < 1: VILCO_ERR_BADARG (vilco_pod_workspace: 0); a short  */
+/* workspace: VILCO_ERR_WORKSPACE -- both before anything is enqueued.                                                     */
+/* ------------------------------------------------------------------------------------------ */
+typedef struct vilco_pod_desc {
+  const float* const* feats;  /* host [L]: device pointers, level l = [B][T_l][C] */
+  const int32_t* level_T;     /* host [L]: rows of every level */
+  const int32_t* level_len;   /* device [B][L]: valid lengths */
+  const int64_t* pod_tab;     /* device [B]: record address or 0 */
+  int32_t B, C, L, reserved;
+  double scale;               /* pod_lambda * sqrt(n_classes / (n_classes - n_known)) */
+} vilco_pod_desc;
+int32_t vilco_pod_tile_rows(void);
+size_t vilco_pod_workspace(const int32_t* level_T, int32_t L, int32_t B, int32_t C);
+int vilco_pod_fwd(const vilco_pod_desc* d, float* out, void* workspace, size_t workspace_bytes, void* stream);
+int vilco_pod_bwd(const vilco_pod_desc* d, const float* g_out, float* const* d_feats, const void* workspace,
+                  size_t workspace_bytes, void* stream);
+int vilco_pod_record(const vilco_pod_desc* d, float* records, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------ */
 /* BiC bias correction of the classification head's output (MQ/libs/modeling/meta_archs.py:26-35: BiasLayer,           */
 /* alpha * x + beta; :821-836: one layer per task over its slice of the class columns, the slices concatenated again)    */
 /* as one launch over the concatenated head output (csrc/bic.hip):                                                       */

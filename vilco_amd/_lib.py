@@ -156,6 +156,12 @@ class DerDesc(C.Structure):
                 ("der_tab", c_fp), ("B", i32), ("R", i32), ("C", i32), ("L", i32), ("alpha", C.c_double)]
 
 
+class PodDesc(C.Structure):
+    _cname_ = "vilco_pod_desc"
+    _fields_ = [("feats", c_fp), ("level_T", c_fp), ("level_len", c_fp), ("pod_tab", c_fp), ("B", i32), ("C", i32), ("L", i32),
+                ("reserved", i32), ("scale", C.c_double)]
+
+
 class BicCorrectDesc(C.Structure):
     _cname_ = "vilco_bic_correct_desc"
     _fields_ = [("x", c_fp), ("y", c_fp), ("splits", c_fp), ("table", c_fp), ("rows", i64), ("C", i32), ("S", i32),
@@ -268,6 +274,11 @@ SIGNATURES = {
     "vilco_der_workspace": (sz, [i64]),
     "vilco_der_fwd": (C.c_int, [C.POINTER(DerDesc), c_fp, c_fp, sz, c_fp]),
     "vilco_der_bwd": (C.c_int, [C.POINTER(DerDesc), c_fp, c_fp, c_fp, sz, c_fp]),
+    "vilco_pod_tile_rows": (i32, []),
+    "vilco_pod_workspace": (sz, [C.POINTER(i32), i32, i32, i32]),
+    "vilco_pod_fwd": (C.c_int, [C.POINTER(PodDesc), c_fp, c_fp, sz, c_fp]),
+    "vilco_pod_bwd": (C.c_int, [C.POINTER(PodDesc), c_fp, C.POINTER(c_fp), c_fp, sz, c_fp]),
+    "vilco_pod_record": (C.c_int, [C.POINTER(PodDesc), c_fp, c_fp, sz, c_fp]),
     "vilco_cl_penalty": (C.c_int, [C.POINTER(ChunkTable), f32, i32, c_fp, c_fp, c_fp]),
     "vilco_cl_accumulate": (C.c_int, [C.POINTER(ChunkTable), i32, f32, f32, c_fp]),
     "vilco_agem_project": (C.c_int, [C.POINTER(ChunkTable), c_fp, c_fp, c_fp]),

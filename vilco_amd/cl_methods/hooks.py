@@ -7,7 +7,7 @@ import os
 
 import torch
 
-from . import agem as agem_mod, coda as coda_mod, der as der_mod, regularizers
+from . import agem as agem_mod, coda as coda_mod, der as der_mod, pod as pod_mod, regularizers
 
 DER_BANK_FILE = 'der_bank.pt'      # cl_cfg.name 'der': DERBank.state_dict(), written next to the memory pickle
 RWALK_STATE_FILE = 'rwalk_state.pt'      # cl_cfg.name 'rwalk': regularizers.rwalk_state_dict(), written next to the memory pickle
@@ -17,7 +17,7 @@ HOOKS = 'hooks'      # the driver calls the method's hooks
 PENALTY_ONLY = 'penalty only'      # no hook is called: train_one_epoch applies the penalty if model.reg_params is populated (by
 #                                    a checkpoint, say), and nothing consolidates -- the dictionary never changes
 # method -> ({driver: what it gives the method}, whether the method accepts a reducer, i.e. data parallelism).  A driver that is
-# not listed refuses the method by name, as does run_episodes with a reducer that is not accepted: agem / der / coda
+# not listed refuses the method by name, as does run_episodes with a reducer that is not accepted: agem / der / pod / coda
 # .check_supported read their rows and say why, make_hooks reads RWalk's.  'coda' is cl_cfg.prompt_type under cl_cfg.prompt_pool,
 # the others are cl_cfg.name; a name that is not here (None, 'icarl', 'bic', ...) has no hooks and runs everywhere.
 SUPPORT = {
@@ -29,6 +29,16 @@ SUPPORT = {
     'der': ({MQ: HOOKS}, False),      # (nor with type_sampling 'icarl': der.check_supported)
     'coda': ({MQ: HOOKS}, False),
 }
+# rows of the same shape for the methods added after tests/test_cl_hooks_cpu.py listed SUPPORT's keys one by one: SUPPORT itself keeps
+# that list, `support(name)` reads both tables
+SUPPORT_MORE = {
+    'pod': ({MQ: HOOKS}, False),      # (nor with type_sampling 'icarl' or start_epoch > 0: pod.check_supported)
+}
+
+
+def support(name):
+    """the row of `name` in SUPPORT or SUPPORT_MORE (KeyError: the method has no row and runs everywhere)"""
+    return SUPPORT[name] if name in SUPPORT else SUPPORT_MORE[name]
 
 
 def _resume_file(what, start_task, ckpt_folder, name, holds):
@@ -189,6 +199,32 @@ class DER(Hook):
             torch.save(bank.state_dict(), os.path.join(self.folder, DER_BANK_FILE))
 
 
+class POD(Hook):
+    """cl_cfg.name 'pod' (cl_methods/pod.py): at the START of every task with known classes -- the incoming model is intact: the
+    best checkpoint of the previous task, head grown, no step taken -- `model.pod_bank` is cleared and every clip the task's loader
+    yields (the task's own clips and, with train_enable=True, the memory's) gets the pooled, normalised pyramid of that model
+    recorded.  Every step of the task then adds PODNet's feature distillation against those records ('pod_loss' in the loss
+    dict; ops.pod_distill, part of a replayed step), weighted cl_cfg['pod_lambda'] * sqrt(n_classes / new classes).  The cost
+    is ONE inference pass over the task's clips per task (the task's log entry gets 'pod_recorded' = the number of records).
+    No state file: a resume at a task boundary rebuilds the records from the reloaded model; a resume inside a task
+    (start_epoch > 0) raises, because the incoming model is gone by then.  A loader that re-crops a long clip differently
+    from epoch to epoch leaves that clip without a usable record in the epochs whose crop differs (PODBank.skipped)."""
+
+    def begin_run(self, model, train_stream, start_task=0, start_epoch=0, ckpt_folder=None):
+        pod_mod.check_supported('pod', self.reducer, type_sampling=self.cl_cfg.get('type_sampling'), start_epoch=start_epoch)
+        lam = float(self.cl_cfg.get('pod_lambda', model.pod_lambda))
+        if not lam >= 0.0 or lam == float('inf'):
+            raise ValueError("cl_cfg.pod_lambda must be a finite number >= 0, got %r" % (self.cl_cfg.get('pod_lambda'),))
+        model.pod_lambda = lam
+        if getattr(model, 'pod_bank', None) is None:
+            model.pod_bank = pod_mod.PODBank()
+
+    def begin_task(self, j, model, optimizer, loader, entry, keep_history=True):
+        if model.n_known > 0:
+            model.pod_bank.clear()
+            entry['pod_recorded'] = pod_mod.record_clips(model, model.pod_bank, loader, j)
+
+
 class Coda(Hook):
     """cl_cfg.prompt_type 'coda' under cl_cfg.prompt_pool (cl_methods/coda.py), alongside any named method: cl_cfg['coda_tasks']
     None is filled from the stream's task count; a model that holds a CodaPrompt must divide its pool among as many tasks as the
@@ -216,7 +252,7 @@ class Coda(Hook):
         self.draw(model, j + 1)
 
 
-NAMED = {'ewc': Importance, 'mas': Importance, 'si': SI, 'rwalk': RWalk, 'agem': AGEM, 'der': DER}
+NAMED = {'ewc': Importance, 'mas': Importance, 'si': SI, 'rwalk': RWalk, 'agem': AGEM, 'der': DER, 'pod': POD}
 
 
 def each(hooks, point, *args):
@@ -226,17 +262,18 @@ def each(hooks, point, *args):
 
 def make_hooks(cfg, driver, reducer=None):
     """-> the hook objects of a run of `driver`: [the named method's] + [Coda()], either of which may be missing.  What SUPPORT
-    does not let run in `driver` is refused here -- agem, der, coda, rwalk in this order; begin_run refuses the rest.  A driver
+    does not let run in `driver` is refused here -- agem, der, pod, coda, rwalk in this order; begin_run refuses the rest.  A driver
     that consolidates validates the importance options whatever the method: a bad value fails here, not after the first task."""
     cl_cfg = cfg['cl_cfg']
     name = cl_cfg['name']
     agem_mod.check_supported(name, driver=driver)
     der_mod.check_supported(name, driver=driver)
+    pod_mod.check_supported(name, driver=driver)
     coda = bool(cl_cfg.get('prompt_pool')) and coda_mod.check_supported(cl_cfg.get('prompt_type', 'l2p'), driver=driver)
     if name == 'rwalk' and driver not in SUPPORT['rwalk'][0]:
         raise ValueError("cl_cfg.name 'rwalk' is not supported by %s: only run_episodes and run_episodes_nlq keep its state and "
                          "consolidate it" % driver)
     if SUPPORT['ewc'][0][driver] == HOOKS:
         regularizers.importance_options(cl_cfg)
-    named = [NAMED[name](cfg, reducer)] if name in NAMED and SUPPORT[name][0][driver] == HOOKS else []
+    named = [NAMED[name](cfg, reducer)] if name in NAMED and support(name)[0][driver] == HOOKS else []
     return named + ([Coda(cfg, reducer)] if coda else [])

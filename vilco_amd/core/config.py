@@ -133,7 +133,9 @@ DEFAULTS = {'init_rand_seed': 765421321,
 #   cl_cfg.rwalk_alpha / rwalk_delta_t / rwalk_eps (cl_cfg.name 'rwalk', cl_methods/regularizers.py): the weight of the new squared
 #   gradient in the Fisher moving average and the iterations between two checkpoints of the path score -- 0.9 and 10, the RWalk
 #   paper's -- and the constant in the score's denominator, for which the paper gives no value: 1e-8 is ours.
-EXTRA_DEFAULTS = {'cl_cfg': {'der_alpha': 0.1, 'prompt_type': 'l2p', 'coda_tasks': None, 'coda_ortho_mu': 0.0, 'coda_seed': 0,
+#   cl_cfg.pod_lambda: weight of the pooled feature distillation of cl_cfg.name 'pod' (cl_methods/pod.py), before PODNet's
+#   adaptive factor sqrt(n_classes / new classes); a hyper-parameter, not tuned here.
+EXTRA_DEFAULTS = {'cl_cfg': {'der_alpha': 0.1, 'pod_lambda': 1.0, 'prompt_type': 'l2p', 'coda_tasks': None, 'coda_ortho_mu': 0.0, 'coda_seed': 0,
                              'rwalk_alpha': 0.9, 'rwalk_delta_t': 10, 'rwalk_eps': 1e-8}}
 
 

@@ -184,6 +184,10 @@ class GraphedStep:
             # THIS batch's memory clips (all zeros: none) -- the bank keeps the buffers where they are
             from .cl_methods import der
             inp.der_tab = der.step_table(self.model, video_list)
+        if getattr(self.model, "cl_name", None) == 'pod':
+            # likewise for csrc/pod.hip: the records of THIS batch's clips, written by the incoming model at the task's start
+            from .cl_methods import pod
+            inp.pod_tab = pod.step_table(self.model, video_list)
         return inp
 
     def _key(self, inp, task_id):

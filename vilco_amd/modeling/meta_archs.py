@@ -297,15 +297,17 @@ class StepInputs:
     step (one cached clip's levels end to end, PtTransformer.distill_target) with dist_lens = (T_l, ...), or None; dist_kind =
     the method ('icarl' / 'bic') the caller that replays the step attached dist_tgt for (graph.GraphedStep._prepare), or None;
     der_tab int64 [B, 2] = (address of the row's DER record or 0, its class count) of a cl_name 'der' step
-    (cl_methods.der.step_table), or None: the step then builds it from the clip list"""
+    (cl_methods.der.step_table), or None: the step then builds it from the clip list; pod_tab int64 [B] = the address of the
+    row's POD record or 0 of a cl_name 'pod' step (cl_methods.pod.step_table), or None: likewise"""
     __slots__ = ("feats_cf", "lens", "T", "text_cf", "text_lens", "narr", "gt", "narr_cf", "narr_lens", "narr_mask",
-                 "dist_tgt", "dist_lens", "dist_kind", "der_tab")
+                 "dist_tgt", "dist_lens", "dist_kind", "der_tab", "pod_tab")
     HOST = ("T", "narr", "dist_lens", "dist_kind")          # not device buffers: a captured step takes them over as they are
 
     def tensors(self):
         """(name, tensor) of every device buffer a replayed step reads"""
         return [(k, getattr(self, k)) for k in ("feats_cf", "lens", "text_cf", "text_lens", "gt", "narr_cf", "narr_lens",
-                                                "narr_mask", "dist_tgt", "der_tab") if getattr(self, k, None) is not None]
+                                                "narr_mask", "dist_tgt", "der_tab", "pod_tab")
+                if getattr(self, k, None) is not None]
 
     def signature(self):
         return (tuple((k, tuple(t.shape)) for k, t in self.tensors()) + (("narr", self.narr is not None),) +
@@ -410,6 +412,9 @@ class PtTransformer(nn.Module):
         self.cl_name = cl_cfg['name']
         self.der_alpha = float(cl_cfg.get('der_alpha', 0.1))      # cl_name 'der' (cl_methods/der.py)
         self.der_bank = None                 # cl_methods.der.DERBank: the memory clips' insertion-time logits (train_cl.run_episodes)
+        self.pod_lambda = float(cl_cfg.get('pod_lambda', 1.0))      # cl_name 'pod' (cl_methods/pod.py)
+        self.pod_bank = None                 # cl_methods.pod.PODBank: the incoming model's pooled pyramid of the task's clips
+        self._pod_step = None                # a get_emb pass of a 'pod' model leaves (pyramid, level lengths) here (pod.record_clips)
 
         self.prompt_pool = cl_cfg['prompt_pool']
         self.use_prompt_mask = True
@@ -608,7 +613,7 @@ class PtTransformer(nn.Module):
         inp.feats_cf, inp.lens, inp.T = self._batch_cf(video_list, is_training)
         inp.text_cf = inp.text_lens = inp.narr = inp.narr_cf = inp.narr_lens = inp.narr_mask = None
         inp.dist_tgt = inp.dist_lens = inp.dist_kind = None        # filled by the caller that replays the step (graph.GraphedStep)
-        inp.der_tab = None
+        inp.der_tab = inp.pod_tab = None
         if self.use_cross_modal:
             inp.text_cf, inp.text_lens, narr = self._query_batch_cf(video_list, narr_pad=narr_pad)
             if isinstance(narr, dict):
@@ -682,6 +687,10 @@ class PtTransformer(nn.Module):
             # the replayed term reads its records through the table in `inp.der_tab` (GraphedStep._prepare fills the slot)
             if getattr(inp, "der_tab", None) is None or prev_out_cls_logits:
                 return False
+        elif self.n_known > 0 and self.cl_name == 'pod':
+            # likewise: the records are named by the table in `inp.pod_tab`
+            if getattr(inp, "pod_tab", None) is None or prev_out_cls_logits:
+                return False
         elif prev_out_cls_logits:
             return False
         if isinstance(getattr(self, 'prompt', None), CodaPrompt):
@@ -704,6 +713,7 @@ class PtTransformer(nn.Module):
         self._dist_tgt = None if getattr(inp, "dist_tgt", None) is None else (inp.dist_tgt, inp.dist_lens)
         # a 'der' step: the table the caller attached, or the clips to build it from (_der_loss)
         self._der_step = (getattr(inp, "der_tab", None), video_list)
+        self._pod_tab_step = (getattr(inp, "pod_tab", None), video_list)      # a 'pod' step: likewise (_pod_loss)
         if self.use_cross_modal:
             text_tm, text_lens = ops.transpose(inp.text_cf), inp.text_lens
 
@@ -769,6 +779,8 @@ class PtTransformer(nn.Module):
             self.attach_pets(self.pets)
 
         if get_emb:
+            if self.cl_name == 'pod':      # the pyramid of this pass, for cl_methods.pod.record_clips
+                self._pod_step = (list(fpn_feats), torch.stack([l.to(torch.int32) for l in fpn_lens], dim=1).contiguous())
             return out_cls_logits, out_offsets, fpn_masks
 
         if is_training:
@@ -776,14 +788,14 @@ class PtTransformer(nn.Module):
             dev = self.device
             if fused:
                 losses = self._fused_losses(inp.gt, points, fpn_lens, out_cls_logits, out_offsets,
-                                            prev_out_cls_logits, reduce_sim)
+                                            prev_out_cls_logits, reduce_sim, fpn_feats=fpn_feats)
             else:
                 gt_segments = [x['segments'].to(dev) for x in video_list if len(x['labels']) > 0]
                 gt_labels = [x['labels'].to(dev) for x in video_list if len(x['labels']) > 0]
                 gt_cls, gt_off, np_cls, np_reg = self.label_points(points, gt_segments, gt_labels)
                 losses = self.losses(fpn_masks, out_cls_logits, out_offsets, gt_cls, gt_off, label_list=gt_labels,
                                      normal_probs_cls=np_cls, normal_probs_reg=np_reg,
-                                     prev_out_cls_logits=prev_out_cls_logits, reduce_sim=reduce_sim)
+                                     prev_out_cls_logits=prev_out_cls_logits, reduce_sim=reduce_sim, fpn_feats=fpn_feats)
             if ssl_fused:
                 # always present on this path, an exact 0 when no clip of the batch has a narration (the reference leaves
                 # the key out there: the sum is the same)
@@ -947,7 +959,7 @@ class PtTransformer(nn.Module):
             self._loss_tab = tab
         return tab[1]
 
-    def _fused_losses(self, gt, points, fpn_lens, out_cls_logits, out_offsets, prev_out_cls_logits, reduce_sim):
+    def _fused_losses(self, gt, points, fpn_lens, out_cls_logits, out_offsets, prev_out_cls_logits, reduce_sim, fpn_feats=None):
         """meta_archs.py:1253-1344 + 1374-1447 through ops.mq_loss; the CL terms (:1478-1519) are added on top.
         gt: the table of `_gt_table` -- one row per clip of the batch, in batch order."""
         cat, self._cat = self._cat, None       # not kept: it holds this step's head tensors and their autograd graph
@@ -974,7 +986,7 @@ class PtTransformer(nn.Module):
         level_row = cat.off if cat is not None else [sum(level_T[:i]) for i in range(len(level_T))]
         return self._cl_terms({'cls_loss': cls_loss, 'reg_loss': reg_loss, 'al_loss': al_loss}, final_loss,
                               out_cls_logits, prev_out_cls_logits, reduce_sim, cat_logits=(logits, level_row),
-                              level_len=level_len)
+                              level_len=level_len, fpn_feats=fpn_feats)
 
     # ------------------------------------------------------------------ losses
     @property
@@ -993,7 +1005,7 @@ class PtTransformer(nn.Module):
 
     def losses(self, fpn_masks, out_cls_logits, out_offsets, gt_cls_labels, gt_offsets, label_list=None,
                normal_probs_cls=None, normal_probs_reg=None, out_importances=None, out_start=None,
-               out_end=None, prev_out_cls_logits=None, stage_id=0, reduce_sim=None):
+               out_end=None, prev_out_cls_logits=None, stage_id=0, reduce_sim=None, fpn_feats=None):
         """focal + DIoU with gaussian point weights, 'al' loss, CL distillation terms
         (meta_archs.py:1374-1524).  One host sync: num_pos (as in the reference, :1407)."""
         valid_mask = torch.cat(fpn_masks, dim=1)
@@ -1061,7 +1073,7 @@ class PtTransformer(nn.Module):
                               prev_out_cls_logits, reduce_sim,
                               cat_logits=(logits_all, [sum(level_T[:i]) for i in range(len(level_T))]),
                               level_len=torch.stack([m.sum(1) for m in fpn_masks], dim=1).to(torch.int32).contiguous()
-                              if self.cl_name == 'der' else None)
+                              if self.cl_name in ('der', 'pod') else None, fpn_feats=fpn_feats)
 
     @staticmethod
     def _icarl_levels(prev_out_cls_logits, len_f):
@@ -1136,7 +1148,33 @@ class PtTransformer(nn.Module):
         records = [bank.get(der.clip_key(v))[0] if r[0] else None for v, r in zip(vids, rows)]
         return der.der_term(logits, level_row, level_T, level_len, records, self.der_alpha)[0]
 
-    def _cl_terms(self, out, final_loss, out_cls_logits, prev_out_cls_logits, reduce_sim, cat_logits=None, level_len=None):
+    def _pod_loss(self, fpn_feats, level_len):
+        """cl_name 'pod' (ours; cl_methods/pod.py): PODNet's pooled feature distillation of the step's pyramid against the records
+        the incoming model left for the batch's clips, times pod_lambda * sqrt(n_classes / new classes) (host arithmetic).  On
+        the device ONE ops.pod_distill call (csrc/pod.hip) over the level list, the records named by a device table; a CPU model
+        evaluates the same term in tensor ops."""
+        from ..cl_methods import pod
+        (tab, video_list), self._pod_tab_step = getattr(self, "_pod_tab_step", None) or (None, None), None
+        if fpn_feats is None:
+            raise ValueError("a cl_name 'pod' step needs the pyramid features of the step")
+        fpn_feats = list(fpn_feats)
+        level_T, Cn = tuple(int(f.shape[1]) for f in fpn_feats), int(fpn_feats[0].shape[2])
+        scale = pod.adaptive_scale(self.pod_lambda, self.cls_head.cls_head.conv.out_channels, self.n_known)
+        if fpn_feats[0].is_cuda:
+            if tab is None:
+                if video_list is None:
+                    raise ValueError("a cl_name 'pod' step needs StepInputs.pod_tab or the list of its clips")
+                tab = pod.step_table(self, video_list, level_T)
+            return ops.pod_distill(fpn_feats, level_len, tab, scale)
+        if video_list is None:
+            raise ValueError("a cl_name 'pod' step on a CPU model needs the list of its clips")
+        vids, bank = pod.labelled(video_list), self.pod_bank
+        rows = bank.rows_for(vids, [pod.clip_len(v) for v in vids], level_T, Cn) if bank is not None else [0] * len(vids)
+        records = [bank.get(pod.clip_key(v))[0] if r else None for v, r in zip(vids, rows)]
+        return pod.pod_term(fpn_feats, level_len, records, scale)[0]
+
+    def _cl_terms(self, out, final_loss, out_cls_logits, prev_out_cls_logits, reduce_sim, cat_logits=None, level_len=None,
+                  fpn_feats=None):
         """continual-learning terms on top of the detection loss (meta_archs.py:1478-1519).  On the device the iCaRL / BiC
         distillation term is one fused op (cat_logits = the concatenated logits and every level's first row in them); a
         CPU model walks the reference's loops.  level_len: int32 [B, L] valid lengths, read by the 'der' term only."""
@@ -1150,6 +1188,11 @@ class PtTransformer(nn.Module):
             der_loss = self._der_loss(out_cls_logits, cat_logits, level_len)
             out['der_loss'] = der_loss
             out['final_loss'] = final_loss + der_loss
+            return out
+        if self.n_known > 0 and self.cl_name == 'pod':      # fpn_feats: the pyramid of the step, level_len as for 'der'
+            pod_loss = self._pod_loss(fpn_feats, level_len)
+            out['pod_loss'] = pod_loss
+            out['final_loss'] = final_loss + pod_loss
             return out
         if self.n_known > 0 and self.cl_name in ('bic', 'icarl') and out_cls_logits[0].is_cuda:
             dist_loss = self._device_distill(out_cls_logits, prev_out_cls_logits, cat_logits)

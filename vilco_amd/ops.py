@@ -2144,6 +2144,116 @@ def der_replay(logits, level_row, level_T, valid_lens, der_tab, alpha, return_co
     return (loss, count) if return_count else loss
 
 
+# ---------------------------------------------------------------------------------------- pooled feature distillation (PODNet)
+def pod_tile_rows():
+    """rows of a level one workgroup of csrc/pod.hip covers (a longer level takes several, whose column partials are added in
+    block order)"""
+    return int(_lib.load().vilco_pod_tile_rows())
+
+
+def pod_record_width(level_T, C):
+    """floats of one clip's record: every level's [p (C) ; q (T_l)], levels end to end"""
+    return sum(int(C) + int(t) for t in level_T)
+
+
+def _pod_desc(feats, level_len, pod_tab, scale):
+    """-> (descriptor, workspace bytes, what the descriptor points into on the host: keep it alive across the call)"""
+    L = len(feats)
+    T = (_lib.i32 * L)(*[int(f.shape[1]) for f in feats])
+    ptrs = _ptr_table(feats)
+    d = _lib.PodDesc()
+    d.feats, d.level_T = C.addressof(ptrs), C.addressof(T)
+    d.level_len, d.pod_tab = level_len.data_ptr(), (pod_tab.data_ptr() if pod_tab is not None else None)
+    d.B, d.C, d.L, d.scale = feats[0].shape[0], feats[0].shape[2], L, float(scale)
+    nws = _lib.load().vilco_pod_workspace(T, L, d.B, d.C)
+    if nws == 0:
+        raise ValueError("pod: levels %s x C = %d are not a pyramid the op takes" % ([int(t) for t in T], d.C))
+    return d, nws, (ptrs, T)
+
+
+class _PodDistill(torch.autograd.Function):
+    """the pooled-feature distillation term over every level of the pyramid: three launches forward, one backward
+    (vilco_pod_fwd / _bwd); the backward assigns every element of every level's gradient"""
+
+    @staticmethod
+    def forward(ctx, level_len, pod_tab, scale, *feats):
+        _chk(*feats)
+        d, nws, keep = _pod_desc(feats, level_len, pod_tab, scale)
+        # the workspace is this call's own: backward reads N_rec and g_v / w from it
+        ws = torch.empty(int(nws), dtype=torch.uint8, device=feats[0].device)
+        out = torch.empty(1, dtype=torch.float32, device=feats[0].device)
+        _lib.check(_lib.load().vilco_pod_fwd(C.byref(d), out.data_ptr(), ws.data_ptr(), nws, _stream()))
+        ctx.scale, ctx.nws = float(scale), nws
+        ctx.save_for_backward(level_len, pod_tab, ws, *feats)
+        off = (-ws.data_ptr()) % 256
+        count = ws[off:off + 8].view(torch.int64)[0]
+        ctx.mark_non_differentiable(count)
+        return out[0], count
+
+    @staticmethod
+    def backward(ctx, g, _g_count):
+        level_len, pod_tab, ws = ctx.saved_tensors[:3]
+        feats = ctx.saved_tensors[3:]
+        g = g.contiguous().float()
+        grads = [torch.empty_like(f) for f in feats]             # the kernel assigns every element
+        d, nws, keep = _pod_desc(feats, level_len, pod_tab, ctx.scale)
+        _lib.check(_lib.load().vilco_pod_bwd(C.byref(d), g.data_ptr(), _ptr_table(grads), ws.data_ptr(), ctx.nws, _stream()))
+        return (None, None, None) + tuple(grads)
+
+
+def _pod_args(name, feats, level_len):
+    feats = list(feats)
+    if not 1 <= len(feats) <= 16:
+        raise ValueError("%s takes 1 to 16 levels, got %d" % (name, len(feats)))
+    for t in feats + [level_len]:
+        if not (torch.is_tensor(t) and t.is_cuda):
+            raise RuntimeError("vilco_amd ops run on the HIP device only (got a %s tensor); there is no CPU fallback"
+                               % (t.device if torch.is_tensor(t) else type(t).__name__))
+    if any(f.dim() != 3 for f in feats):
+        raise ValueError("%s: every level must be [B, T_l, C]" % name)
+    B, Cn = feats[0].shape[0], feats[0].shape[2]
+    if any(f.shape[0] != B or f.shape[2] != Cn or f.shape[1] < 1 or f.dtype != torch.float32 for f in feats) or B < 1 or Cn < 1:
+        raise ValueError("%s: every level must be fp32 [B, T_l, C] with the same B >= 1 and C >= 1 and T_l >= 1" % name)
+    if level_len.dtype != torch.int32 or tuple(level_len.shape) != (B, len(feats)):
+        raise ValueError("%s: level_len must be int32 [%d, %d], got %s %s"
+                         % (name, B, len(feats), level_len.dtype, tuple(level_len.shape)))
+    if any(f.device != feats[0].device for f in feats) or level_len.device != feats[0].device:
+        raise RuntimeError("%s: all tensors must live on one device" % name)
+    return [f.contiguous() for f in feats], level_len.contiguous()
+
+
+def pod_distill(feats, level_len, pod_tab, scale, return_count=False):
+    """PODNet's pooled feature distillation over the pyramid (include/vilco_hip.h: vilco_pod_desc) -> the scalar
+    scale / (L N_rec) * sum_b sum_l ||u_bl - r_bl||, an exact 0 when no row has a record.  feats: list of L <= 16 token-major
+    fp32 [B, T_l, C]; level_len: device int32 [B, L] valid lengths; pod_tab: device int64 [B] = the address of the row's record
+    (fp32 [sum_l (C + T_l)], ops.pod_record's layout) or 0 -- cl_methods.pod.PODBank.table_for builds it and keeps the records
+    alive.  return_count: also the device int64 scalar N_rec."""
+    feats, level_len = _pod_args("pod_distill", feats, level_len)
+    B = feats[0].shape[0]
+    if not (torch.is_tensor(pod_tab) and pod_tab.is_cuda):
+        raise RuntimeError("vilco_amd ops run on the HIP device only (got a %s tensor); there is no CPU fallback"
+                           % (pod_tab.device if torch.is_tensor(pod_tab) else type(pod_tab).__name__))
+    if pod_tab.dtype != torch.int64 or tuple(pod_tab.shape) != (B,):
+        raise ValueError("pod_distill: pod_tab must be int64 [%d], got %s %s" % (B, pod_tab.dtype, tuple(pod_tab.shape)))
+    if pod_tab.device != feats[0].device:
+        raise RuntimeError("pod_distill: all tensors must live on one device")
+    loss, count = _PodDistill.apply(level_len, pod_tab.contiguous(), float(scale), *feats)
+    return (loss, count) if return_count else loss
+
+
+def pod_record(feats, level_len):
+    """-> fp32 [B, L * C + sum T_l]: every row's pooled, normalised vectors u_bl = [p ; q] / max(||[p ; q]||, 1e-12), levels
+    end to end, entries at t >= level_len[b][l] zero (vilco_pod_record: two launches) -- what pod_distill compares against"""
+    feats, level_len = _pod_args("pod_record", feats, level_len)
+    with torch.no_grad():
+        d, nws, keep = _pod_desc(feats, level_len, None, 1.0)
+        ws = torch.empty(int(nws), dtype=torch.uint8, device=feats[0].device)
+        rec = torch.empty(feats[0].shape[0], pod_record_width([f.shape[1] for f in feats], feats[0].shape[2]),
+                          dtype=torch.float32, device=feats[0].device)
+        _lib.check(_lib.load().vilco_pod_record(C.byref(d), rec.data_ptr(), ws.data_ptr(), nws, _stream()))
+    return rec
+
+
 # ---------------------------------------------------------------------------------------- BiC bias correction
 _bic_tabs = {}
 

@@ -13,7 +13,7 @@ reference driver MQ/train_cl.py:206-389 (+ load_best_checkpoint :31-40), written
           and scheduler                                             (:373-389)
 
 A continual-learning method acts at six points of that loop -- begin_run, begin_task, end_training, save_state, after_reload,
-before_next_task: cl_methods/hooks.py names them, holds one class per method (EWC / MAS, SI, RWalk, A-GEM, DER, the CODA task
+before_next_task: cl_methods/hooks.py names them, holds one class per method (EWC / MAS, SI, RWalk, A-GEM, DER, POD, the CODA task
 switch) and the table of which method runs in which driver (hooks.SUPPORT).  The drivers call the points and know no method.
 
 What is ours rather than the reference's: the stream is any iterable with QILSetTask's contract
