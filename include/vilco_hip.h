@@ -802,6 +802,66 @@ int vilco_pod_bwd(const vilco_pod_desc* d, const float* g_out, float* const* d_f
 int vilco_pod_record(const vilco_pod_desc* d, float* records, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------ */
+/* Elastic Response Distillation (Feng, Wang, Yuan, CVPR 2022; the reference has no method that holds the regression head)  */
+/* (csrc/erd.hip; the definition is tests/erd_restatement.py).  Record time: z = the incoming model's logits [B][P][C],    */
+/* levels end to end (P = sum T_l), o^ = its finished offsets [B][P][2]; V = the positions below level_len[b][l].          */
+/*   c_i = max_{y < n_old} z_iy   mu = mean_V c   sigma = sqrt(mean_V (c - mu)^2)     (fp64, two passes, fixed order)       */
+/*   S_cls = {i in V: c_i > mu + alpha_cls sigma}   S_reg = {i in V: c_i > mu + alpha_reg sigma and o^_i0 + o^_i1 > 0}      */
+/* vilco_erd_select: two launches; conf [B][P] and flags [B][P] are scratch the fill reads again, counts [B][2] = |S_cls|,  */
+/* |S_reg| per clip, which the HOST reads to size the buffers.  vilco_erd_select_fill: one launch; out_tab = DEVICE int64   */
+/* [B][4] = the addresses of the clip's map_cls, map_reg (int32 [P]: position -> slot, ascending, -1 = not selected),      */
+/* val_cls (fp32 [|S_cls|][n_old]) and val_reg (fp32 [|S_reg|][2]); slots come from a prefix scan, never from an atomic.    */
+/* Every step: x = the concatenated head output [B][R][C], o = the offsets [B][R][2] in the same rows -- finished, or, with */
+/* scale != null (DEVICE float [L], the fused loss route), raw: o = relu(fl32(scale_l raw)).                               */
+/*   erd_tab = DEVICE int64 [B][5]: map_cls, map_reg, val_cls, val_reg, n_b (the record's class count and row stride), or   */
+/*             zeros: row b has no record.  A row with n_b outside [1, C] is skipped, not trusted.                          */
+/*   A = sum_b sum_{i in S_cls(b)} sum_{y < n_b} (x_iy - z_iy)^2   N_c = sum_b |S_cls(b)| n_b                               */
+/*   D = sum_b sum_{i in S_reg(b)} diou(o_i, o^_i)                 N_r = sum_b |S_reg(b)|     (ctr_diou_loss_1d, eps 1e-8) */
+/*   out[0..2] = lambda_cls A / N_c + lambda_reg D / N_r, its first part, its second part; a part whose count is 0 is 0.    */
+/*   Terms fp64 from the fp32 inputs, sums fp64 in a fixed order, every output rounded to fp32 once.                        */
+/* fwd: two launches; N_c, N_r (two int64 at the workspace's first 256-byte boundary) and the unweighted d scale are left   */
+/* in the workspace (vilco_erd_workspace(B * sum T_l) bytes): hand bwd the SAME workspace, untouched in between.            */
+/* bwd: one launch; g_out = device scalar; EVERY element of d_logits [B][R][C] and d_offsets [B][R][2] is assigned (zeros   */
+/* where nothing is compared); with scale, d_offsets is the gradient of raw and d_scale [L] is written too.  The gradient   */
+/* of diou takes autograd's choices: half to each side of a min / max tie, a clamp passes the gradient at >= eps.           */
+/* erd_tab and level_len are read when the kernels RUN, so a captured launch follows a table rewritten between replays; the */
+/* records must stay where they are while a graph may replay.  No atomics: the same bits on every call.  A null pointer,    */
+/* L outside 1..16, B < 1, a level outside R, P != sum T_l, n_old outside 1..C: VILCO_ERR_BADARG; a short workspace:        */
+/* VILCO_ERR_WORKSPACE -- both before anything is enqueued.                                                                */
+/* ------------------------------------------------------------------------------------------ */
+typedef struct vilco_erd_desc {
+  const float* logits;        /* [B][R][C] */
+  const float* offsets;       /* [B][R][2] */
+  const float* scale;         /* device [L], or null: offsets are finished */
+  const int32_t* level_row;   /* host [L]: first row of every level inside R */
+  const int32_t* level_T;     /* host [L]: rows of every level */
+  const int32_t* level_dev;   /* device [2][L]: level_row, level_T */
+  const int32_t* level_len;   /* device [B][L]: valid lengths */
+  const int64_t* erd_tab;     /* device [B][5] */
+  int32_t B, R, C, L;
+  double lambda_cls, lambda_reg;
+} vilco_erd_desc;
+typedef struct vilco_erd_select_desc {
+  const float* logits;        /* [B][P][C] */
+  const float* offsets;       /* [B][P][2] */
+  const int32_t* level_T;     /* host [L] */
+  const int32_t* level_len;   /* device [B][L] */
+  float* conf;                /* device [B][P] */
+  int32_t* flags;             /* device [B][P] */
+  int32_t* counts;            /* device [B][2] */
+  const int64_t* out_tab;     /* device [B][4] (fill only) */
+  int32_t B, P, C, n_old, L, reserved;
+  double alpha_cls, alpha_reg;
+} vilco_erd_select_desc;
+int32_t vilco_erd_pairs_per_round(void);                /* (batch row, pyramid row) pairs one round of the forward grid covers */
+size_t vilco_erd_workspace(int64_t n_pairs);            /* n_pairs = B * sum T_l */
+int vilco_erd_fwd(const vilco_erd_desc* d, float* out, void* workspace, size_t workspace_bytes, void* stream);
+int vilco_erd_bwd(const vilco_erd_desc* d, const float* g_out, float* d_logits, float* d_offsets, float* d_scale,
+                  const void* workspace, size_t workspace_bytes, void* stream);
+int vilco_erd_select(const vilco_erd_select_desc* d, void* stream);
+int vilco_erd_select_fill(const vilco_erd_select_desc* d, void* stream);
+
+/* ------------------------------------------------------------------------------------------ */
 /* BiC bias correction of the classification head's output (MQ/libs/modeling/meta_archs.py:26-35: BiasLayer,           */
 /* alpha * x + beta; :821-836: one layer per task over its slice of the class columns, the slices concatenated again)    */
 /* as one launch over the concatenated head output (csrc/bic.hip):                                                       */

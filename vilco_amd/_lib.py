@@ -162,6 +162,20 @@ class PodDesc(C.Structure):
                 ("reserved", i32), ("scale", C.c_double)]
 
 
+class ErdDesc(C.Structure):
+    _cname_ = "vilco_erd_desc"
+    _fields_ = [("logits", c_fp), ("offsets", c_fp), ("scale", c_fp), ("level_row", c_fp), ("level_T", c_fp), ("level_dev", c_fp),
+                ("level_len", c_fp), ("erd_tab", c_fp), ("B", i32), ("R", i32), ("C", i32), ("L", i32),
+                ("lambda_cls", C.c_double), ("lambda_reg", C.c_double)]
+
+
+class ErdSelectDesc(C.Structure):
+    _cname_ = "vilco_erd_select_desc"
+    _fields_ = [("logits", c_fp), ("offsets", c_fp), ("level_T", c_fp), ("level_len", c_fp), ("conf", c_fp), ("flags", c_fp),
+                ("counts", c_fp), ("out_tab", c_fp), ("B", i32), ("P", i32), ("C", i32), ("n_old", i32), ("L", i32),
+                ("reserved", i32), ("alpha_cls", C.c_double), ("alpha_reg", C.c_double)]
+
+
 class BicCorrectDesc(C.Structure):
     _cname_ = "vilco_bic_correct_desc"
     _fields_ = [("x", c_fp), ("y", c_fp), ("splits", c_fp), ("table", c_fp), ("rows", i64), ("C", i32), ("S", i32),
@@ -279,6 +293,12 @@ SIGNATURES = {
     "vilco_pod_fwd": (C.c_int, [C.POINTER(PodDesc), c_fp, c_fp, sz, c_fp]),
     "vilco_pod_bwd": (C.c_int, [C.POINTER(PodDesc), c_fp, C.POINTER(c_fp), c_fp, sz, c_fp]),
     "vilco_pod_record": (C.c_int, [C.POINTER(PodDesc), c_fp, c_fp, sz, c_fp]),
+    "vilco_erd_pairs_per_round": (i32, []),
+    "vilco_erd_workspace": (sz, [i64]),
+    "vilco_erd_fwd": (C.c_int, [C.POINTER(ErdDesc), c_fp, c_fp, sz, c_fp]),
+    "vilco_erd_bwd": (C.c_int, [C.POINTER(ErdDesc), c_fp, c_fp, c_fp, c_fp, c_fp, sz, c_fp]),
+    "vilco_erd_select": (C.c_int, [C.POINTER(ErdSelectDesc), c_fp]),
+    "vilco_erd_select_fill": (C.c_int, [C.POINTER(ErdSelectDesc), c_fp]),
     "vilco_cl_penalty": (C.c_int, [C.POINTER(ChunkTable), f32, i32, c_fp, c_fp, c_fp]),
     "vilco_cl_accumulate": (C.c_int, [C.POINTER(ChunkTable), i32, f32, f32, c_fp]),
     "vilco_agem_project": (C.c_int, [C.POINTER(ChunkTable), c_fp, c_fp, c_fp]),

@@ -7,7 +7,7 @@ import os
 
 import torch
 
-from . import agem as agem_mod, coda as coda_mod, der as der_mod, pod as pod_mod, regularizers
+from . import agem as agem_mod, coda as coda_mod, der as der_mod, erd as erd_mod, pod as pod_mod, regularizers
 
 DER_BANK_FILE = 'der_bank.pt'      # cl_cfg.name 'der': DERBank.state_dict(), written next to the memory pickle
 RWALK_STATE_FILE = 'rwalk_state.pt'      # cl_cfg.name 'rwalk': regularizers.rwalk_state_dict(), written next to the memory pickle
@@ -17,7 +17,7 @@ HOOKS = 'hooks'      # the driver calls the method's hooks
 PENALTY_ONLY = 'penalty only'      # no hook is called: train_one_epoch applies the penalty if model.reg_params is populated (by
 #                                    a checkpoint, say), and nothing consolidates -- the dictionary never changes
 # method -> ({driver: what it gives the method}, whether the method accepts a reducer, i.e. data parallelism).  A driver that is
-# not listed refuses the method by name, as does run_episodes with a reducer that is not accepted: agem / der / pod / coda
+# not listed refuses the method by name, as does run_episodes with a reducer that is not accepted: agem / der / pod / erd / coda
 # .check_supported read their rows and say why, make_hooks reads RWalk's.  'coda' is cl_cfg.prompt_type under cl_cfg.prompt_pool,
 # the others are cl_cfg.name; a name that is not here (None, 'icarl', 'bic', ...) has no hooks and runs everywhere.
 SUPPORT = {
@@ -33,6 +33,7 @@ SUPPORT = {
 # that list, `support(name)` reads both tables
 SUPPORT_MORE = {
     'pod': ({MQ: HOOKS}, False),      # (nor with type_sampling 'icarl' or start_epoch > 0: pod.check_supported)
+    'erd': ({MQ: HOOKS}, False),      # (likewise: erd.check_supported)
 }
 
 
@@ -225,6 +226,35 @@ class POD(Hook):
             entry['pod_recorded'] = pod_mod.record_clips(model, model.pod_bank, loader, j)
 
 
+class ERD(Hook):
+    """cl_cfg.name 'erd' (cl_methods/erd.py): at the START of every task with known classes -- where POD records, from the same
+    intact incoming model and with the same loader walk -- `model.erd_bank` is cleared and every clip the task's loader yields
+    gets the positions selected at which that model answers confidently (per clip, above mean + alpha * std of the clip's
+    responses) and their logits over the known classes and finished offsets recorded.  Every step of the task then holds the new
+    model's logits and boundaries to the records at those positions ('erd_loss' = 'erd_cls_loss' + 'erd_reg_loss' in the loss
+    dict; ops.erd_distill, part of a replayed step).  The cost is ONE inference pass over the task's clips per task; the task's
+    log entry gets 'erd_recorded' = the number of records and 'erd_bytes' = what they take.  The records of the previous task
+    are released only after the new ones are in place.  No state file: a resume at a task boundary re-records from the
+    reloaded model; a resume inside a task (start_epoch > 0) raises, because the incoming model is gone by then."""
+
+    def begin_run(self, model, train_stream, start_task=0, start_epoch=0, ckpt_folder=None):
+        erd_mod.check_supported('erd', self.reducer, type_sampling=self.cl_cfg.get('type_sampling'), start_epoch=start_epoch)
+        self.opts = erd_mod.options(self.cl_cfg)
+        for k, v in self.opts.items():
+            setattr(model, k, v)
+        if getattr(model, 'erd_bank', None) is None:
+            model.erd_bank = erd_mod.ERDBank()
+
+    def begin_task(self, j, model, optimizer, loader, entry, keep_history=True):
+        if model.n_known > 0:
+            bank = model.erd_bank
+            bank.clear()
+            try:
+                entry['erd_recorded'], entry['erd_bytes'] = erd_mod.record_clips(model, bank, loader, j, self.opts)
+            finally:
+                bank.release()      # the previous task's buffers: no table names them any more
+
+
 class Coda(Hook):
     """cl_cfg.prompt_type 'coda' under cl_cfg.prompt_pool (cl_methods/coda.py), alongside any named method: cl_cfg['coda_tasks']
     None is filled from the stream's task count; a model that holds a CodaPrompt must divide its pool among as many tasks as the
@@ -252,7 +282,7 @@ class Coda(Hook):
         self.draw(model, j + 1)
 
 
-NAMED = {'ewc': Importance, 'mas': Importance, 'si': SI, 'rwalk': RWalk, 'agem': AGEM, 'der': DER, 'pod': POD}
+NAMED = {'ewc': Importance, 'mas': Importance, 'si': SI, 'rwalk': RWalk, 'agem': AGEM, 'der': DER, 'pod': POD, 'erd': ERD}
 
 
 def each(hooks, point, *args):
@@ -262,13 +292,14 @@ def each(hooks, point, *args):
 
 def make_hooks(cfg, driver, reducer=None):
     """-> the hook objects of a run of `driver`: [the named method's] + [Coda()], either of which may be missing.  What SUPPORT
-    does not let run in `driver` is refused here -- agem, der, pod, coda, rwalk in this order; begin_run refuses the rest.  A driver
+    does not let run in `driver` is refused here -- agem, der, pod, erd, coda, rwalk in this order; begin_run refuses the rest.  A driver
     that consolidates validates the importance options whatever the method: a bad value fails here, not after the first task."""
     cl_cfg = cfg['cl_cfg']
     name = cl_cfg['name']
     agem_mod.check_supported(name, driver=driver)
     der_mod.check_supported(name, driver=driver)
     pod_mod.check_supported(name, driver=driver)
+    erd_mod.check_supported(name, driver=driver)
     coda = bool(cl_cfg.get('prompt_pool')) and coda_mod.check_supported(cl_cfg.get('prompt_type', 'l2p'), driver=driver)
     if name == 'rwalk' and driver not in SUPPORT['rwalk'][0]:
         raise ValueError("cl_cfg.name 'rwalk' is not supported by %s: only run_episodes and run_episodes_nlq keep its state and "

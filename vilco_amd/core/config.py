@@ -135,7 +135,11 @@ DEFAULTS = {'init_rand_seed': 765421321,
 #   paper's -- and the constant in the score's denominator, for which the paper gives no value: 1e-8 is ours.
 #   cl_cfg.pod_lambda: weight of the pooled feature distillation of cl_cfg.name 'pod' (cl_methods/pod.py), before PODNet's
 #   adaptive factor sqrt(n_classes / new classes); a hyper-parameter, not tuned here.
-EXTRA_DEFAULTS = {'cl_cfg': {'der_alpha': 0.1, 'pod_lambda': 1.0, 'prompt_type': 'l2p', 'coda_tasks': None, 'coda_ortho_mu': 0.0, 'coda_seed': 0,
+#   cl_cfg.erd_alpha_cls / erd_alpha_reg (cl_cfg.name 'erd', cl_methods/erd.py): how many standard deviations above a clip's mean
+#   response a position must lie to be distilled (classification / regression set) -- 2 and 2, the ERD paper's;
+#   cl_cfg.erd_lambda_cls / erd_lambda_reg: the weights of the two parts, 1 and 1: hyper-parameters, not tuned here.
+EXTRA_DEFAULTS = {'cl_cfg': {'der_alpha': 0.1, 'pod_lambda': 1.0, 'erd_alpha_cls': 2.0, 'erd_alpha_reg': 2.0, 'erd_lambda_cls': 1.0,
+                             'erd_lambda_reg': 1.0, 'prompt_type': 'l2p', 'coda_tasks': None, 'coda_ortho_mu': 0.0, 'coda_seed': 0,
                              'rwalk_alpha': 0.9, 'rwalk_delta_t': 10, 'rwalk_eps': 1e-8}}
 
 

@@ -22,6 +22,7 @@ extern "C" size_t vilco_abi_sizeof(const char* struct_name) {
   ABI_SIZE(vilco_act_bwd_desc) ABI_SIZE(vilco_optim_desc) ABI_SIZE(vilco_distill_desc) ABI_SIZE(vilco_bic_correct_desc)
   ABI_SIZE(vilco_prompt_desc) ABI_SIZE(vilco_si_desc) ABI_SIZE(vilco_chunk_table) ABI_SIZE(vilco_der_desc)
   ABI_SIZE(vilco_coda_desc) ABI_SIZE(vilco_rwalk_step_desc) ABI_SIZE(vilco_rwalk_desc) ABI_SIZE(vilco_pod_desc)
+  ABI_SIZE(vilco_erd_desc) ABI_SIZE(vilco_erd_select_desc)
 #undef ABI_SIZE
   return 0;
 }

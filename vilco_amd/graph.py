@@ -188,6 +188,10 @@ class GraphedStep:
             # likewise for csrc/pod.hip: the records of THIS batch's clips, written by the incoming model at the task's start
             from .cl_methods import pod
             inp.pod_tab = pod.step_table(self.model, video_list)
+        if getattr(self.model, "cl_name", None) == 'erd':
+            # and for csrc/erd.hip: the maps and selected rows of THIS batch's clips, written at the task's start
+            from .cl_methods import erd
+            inp.erd_tab = erd.step_table(self.model, video_list)
         return inp
 
     def _key(self, inp, task_id):

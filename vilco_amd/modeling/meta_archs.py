@@ -298,15 +298,17 @@ class StepInputs:
     the method ('icarl' / 'bic') the caller that replays the step attached dist_tgt for (graph.GraphedStep._prepare), or None;
     der_tab int64 [B, 2] = (address of the row's DER record or 0, its class count) of a cl_name 'der' step
     (cl_methods.der.step_table), or None: the step then builds it from the clip list; pod_tab int64 [B] = the address of the
-    row's POD record or 0 of a cl_name 'pod' step (cl_methods.pod.step_table), or None: likewise"""
+    row's POD record or 0 of a cl_name 'pod' step (cl_methods.pod.step_table), or None: likewise; erd_tab int64 [B, 5] = the
+    addresses of the row's ERD maps and selected rows and its class count, or zeros, of a cl_name 'erd' step
+    (cl_methods.erd.step_table), or None: likewise"""
     __slots__ = ("feats_cf", "lens", "T", "text_cf", "text_lens", "narr", "gt", "narr_cf", "narr_lens", "narr_mask",
-                 "dist_tgt", "dist_lens", "dist_kind", "der_tab", "pod_tab")
+                 "dist_tgt", "dist_lens", "dist_kind", "der_tab", "pod_tab", "erd_tab")
     HOST = ("T", "narr", "dist_lens", "dist_kind")          # not device buffers: a captured step takes them over as they are
 
     def tensors(self):
         """(name, tensor) of every device buffer a replayed step reads"""
         return [(k, getattr(self, k)) for k in ("feats_cf", "lens", "text_cf", "text_lens", "gt", "narr_cf", "narr_lens",
-                                                "narr_mask", "dist_tgt", "der_tab", "pod_tab")
+                                                "narr_mask", "dist_tgt", "der_tab", "pod_tab", "erd_tab")
                 if getattr(self, k, None) is not None]
 
     def signature(self):
@@ -415,6 +417,10 @@ class PtTransformer(nn.Module):
         self.pod_lambda = float(cl_cfg.get('pod_lambda', 1.0))      # cl_name 'pod' (cl_methods/pod.py)
         self.pod_bank = None                 # cl_methods.pod.PODBank: the incoming model's pooled pyramid of the task's clips
         self._pod_step = None                # a get_emb pass of a 'pod' model leaves (pyramid, level lengths) here (pod.record_clips)
+        from ..cl_methods import erd as _erd
+        for k, v in _erd.OPTIONS.items():    # cl_name 'erd' (cl_methods/erd.py): erd_alpha_cls / _reg, erd_lambda_cls / _reg
+            setattr(self, k, float(cl_cfg.get(k, v)))
+        self.erd_bank = None                 # cl_methods.erd.ERDBank: the incoming model's confident responses on the task's clips
 
         self.prompt_pool = cl_cfg['prompt_pool']
         self.use_prompt_mask = True
@@ -613,7 +619,7 @@ class PtTransformer(nn.Module):
         inp.feats_cf, inp.lens, inp.T = self._batch_cf(video_list, is_training)
         inp.text_cf = inp.text_lens = inp.narr = inp.narr_cf = inp.narr_lens = inp.narr_mask = None
         inp.dist_tgt = inp.dist_lens = inp.dist_kind = None        # filled by the caller that replays the step (graph.GraphedStep)
-        inp.der_tab = inp.pod_tab = None
+        inp.der_tab = inp.pod_tab = inp.erd_tab = None
         if self.use_cross_modal:
             inp.text_cf, inp.text_lens, narr = self._query_batch_cf(video_list, narr_pad=narr_pad)
             if isinstance(narr, dict):
@@ -691,6 +697,10 @@ class PtTransformer(nn.Module):
             # likewise: the records are named by the table in `inp.pod_tab`
             if getattr(inp, "pod_tab", None) is None or prev_out_cls_logits:
                 return False
+        elif self.n_known > 0 and self.cl_name == 'erd':
+            # likewise: the maps and the selected rows are named by the table in `inp.erd_tab`
+            if getattr(inp, "erd_tab", None) is None or prev_out_cls_logits:
+                return False
         elif prev_out_cls_logits:
             return False
         if isinstance(getattr(self, 'prompt', None), CodaPrompt):
@@ -714,6 +724,7 @@ class PtTransformer(nn.Module):
         # a 'der' step: the table the caller attached, or the clips to build it from (_der_loss)
         self._der_step = (getattr(inp, "der_tab", None), video_list)
         self._pod_tab_step = (getattr(inp, "pod_tab", None), video_list)      # a 'pod' step: likewise (_pod_loss)
+        self._erd_tab_step = (getattr(inp, "erd_tab", None), video_list)      # an 'erd' step: likewise (_erd_loss)
         if self.use_cross_modal:
             text_tm, text_lens = ops.transpose(inp.text_cf), inp.text_lens
 
@@ -986,7 +997,7 @@ class PtTransformer(nn.Module):
         level_row = cat.off if cat is not None else [sum(level_T[:i]) for i in range(len(level_T))]
         return self._cl_terms({'cls_loss': cls_loss, 'reg_loss': reg_loss, 'al_loss': al_loss}, final_loss,
                               out_cls_logits, prev_out_cls_logits, reduce_sim, cat_logits=(logits, level_row),
-                              level_len=level_len, fpn_feats=fpn_feats)
+                              level_len=level_len, fpn_feats=fpn_feats, cat_offsets=(offsets, scale))
 
     # ------------------------------------------------------------------ losses
     @property
@@ -1073,7 +1084,8 @@ class PtTransformer(nn.Module):
                               prev_out_cls_logits, reduce_sim,
                               cat_logits=(logits_all, [sum(level_T[:i]) for i in range(len(level_T))]),
                               level_len=torch.stack([m.sum(1) for m in fpn_masks], dim=1).to(torch.int32).contiguous()
-                              if self.cl_name in ('der', 'pod') else None, fpn_feats=fpn_feats)
+                              if self.cl_name in ('der', 'pod', 'erd') else None, fpn_feats=fpn_feats,
+                              cat_offsets=(offsets_all, None))
 
     @staticmethod
     def _icarl_levels(prev_out_cls_logits, len_f):
@@ -1173,8 +1185,34 @@ class PtTransformer(nn.Module):
         records = [bank.get(pod.clip_key(v))[0] if r else None for v, r in zip(vids, rows)]
         return pod.pod_term(fpn_feats, level_len, records, scale)[0]
 
+    def _erd_loss(self, out_cls_logits, cat_logits, cat_offsets, level_len):
+        """cl_name 'erd' (ours; cl_methods/erd.py): at the positions the incoming model answered confidently on the batch's clips,
+        the squared distance of the logits over the classes known then and the DIoU of the offsets against the records.  On the
+        device ONE ops.erd_distill call (csrc/erd.hip) over the concatenated head output -- the fused loss route hands it the raw
+        offsets and the per-level Scale --, the records named by a device table; a CPU model evaluates the same term in tensor
+        ops.  -> (erd_loss, its classification part, its regression part)"""
+        from ..cl_methods import erd
+        (tab, video_list), self._erd_tab_step = getattr(self, "_erd_tab_step", None) or (None, None), None
+        if cat_offsets is None:
+            raise ValueError("a cl_name 'erd' step needs the offsets of the step")
+        (logits, level_row), (offsets, scale) = cat_logits, cat_offsets
+        level_T = tuple(int(x.shape[1]) for x in out_cls_logits)
+        if logits.is_cuda:
+            if tab is None:
+                if video_list is None:
+                    raise ValueError("a cl_name 'erd' step needs StepInputs.erd_tab or the list of its clips")
+                tab = erd.step_table(self, video_list, level_T)
+            return ops.erd_distill(logits, offsets, scale, level_row, level_T, level_len, tab, self.erd_lambda_cls,
+                                   self.erd_lambda_reg)
+        if video_list is None:
+            raise ValueError("a cl_name 'erd' step on a CPU model needs the list of its clips")
+        vids, bank = erd.labelled(video_list), self.erd_bank
+        records = (bank.usable(vids, [erd.clip_len(v) for v in vids], level_T) if bank is not None else [None] * len(vids))
+        return erd.erd_term(logits, offsets, scale, level_row, level_T, level_len, records, self.erd_lambda_cls,
+                            self.erd_lambda_reg)[:3]
+
     def _cl_terms(self, out, final_loss, out_cls_logits, prev_out_cls_logits, reduce_sim, cat_logits=None, level_len=None,
-                  fpn_feats=None):
+                  fpn_feats=None, cat_offsets=None):
         """continual-learning terms on top of the detection loss (meta_archs.py:1478-1519).  On the device the iCaRL / BiC
         distillation term is one fused op (cat_logits = the concatenated logits and every level's first row in them); a
         CPU model walks the reference's loops.  level_len: int32 [B, L] valid lengths, read by the 'der' term only."""
@@ -1193,6 +1231,11 @@ class PtTransformer(nn.Module):
             pod_loss = self._pod_loss(fpn_feats, level_len)
             out['pod_loss'] = pod_loss
             out['final_loss'] = final_loss + pod_loss
+            return out
+        if self.n_known > 0 and self.cl_name == 'erd':      # cat_offsets: the offsets in the logits' rows and the Scale, or None
+            erd_loss, erd_cls, erd_reg = self._erd_loss(out_cls_logits, cat_logits, cat_offsets, level_len)
+            out['erd_loss'], out['erd_cls_loss'], out['erd_reg_loss'] = erd_loss, erd_cls.detach(), erd_reg.detach()
+            out['final_loss'] = final_loss + erd_loss
             return out
         if self.n_known > 0 and self.cl_name in ('bic', 'icarl') and out_cls_logits[0].is_cuda:
             dist_loss = self._device_distill(out_cls_logits, prev_out_cls_logits, cat_logits)

@@ -2254,6 +2254,140 @@ def pod_record(feats, level_len):
     return rec
 
 
+# ---------------------------------------------------------------------------------------- Elastic Response Distillation
+ERD_TAB_COLS = 5      # erd_tab columns: map_cls, map_reg, val_cls, val_reg (addresses), n_b
+
+
+def erd_pairs_per_round():
+    """(batch row, pyramid row) pairs the capped forward grid of csrc/erd.hip covers in one round; beyond it the waves walk
+    further pairs"""
+    return int(_lib.load().vilco_erd_pairs_per_round())
+
+
+class _ErdDistill(torch.autograd.Function):
+    """the response-distillation term over the concatenated head output: two launches forward, one backward (vilco_erd_fwd /
+    _bwd); the backward assigns every element of the logits' and the offsets' gradient (and d scale on the raw-offset route)"""
+
+    @staticmethod
+    def forward(ctx, logits, offsets, scale, tab, level_len, erd_tab, lambda_cls, lambda_reg):
+        _chk(logits, offsets)
+        lib = _lib.load()
+        d = _lib.ErdDesc()
+        d.logits, d.offsets, d.scale = logits.data_ptr(), offsets.data_ptr(), (scale.data_ptr() if scale is not None else None)
+        d.level_len, d.erd_tab = level_len.data_ptr(), erd_tab.data_ptr()
+        d.level_row, d.level_T, d.level_dev = C.addressof(tab[0]), C.addressof(tab[1]), tab[2].data_ptr()
+        d.B, d.R, d.C, d.L = logits.shape[0], logits.shape[1], logits.shape[2], len(tab[0])
+        d.lambda_cls, d.lambda_reg = float(lambda_cls), float(lambda_reg)
+        nws = lib.vilco_erd_workspace(logits.shape[0] * sum(tab[1]))
+        # the workspace is this call's own: backward reads N_c, N_r and the unweighted d scale from it
+        ws = torch.empty(int(nws), dtype=torch.uint8, device=logits.device)
+        out = torch.empty(3, dtype=torch.float32, device=logits.device)
+        _lib.check(lib.vilco_erd_fwd(C.byref(d), out.data_ptr(), ws.data_ptr(), nws, _stream()))
+        ctx.desc, ctx.tab, ctx.nws, ctx.has_scale = d, tab, nws, scale is not None
+        ctx.save_for_backward(logits, offsets, scale, level_len, erd_tab, ws)
+        off = (-ws.data_ptr()) % 256
+        counts = ws[off:off + 16].view(torch.int64)
+        parts = out[1:3]
+        ctx.mark_non_differentiable(parts, counts)
+        return out[0], parts, counts
+
+    @staticmethod
+    def backward(ctx, g, _g_parts, _g_counts):
+        logits, offsets, scale, level_len, erd_tab, ws = ctx.saved_tensors
+        g = g.contiguous().float()
+        dl, do = torch.empty_like(logits), torch.empty_like(offsets)          # the kernel assigns every element
+        ds = torch.empty_like(scale) if ctx.has_scale else None
+        _lib.check(_lib.load().vilco_erd_bwd(C.byref(ctx.desc), g.data_ptr(), dl.data_ptr(), do.data_ptr(),
+                                             ds.data_ptr() if ds is not None else None, ws.data_ptr(), ctx.nws, _stream()))
+        return dl, do, ds, None, None, None, None, None
+
+
+def erd_distill(logits, offsets, scale, level_row, level_T, level_len, erd_tab, lambda_cls, lambda_reg, return_counts=False):
+    """Elastic Response Distillation's term (include/vilco_hip.h: vilco_erd_desc) -> (erd_loss, erd_cls_loss, erd_reg_loss):
+    lambda_cls A / N_c + lambda_reg D / N_r and its two parts (detached), a part whose count is 0 an exact 0.
+    logits: [B, R, C] with level l in rows level_row[l] .. level_row[l] + level_T[l]; offsets: [B, R, 2] in the same rows --
+    finished, or, with `scale` (fp32 [L], the per-level Scale of the fused loss route), raw: the op takes relu(scale_l raw)
+    itself and returns the gradients of raw and scale; level_len: device int32 [B, L] valid lengths; erd_tab: device int64
+    [B, 5] = the addresses of the row's two maps and two value buffers and n_b, or zeros -- cl_methods.erd.ERDBank.table_for
+    builds it and keeps the records alive.  return_counts: also the device int64 [2] (N_c, N_r)."""
+    for t in (logits, offsets, level_len, erd_tab) + ((scale,) if scale is not None else ()):
+        if not (torch.is_tensor(t) and t.is_cuda):
+            raise RuntimeError("vilco_amd ops run on the HIP device only (got a %s tensor); there is no CPU fallback"
+                               % (t.device if torch.is_tensor(t) else type(t).__name__))
+    if logits.dim() != 3 or logits.dtype != torch.float32:
+        raise ValueError("erd_distill: logits must be fp32 [B, R, C]")
+    tab = _distill_levels(level_row, level_T, logits.device)
+    B, R, L = logits.shape[0], logits.shape[1], len(tab[0])
+    if L > 16:
+        raise ValueError("erd_distill takes 1 to 16 levels, got %d" % L)
+    if tuple(offsets.shape) != (B, R, 2) or offsets.dtype != torch.float32:
+        raise ValueError("erd_distill: offsets must be fp32 [%d, %d, 2], got %s %s" % (B, R, offsets.dtype, tuple(offsets.shape)))
+    if scale is not None and (tuple(scale.shape) != (L,) or scale.dtype != torch.float32):
+        raise ValueError("erd_distill: scale must be fp32 [%d], got %s %s" % (L, scale.dtype, tuple(scale.shape)))
+    if level_len.dtype != torch.int32 or tuple(level_len.shape) != (B, L):
+        raise ValueError("erd_distill: level_len must be int32 [%d, %d], got %s %s" % (B, L, level_len.dtype, tuple(level_len.shape)))
+    if erd_tab.dtype != torch.int64 or tuple(erd_tab.shape) != (B, ERD_TAB_COLS):
+        raise ValueError("erd_distill: erd_tab must be int64 [%d, %d], got %s %s"
+                         % (B, ERD_TAB_COLS, erd_tab.dtype, tuple(erd_tab.shape)))
+    if any(t.device != logits.device for t in (offsets, level_len, erd_tab)) or (scale is not None and scale.device != logits.device):
+        raise RuntimeError("erd_distill: all tensors must live on one device")
+    loss, parts, counts = _ErdDistill.apply(logits.contiguous(), offsets.contiguous(),
+                                            scale.contiguous() if scale is not None else None, tab, level_len.contiguous(),
+                                            erd_tab.contiguous(), float(lambda_cls), float(lambda_reg))
+    out = (loss, parts[0], parts[1])
+    return out + (counts,) if return_counts else out
+
+
+def erd_select(logits, offsets, level_T, level_len, n_old, alpha_cls, alpha_reg):
+    """The record-time selection of Elastic Response Distillation (vilco_erd_select, vilco_erd_select_fill: three launches and
+    one host read of the counts in between).  logits: fp32 [B, P, C], the incoming model's logits, levels end to end; offsets:
+    fp32 [B, P, 2], its finished offsets; level_len: device int32 [B, L].  -> per clip (map_cls int32 [P], map_reg int32 [P],
+    val_cls fp32 [max(K_c, 1), n_old], val_reg fp32 [max(K_r, 1), 2], K_c, K_r): position -> slot (-1: not selected) and the
+    selected rows in ascending position; a set that is empty keeps one unused row, so that every buffer has an address."""
+    for t in (logits, offsets, level_len):
+        if not (torch.is_tensor(t) and t.is_cuda):
+            raise RuntimeError("vilco_amd ops run on the HIP device only (got a %s tensor); there is no CPU fallback"
+                               % (t.device if torch.is_tensor(t) else type(t).__name__))
+    level_T = [int(t) for t in level_T]
+    L = len(level_T)
+    if logits.dim() != 3 or logits.dtype != torch.float32:
+        raise ValueError("erd_select: logits must be fp32 [B, P, C]")
+    B, P, Cn = logits.shape
+    if P != sum(level_T) or not 1 <= L <= 16 or min(level_T) < 1:
+        raise ValueError("erd_select: %d rows do not hold the levels %s" % (P, level_T))
+    if tuple(offsets.shape) != (B, P, 2) or offsets.dtype != torch.float32:
+        raise ValueError("erd_select: offsets must be fp32 [%d, %d, 2], got %s %s" % (B, P, offsets.dtype, tuple(offsets.shape)))
+    if level_len.dtype != torch.int32 or tuple(level_len.shape) != (B, L):
+        raise ValueError("erd_select: level_len must be int32 [%d, %d], got %s %s" % (B, L, level_len.dtype, tuple(level_len.shape)))
+    if not 1 <= int(n_old) <= Cn:
+        raise ValueError("erd_select: n_old = %d outside 1 .. %d" % (n_old, Cn))
+    dev = logits.device
+    with torch.no_grad():
+        logits, offsets, level_len = logits.contiguous(), offsets.contiguous(), level_len.contiguous()
+        lib = _lib.load()
+        T = (_lib.i32 * L)(*level_T)
+        conf = torch.empty(B, P, dtype=torch.float32, device=dev)
+        flags = torch.empty(B, P, dtype=torch.int32, device=dev)
+        counts = torch.empty(B, 2, dtype=torch.int32, device=dev)
+        d = _lib.ErdSelectDesc()
+        d.logits, d.offsets, d.level_T, d.level_len = logits.data_ptr(), offsets.data_ptr(), C.addressof(T), level_len.data_ptr()
+        d.conf, d.flags, d.counts, d.out_tab = conf.data_ptr(), flags.data_ptr(), counts.data_ptr(), None
+        d.B, d.P, d.C, d.n_old, d.L = B, P, Cn, int(n_old), L
+        d.alpha_cls, d.alpha_reg = float(alpha_cls), float(alpha_reg)
+        _lib.check(lib.vilco_erd_select(C.byref(d), _stream()))
+        K = counts.tolist()                                      # the one host read: the buffers' sizes
+        recs = []
+        for kc, kr in K:
+            recs.append((torch.empty(P, dtype=torch.int32, device=dev), torch.empty(P, dtype=torch.int32, device=dev),
+                         torch.zeros(max(kc, 1), int(n_old), dtype=torch.float32, device=dev),
+                         torch.zeros(max(kr, 1), 2, dtype=torch.float32, device=dev), int(kc), int(kr)))
+        out_tab = torch.tensor([[r[0].data_ptr(), r[1].data_ptr(), r[2].data_ptr(), r[3].data_ptr()] for r in recs],
+                               dtype=torch.int64).to(dev)
+        d.out_tab = out_tab.data_ptr()
+        _lib.check(lib.vilco_erd_select_fill(C.byref(d), _stream()))
+    return recs
+
+
 # ---------------------------------------------------------------------------------------- BiC bias correction
 _bic_tabs = {}
 
