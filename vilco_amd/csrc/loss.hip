@@ -115,9 +115,11 @@ __device__ __forceinline__ float diou_elem(float lp, float rp, float lg, float r
   const float rho = 0.5f * (rp - lp - rg + lg);
   const float z = rho / ec;
   if (dlp) {
-    const float di_l = lp <= lg ? 1.f : 0.f, di_r = rp <= rg ? 1.f : 0.f;          // d inter
+    // a prediction equal to its target: min and max each pass half the gradient to either argument, as autograd through
+    // torch.min / torch.max (and with it the tensor-expression path) does
+    const float di_l = lp < lg ? 1.f : (lp == lg ? 0.5f : 0.f), di_r = rp < rg ? 1.f : (rp == rg ? 0.5f : 0.f);   // d inter
     const float du_l = uni > eps ? 1.f - di_l : 0.f, du_r = uni > eps ? 1.f - di_r : 0.f;   // d clamp(union)
-    const float de_l = enc > eps ? (lp >= lg ? 1.f : 0.f) : 0.f, de_r = enc > eps ? (rp >= rg ? 1.f : 0.f) : 0.f;
+    const float de_l = enc > eps ? 1.f - di_l : 0.f, de_r = enc > eps ? 1.f - di_r : 0.f;   // d max(lp, lg) = 1 - d min(lp, lg)
     *dlp = -(di_l * uc - inter * du_l) / (uc * uc) + 2.f * z * ((-0.5f) * ec - rho * de_l) / (ec * ec);
     *drp = -(di_r * uc - inter * du_r) / (uc * uc) + 2.f * z * (0.5f * ec - rho * de_r) / (ec * ec);
   }

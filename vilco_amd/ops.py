@@ -1970,7 +1970,11 @@ class _MQLoss(torch.autograd.Function):
 def mq_loss(logits, offsets, level_scale, gauss, tables, level_len, gt, loss_norm, radius, smoothing, momentum, loss_weight,
             al_weight, use_al):
     """logits [B,R,C], offsets [B,R,2] (raw when level_scale [L] is given), gauss [6,C], tables = (points [R,4],
-    row_level [R] int32, row_pos [R] int32), level_len [B,L] int32, gt float [B, 3*Nmax+1] (include/vilco_hip.h)."""
+    row_level [R] int32, row_pos [R] int32), level_len [B,L] int32, gt float [B, 3*Nmax+1] (include/vilco_hip.h).
+    loss_weight must be positive: loss_weight <= 0 means cls / max(reg, 0.01) as the weight (meta_archs.py:1076-1079), which the
+    kernels do not compute -- the model keeps that configuration on the tensor expressions."""
+    if not float(loss_weight) > 0:
+        raise ValueError("mq_loss: loss_weight must be > 0 (got %r): the adaptive weight is not implemented by the fused op" % (loss_weight,))
     cfg = dict(radius=float(radius), smoothing=float(smoothing), momentum=float(momentum), loss_weight=float(loss_weight),
                al_weight=float(al_weight), use_al=bool(use_al))
     return _MQLoss.apply(logits.contiguous(), offsets.contiguous(), level_scale, gauss.contiguous(), tables, level_len, gt,
