@@ -694,6 +694,18 @@ int vilco_mq_loss_fwd(const vilco_loss_desc* d, float* out, float* saved, void* 
 int vilco_mq_loss_bwd(const vilco_loss_desc* d, const float* g_cls, const float* g_reg, const float* g_al,
                       const float* g_final, const float* saved, const void* workspace, float* d_logits,
                       float* d_offsets, float* d_level_scale, float* d_gauss, void* stream);
+/* ER-ACE (Caccia et al., ICLR 2022): the same loss with a class window per clip.  cls_lo = DEVICE int32 [B], read when the
+ * kernels run (a captured launch follows a table rewritten between replays); lo_b = cls_lo[b], a value outside [0, C) is
+ * taken as 0.  For the rows of clip b the focal sum, the al softmax (a masked row: uniform 1/(C - lo_b)), the al maximum and
+ * the al sum run over the columns [lo_b, C) only; targets, smoothing (C + 1), gaussian weights, the positive / negative
+ * decision, the regression sum, #pos and the normaliser are those of the plain entries.  bwd writes d_logits[b, r, c] = 0 for
+ * c < lo_b and assigns every element.  Workspace, almax_state, error returns (plus: cls_lo NULL -> VILCO_ERR_BADARG) and the
+ * fixed summation order are the plain entries'; with cls_lo all zero every output is bit-identical to theirs. */
+int vilco_mq_loss_ace_fwd(const vilco_loss_desc* d, const int32_t* cls_lo, float* out, float* saved, void* almax_state,
+                          void* workspace, size_t workspace_bytes, void* stream);
+int vilco_mq_loss_ace_bwd(const vilco_loss_desc* d, const int32_t* cls_lo, const float* g_cls, const float* g_reg,
+                          const float* g_al, const float* g_final, const float* saved, const void* workspace,
+                          float* d_logits, float* d_offsets, float* d_level_scale, float* d_gauss, void* stream);
 
 /* ------------------------------------------------------------------------------------------ */
 /* Distillation term of iCaRL / BiC (MQ/libs/modeling/meta_archs.py:1482-1519) and its gradient (csrc/distill.hip).  */

@@ -282,6 +282,9 @@ SIGNATURES = {
     "vilco_mq_loss_fwd": (C.c_int, [C.POINTER(LossDesc), c_fp, c_fp, c_fp, c_fp, sz, c_fp]),
     "vilco_mq_loss_bwd": (C.c_int, [C.POINTER(LossDesc), c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp,
                                     c_fp]),
+    "vilco_mq_loss_ace_fwd": (C.c_int, [C.POINTER(LossDesc), c_fp, c_fp, c_fp, c_fp, c_fp, sz, c_fp]),
+    "vilco_mq_loss_ace_bwd": (C.c_int, [C.POINTER(LossDesc), c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp,
+                                        c_fp, c_fp]),
     "vilco_cl_distill_workspace": (sz, [i64]),
     "vilco_cl_distill_fwd": (C.c_int, [C.POINTER(DistillDesc), c_fp, c_fp, sz, c_fp]),
     "vilco_cl_distill_bwd": (C.c_int, [C.POINTER(DistillDesc), c_fp, c_fp, c_fp]),

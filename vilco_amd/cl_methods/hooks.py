@@ -7,7 +7,7 @@ import os
 
 import torch
 
-from . import agem as agem_mod, coda as coda_mod, der as der_mod, erd as erd_mod, pod as pod_mod, regularizers
+from . import ace as ace_mod, agem as agem_mod, coda as coda_mod, der as der_mod, erd as erd_mod, pod as pod_mod, regularizers
 
 DER_BANK_FILE = 'der_bank.pt'      # cl_cfg.name 'der': DERBank.state_dict(), written next to the memory pickle
 RWALK_STATE_FILE = 'rwalk_state.pt'      # cl_cfg.name 'rwalk': regularizers.rwalk_state_dict(), written next to the memory pickle
@@ -34,6 +34,7 @@ SUPPORT = {
 SUPPORT_MORE = {
     'pod': ({MQ: HOOKS}, False),      # (nor with type_sampling 'icarl' or start_epoch > 0: pod.check_supported)
     'erd': ({MQ: HOOKS}, False),      # (likewise: erd.check_supported)
+    'er_ace': ({MQ: HOOKS}, False),      # (NLQ has one query class, BiC trains its own loss: ace.check_supported)
 }
 
 
@@ -255,6 +256,17 @@ class ERD(Hook):
                 bank.release()      # the previous task's buffers: no table names them any more
 
 
+class ERACE(Hook):
+    """cl_cfg.name 'er_ace' (cl_methods/ace.py): from the first task with known classes the detection loss itself is asymmetric
+    -- a clip of the current task is scored over the current task's classes only, a clip of the replay memory over all classes
+    (ops.mq_loss_ace, part of a replayed step; the window table is built per batch from the memory's keys).  A stream built with
+    train_enable=True replays the memory under full supervision; with train_enable=False the method is the window alone.  The
+    hook refuses what ace.check_supported refuses and keeps no state: a resume works at any task or epoch."""
+
+    def begin_run(self, model, train_stream, start_task=0, start_epoch=0, ckpt_folder=None):
+        ace_mod.check_supported('er_ace', self.reducer)
+
+
 class Coda(Hook):
     """cl_cfg.prompt_type 'coda' under cl_cfg.prompt_pool (cl_methods/coda.py), alongside any named method: cl_cfg['coda_tasks']
     None is filled from the stream's task count; a model that holds a CodaPrompt must divide its pool among as many tasks as the
@@ -282,7 +294,8 @@ class Coda(Hook):
         self.draw(model, j + 1)
 
 
-NAMED = {'ewc': Importance, 'mas': Importance, 'si': SI, 'rwalk': RWalk, 'agem': AGEM, 'der': DER, 'pod': POD, 'erd': ERD}
+NAMED = {'ewc': Importance, 'mas': Importance, 'si': SI, 'rwalk': RWalk, 'agem': AGEM, 'der': DER, 'pod': POD, 'erd': ERD,
+         'er_ace': ERACE}
 
 
 def each(hooks, point, *args):
@@ -292,7 +305,7 @@ def each(hooks, point, *args):
 
 def make_hooks(cfg, driver, reducer=None):
     """-> the hook objects of a run of `driver`: [the named method's] + [Coda()], either of which may be missing.  What SUPPORT
-    does not let run in `driver` is refused here -- agem, der, pod, erd, coda, rwalk in this order; begin_run refuses the rest.  A driver
+    does not let run in `driver` is refused here -- agem, der, pod, erd, er_ace, coda, rwalk in this order; begin_run refuses the rest.  A driver
     that consolidates validates the importance options whatever the method: a bad value fails here, not after the first task."""
     cl_cfg = cfg['cl_cfg']
     name = cl_cfg['name']
@@ -300,6 +313,7 @@ def make_hooks(cfg, driver, reducer=None):
     der_mod.check_supported(name, driver=driver)
     pod_mod.check_supported(name, driver=driver)
     erd_mod.check_supported(name, driver=driver)
+    ace_mod.check_supported(name, driver=driver)
     coda = bool(cl_cfg.get('prompt_pool')) and coda_mod.check_supported(cl_cfg.get('prompt_type', 'l2p'), driver=driver)
     if name == 'rwalk' and driver not in SUPPORT['rwalk'][0]:
         raise ValueError("cl_cfg.name 'rwalk' is not supported by %s: only run_episodes and run_episodes_nlq keep its state and "

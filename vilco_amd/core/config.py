@@ -138,6 +138,7 @@ DEFAULTS = {'init_rand_seed': 765421321,
 #   cl_cfg.erd_alpha_cls / erd_alpha_reg (cl_cfg.name 'erd', cl_methods/erd.py): how many standard deviations above a clip's mean
 #   response a position must lie to be distilled (classification / regression set) -- 2 and 2, the ERD paper's;
 #   cl_cfg.erd_lambda_cls / erd_lambda_reg: the weights of the two parts, 1 and 1: hyper-parameters, not tuned here.
+#   cl_cfg.name 'er_ace' (cl_methods/ace.py): the asymmetric detection loss; it has no option, so nothing is added below.
 EXTRA_DEFAULTS = {'cl_cfg': {'der_alpha': 0.1, 'pod_lambda': 1.0, 'erd_alpha_cls': 2.0, 'erd_alpha_reg': 2.0, 'erd_lambda_cls': 1.0,
                              'erd_lambda_reg': 1.0, 'prompt_type': 'l2p', 'coda_tasks': None, 'coda_ortho_mu': 0.0, 'coda_seed': 0,
                              'rwalk_alpha': 0.9, 'rwalk_delta_t': 10, 'rwalk_eps': 1e-8}}

@@ -12,6 +12,12 @@
 // Backward recomputes the assignment (cheap: N GT per clip) and writes d logits, d raw offsets, and accumulates the few
 // learnable-scalar gradients (mu/sigma x3, level scales) with atomics.
 // Rows can be the plain concatenation of the levels or the LevelCat layout with separator rows (stride <= 0).
+//
+// ER-ACE (vilco_mq_loss_ace_*): the same kernel bodies with WIN = true read a per-clip class window lo_b = cls_lo[b] (device
+// int32 [B], read when the kernel runs; outside [0, C) -> 0): the focal sum, the al softmax, the al maximum and the finish
+// kernel's al sum of clip b visit the columns [lo_b, C) only, d logits of the columns below are written as 0.  The label
+// assignment, the gaussian weights, the regression sum and the normaliser do not know about the window.  WIN = false is the
+// plain loss: lo is the constant 0 and every window expression folds away.
 #include "common.h"
 
 namespace {
@@ -35,6 +41,17 @@ struct Assign {
 
 // gt block of clip b: [Nmax][2] segments, [Nmax] labels (as floats), [1] count
 __device__ __forceinline__ const float* gt_of(const LossArgs& a, int b) { return a.gt + (long)b * (3 * a.Nmax + 1); }
+
+// first class column clip b's classification terms visit; WIN = false: the constant 0
+template <bool WIN>
+__device__ __forceinline__ int window_lo(const int* __restrict__ cls_lo, int b, int C) {
+  if constexpr (WIN) {
+    const int lo = cls_lo[b];
+    return (lo < 0 || lo >= C) ? 0 : lo;
+  } else {
+    return 0;
+  }
+}
 
 __device__ __forceinline__ void assign_row(const LossArgs& a, int b, int r, Assign& s) {
   const float4 pt = *reinterpret_cast<const float4*>(a.points + 4L * r);
@@ -135,11 +152,14 @@ __device__ __forceinline__ float block_sum(float v, float* red) {
 }
 
 // forward, one thread per (b, r).  partial[(b * gridDim.x + bx) * 3 + {0,1,2}] = cls sum, reg sum, #pos
+template <bool WIN>
 __global__ __launch_bounds__(LT) void loss_fwd_kernel(LossArgs a, float* __restrict__ partial,
-                                                      unsigned long long* __restrict__ almax, int use_al) {
+                                                      unsigned long long* __restrict__ almax, int use_al,
+                                                      const int* __restrict__ cls_lo) {
   __shared__ float red[4];
   __shared__ unsigned long long smax[MAXC];
   const int b = blockIdx.y, r = blockIdx.x * LT + threadIdx.x;
+  const int lo = window_lo<WIN>(cls_lo, b, a.C);
   if (use_al) for (int c = threadIdx.x; c < a.C; c += LT) smax[c] = 0ull;
   __syncthreads();
   float cls = 0.f, reg = 0.f, npos = 0.f;
@@ -163,21 +183,22 @@ __global__ __launch_bounds__(LT) void loss_fwd_kernel(LossArgs a, float* __restr
         npos = 1.f;
       }
       float f = 0.f;
-      for (int c = 0; c < a.C; ++c) {
+      for (int c = lo; c < a.C; ++c) {
         const float t = ((s.bits[c >> 5] >> (c & 31)) & 1u) ? 1.f : 0.f;
         f += focal_elem(x[c], t * (1.f - a.smoothing) + a.smoothing / (a.C + 1), nullptr);
       }
       cls = f * wc;
     }
     if (use_al && !s.gap) {
-      // score = softmax_c(logits masked_fill(~valid, -1e7)): a masked row is uniform 1/C (and carries no gradient)
+      // score = softmax_c(logits masked_fill(~valid, -1e7)) over the window: a masked row is uniform 1/(C - lo) (and carries no
+      // gradient)
       float m = -INFINITY, z = 0.f;
       if (s.valid) {
-        for (int c = 0; c < a.C; ++c) m = fmaxf(m, x[c]);
-        for (int c = 0; c < a.C; ++c) z += expf(x[c] - m);
+        for (int c = lo; c < a.C; ++c) m = fmaxf(m, x[c]);
+        for (int c = lo; c < a.C; ++c) z += expf(x[c] - m);
       }
-      for (int c = 0; c < a.C; ++c) {
-        const float p = s.valid ? expf(x[c] - m) / z : 1.f / a.C;
+      for (int c = lo; c < a.C; ++c) {
+        const float p = s.valid ? expf(x[c] - m) / z : 1.f / (a.C - lo);
         // first maximum wins on ties: larger packed value = larger score, then SMALLER row
         const unsigned long long pk = ((unsigned long long)__float_as_uint(p) << 32) | (unsigned)(0xFFFFFFFFu - (unsigned)r);
         atomicMax(&smax[c], pk);
@@ -191,18 +212,19 @@ __global__ __launch_bounds__(LT) void loss_fwd_kernel(LossArgs a, float* __restr
   }
   if (use_al) {
     __syncthreads();
-    for (int c = threadIdx.x; c < a.C; c += LT) atomicMax(&almax[(long)b * a.C + c], smax[c]);
+    for (int c = lo + threadIdx.x; c < a.C; c += LT) atomicMax(&almax[(long)b * a.C + c], smax[c]);
   }
 }
 
 // one block: out[0..3] = cls, reg, al, final; saved[0] = the normaliser this step divides by; al_row[b*C+c] = argmax row
 // (or -1), al_score likewise; the packed-maximum workspace is returned to zero for the next call.
+template <bool WIN>
 __global__ __launch_bounds__(LT) void loss_finish_kernel(LossArgs a, const float* __restrict__ partial, int nparts,
                                                          unsigned long long* __restrict__ almax, int use_al,
                                                          float* __restrict__ loss_norm, float momentum, float loss_weight,
                                                          float al_weight, float* __restrict__ out,
                                                          float* __restrict__ saved, int* __restrict__ al_row,
-                                                         float* __restrict__ al_score) {
+                                                         float* __restrict__ al_score, const int* __restrict__ cls_lo) {
   __shared__ double red[4][LT];
   double s0 = 0, s1 = 0, s2 = 0, al = 0;
   for (int i = threadIdx.x; i < nparts; i += LT) { s0 += partial[3 * i]; s1 += partial[3 * i + 1]; s2 += partial[3 * i + 2]; }
@@ -214,6 +236,7 @@ __global__ __launch_bounds__(LT) void loss_finish_kernel(LossArgs a, const float
       const float sc = __uint_as_float((unsigned)(pk >> 32));
       al_row[i] = pk ? (int)(0xFFFFFFFFu - (unsigned)(pk & 0xFFFFFFFFull)) : -1;
       al_score[i] = sc;
+      if (c < window_lo<WIN>(cls_lo, b, a.C)) continue;      // outside the clip's window: no maximum was taken, no al term
       const float* g = gt_of(a, b);
       const int n = (int)g[3 * a.Nmax];
       bool inv = false;
@@ -243,11 +266,13 @@ __global__ __launch_bounds__(LT) void loss_finish_kernel(LossArgs a, const float
 // backward, one thread per (b, r): wts = {g_cls, g_reg, g_al} effective weights of the three UNNORMALISED sums
 struct GradOut { const float* g[4]; };     // upstream gradients of {cls, reg, al, final}; null = 0
 
+template <bool WIN>
 __global__ __launch_bounds__(LT) void loss_bwd_kernel(LossArgs a, GradOut go, float loss_weight,
                                                       float al_weight, const float* __restrict__ saved,
                                                       const int* __restrict__ al_row, const float* __restrict__ al_score,
                                                       int use_al, float* __restrict__ dlogits, float* __restrict__ doffsets,
-                                                      float* __restrict__ contrib) {
+                                                      float* __restrict__ contrib, const int* __restrict__ cls_lo) {
+  static_assert(MAXC <= 256, "the contrib key 256 * level + class holds the class in its low 8 bits");
   // contrib[(b R + r) * 8 ..]: this row's share of the PARAMETER gradients -- {key, d level_scale, 6 x d gauss} with key =
   // 256 * level + class for a positive row, -1 otherwise -- summed in a fixed order by loss_bwd_finish_kernel (round 6: these
   // were float atomicAdds, the only sums of the step whose order changed from launch to launch)
@@ -272,6 +297,7 @@ __global__ __launch_bounds__(LT) void loss_bwd_kernel(LossArgs a, GradOut go, fl
     return;
   }
   const float* g = gt_of(a, b);
+  const int lo = window_lo<WIN>(cls_lo, b, a.C);
   float wc = 1.f, fsum = 0.f;
   int cg = 0;
   float rel = 0.f;
@@ -284,13 +310,13 @@ __global__ __launch_bounds__(LT) void loss_bwd_kernel(LossArgs a, GradOut go, fl
   float m = -INFINITY, z = 1.f, alsum = 0.f;       // alsum = sum_c coef_c * p_c over the classes this row wins
   bool any_al = false;
   if (use_al) {
-    for (int c = 0; c < a.C; ++c) any_al = any_al || (al_row[b * a.C + c] == r);
+    for (int c = lo; c < a.C; ++c) any_al = any_al || (al_row[b * a.C + c] == r);
     if (any_al) {
       z = 0.f;
-      for (int c = 0; c < a.C; ++c) m = fmaxf(m, x[c]);
-      for (int c = 0; c < a.C; ++c) z += expf(x[c] - m);
+      for (int c = lo; c < a.C; ++c) m = fmaxf(m, x[c]);
+      for (int c = lo; c < a.C; ++c) z += expf(x[c] - m);
       const int n = (int)g[3 * a.Nmax];
-      for (int c = 0; c < a.C; ++c)
+      for (int c = lo; c < a.C; ++c)
         if (al_row[b * a.C + c] == r) {
           bool inv = false;
           for (int j = 0; j < n; ++j) inv = inv || ((int)g[2 * a.Nmax + j] == c);
@@ -300,7 +326,8 @@ __global__ __launch_bounds__(LT) void loss_bwd_kernel(LossArgs a, GradOut go, fl
     }
   }
   const int n = (int)g[3 * a.Nmax];
-  for (int c = 0; c < a.C; ++c) {
+  for (int c = 0; c < lo; ++c) dx[c] = 0.f;        // below the window: exactly zero
+  for (int c = lo; c < a.C; ++c) {
     const float t = ((s.bits[c >> 5] >> (c & 31)) & 1u) ? 1.f : 0.f;
     float d;
     fsum += focal_elem(x[c], t * (1.f - a.smoothing) + a.smoothing / (a.C + 1), &d);
@@ -413,9 +440,12 @@ extern "C" size_t vilco_mq_loss_workspace(int32_t B, int32_t R, int32_t C) {
   return ((parts + 15) / 16) * 16 + 2 * (((size_t)B * C * 4 + 15) / 16) * 16 + (size_t)B * R * 8 * sizeof(float);      // + backward's per-row parameter-gradient shares
 }
 
-extern "C" int vilco_mq_loss_fwd(const vilco_loss_desc* d, float* out, float* saved, void* almax_state, void* workspace,
-                                 size_t workspace_bytes, void* stream) {
-  if (bad_desc(d) || !out || !saved || !almax_state || !workspace) return VILCO_ERR_BADARG;
+namespace {
+
+template <bool WIN>
+int loss_fwd(const vilco_loss_desc* d, const int32_t* cls_lo, float* out, float* saved, void* almax_state, void* workspace,
+             size_t workspace_bytes, void* stream) {
+  if (bad_desc(d) || !out || !saved || !almax_state || !workspace || (WIN && !cls_lo)) return VILCO_ERR_BADARG;
   if (d->C > MAXC) return VILCO_ERR_UNSUPPORTED;
   if (workspace_bytes < vilco_mq_loss_workspace(d->B, d->R, d->C)) return VILCO_ERR_WORKSPACE;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
@@ -427,16 +457,17 @@ extern "C" int vilco_mq_loss_fwd(const vilco_loss_desc* d, float* out, float* sa
   float* al_score = reinterpret_cast<float*>(reinterpret_cast<char*>(al_row) + (((size_t)d->B * d->C * 4 + 15) / 16) * 16);
   unsigned long long* almax = reinterpret_cast<unsigned long long*>(almax_state);
   const int use_al = d->use_al ? 1 : 0;
-  hipLaunchKernelGGL(loss_fwd_kernel, dim3(gx, d->B), dim3(LT), 0, s, a, partial, almax, use_al);
-  hipLaunchKernelGGL(loss_finish_kernel, dim3(1), dim3(LT), 0, s, a, partial, d->B * gx, almax, use_al, d->loss_norm,
-                     d->momentum, d->loss_weight, d->al_weight, out, saved, al_row, al_score);
+  hipLaunchKernelGGL(loss_fwd_kernel<WIN>, dim3(gx, d->B), dim3(LT), 0, s, a, partial, almax, use_al, cls_lo);
+  hipLaunchKernelGGL(loss_finish_kernel<WIN>, dim3(1), dim3(LT), 0, s, a, partial, d->B * gx, almax, use_al, d->loss_norm,
+                     d->momentum, d->loss_weight, d->al_weight, out, saved, al_row, al_score, cls_lo);
   return vilco_launch_status();
 }
 
-extern "C" int vilco_mq_loss_bwd(const vilco_loss_desc* d, const float* g_cls, const float* g_reg, const float* g_al,
-                                 const float* g_final, const float* saved, const void* workspace, float* d_logits,
-                                 float* d_offsets, float* d_level_scale, float* d_gauss, void* stream) {
-  if (bad_desc(d) || !saved || !workspace || !d_logits || !d_offsets || !d_gauss) return VILCO_ERR_BADARG;
+template <bool WIN>
+int loss_bwd(const vilco_loss_desc* d, const int32_t* cls_lo, const float* g_cls, const float* g_reg, const float* g_al,
+             const float* g_final, const float* saved, const void* workspace, float* d_logits, float* d_offsets,
+             float* d_level_scale, float* d_gauss, void* stream) {
+  if (bad_desc(d) || !saved || !workspace || !d_logits || !d_offsets || !d_gauss || (WIN && !cls_lo)) return VILCO_ERR_BADARG;
   GradOut grad_out{{g_cls, g_reg, g_al, g_final}};
   if (d->level_scale && !d_level_scale) return VILCO_ERR_BADARG;
   if (d->C > MAXC) return VILCO_ERR_UNSUPPORTED;
@@ -448,9 +479,36 @@ extern "C" int vilco_mq_loss_bwd(const vilco_loss_desc* d, const float* g_cls, c
   const float* al_score = reinterpret_cast<const float*>(reinterpret_cast<const char*>(al_row) + (((size_t)d->B * d->C * 4 + 15) / 16) * 16);
   // (the workspace is the forward's: its last region is written here -- the `const` of the signature predates it)
   float* contrib = const_cast<float*>(reinterpret_cast<const float*>(reinterpret_cast<const char*>(al_score) + (((size_t)d->B * d->C * 4 + 15) / 16) * 16));
-  hipLaunchKernelGGL(loss_bwd_kernel, dim3(gx, d->B), dim3(LT), 0, s, a, grad_out, d->loss_weight, d->al_weight, saved,
-                     al_row, al_score, d->use_al ? 1 : 0, d_logits, d_offsets, contrib);
+  hipLaunchKernelGGL(loss_bwd_kernel<WIN>, dim3(gx, d->B), dim3(LT), 0, s, a, grad_out, d->loss_weight, d->al_weight, saved,
+                     al_row, al_score, d->use_al ? 1 : 0, d_logits, d_offsets, contrib, cls_lo);
   hipLaunchKernelGGL(loss_bwd_finish_kernel, dim3(d->C + (d->level_scale ? d->L : 0)), dim3(LT), 0, s, contrib, (long)d->B * d->R, d->C,
                      d->L, d->level_scale ? d_level_scale : nullptr, d_gauss);
   return vilco_launch_status();
+}
+
+}  // namespace
+
+extern "C" int vilco_mq_loss_fwd(const vilco_loss_desc* d, float* out, float* saved, void* almax_state, void* workspace,
+                                 size_t workspace_bytes, void* stream) {
+  return loss_fwd<false>(d, nullptr, out, saved, almax_state, workspace, workspace_bytes, stream);
+}
+
+extern "C" int vilco_mq_loss_bwd(const vilco_loss_desc* d, const float* g_cls, const float* g_reg, const float* g_al,
+                                 const float* g_final, const float* saved, const void* workspace, float* d_logits,
+                                 float* d_offsets, float* d_level_scale, float* d_gauss, void* stream) {
+  return loss_bwd<false>(d, nullptr, g_cls, g_reg, g_al, g_final, saved, workspace, d_logits, d_offsets, d_level_scale, d_gauss,
+                         stream);
+}
+
+// ER-ACE: the same two launches each way over the per-clip class windows cls_lo (device int32 [B])
+extern "C" int vilco_mq_loss_ace_fwd(const vilco_loss_desc* d, const int32_t* cls_lo, float* out, float* saved,
+                                     void* almax_state, void* workspace, size_t workspace_bytes, void* stream) {
+  return loss_fwd<true>(d, cls_lo, out, saved, almax_state, workspace, workspace_bytes, stream);
+}
+
+extern "C" int vilco_mq_loss_ace_bwd(const vilco_loss_desc* d, const int32_t* cls_lo, const float* g_cls, const float* g_reg,
+                                     const float* g_al, const float* g_final, const float* saved, const void* workspace,
+                                     float* d_logits, float* d_offsets, float* d_level_scale, float* d_gauss, void* stream) {
+  return loss_bwd<true>(d, cls_lo, g_cls, g_reg, g_al, g_final, saved, workspace, d_logits, d_offsets, d_level_scale, d_gauss,
+                        stream);
 }

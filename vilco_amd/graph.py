@@ -192,6 +192,10 @@ class GraphedStep:
             # and for csrc/erd.hip: the maps and selected rows of THIS batch's clips, written at the task's start
             from .cl_methods import erd
             inp.erd_tab = erd.step_table(self.model, video_list)
+        if getattr(self.model, "cl_name", None) == 'er_ace':
+            # and for the windowed loss kernels (csrc/loss.hip, WIN): which of THIS batch's clips are memory clips (window 0)
+            from .cl_methods import ace
+            inp.ace_lo = ace.step_table(self.model, video_list)
         return inp
 
     def _key(self, inp, task_id):

@@ -300,15 +300,16 @@ class StepInputs:
     (cl_methods.der.step_table), or None: the step then builds it from the clip list; pod_tab int64 [B] = the address of the
     row's POD record or 0 of a cl_name 'pod' step (cl_methods.pod.step_table), or None: likewise; erd_tab int64 [B, 5] = the
     addresses of the row's ERD maps and selected rows and its class count, or zeros, of a cl_name 'erd' step
-    (cl_methods.erd.step_table), or None: likewise"""
+    (cl_methods.erd.step_table), or None: likewise; ace_lo int32 [B] = the first class column the row's classification terms
+    visit under cl_name 'er_ace' (cl_methods.ace.step_table), or None: likewise"""
     __slots__ = ("feats_cf", "lens", "T", "text_cf", "text_lens", "narr", "gt", "narr_cf", "narr_lens", "narr_mask",
-                 "dist_tgt", "dist_lens", "dist_kind", "der_tab", "pod_tab", "erd_tab")
+                 "dist_tgt", "dist_lens", "dist_kind", "der_tab", "pod_tab", "erd_tab", "ace_lo")
     HOST = ("T", "narr", "dist_lens", "dist_kind")          # not device buffers: a captured step takes them over as they are
 
     def tensors(self):
         """(name, tensor) of every device buffer a replayed step reads"""
         return [(k, getattr(self, k)) for k in ("feats_cf", "lens", "text_cf", "text_lens", "gt", "narr_cf", "narr_lens",
-                                                "narr_mask", "dist_tgt", "der_tab", "pod_tab", "erd_tab")
+                                                "narr_mask", "dist_tgt", "der_tab", "pod_tab", "erd_tab", "ace_lo")
                 if getattr(self, k, None) is not None]
 
     def signature(self):
@@ -619,7 +620,7 @@ class PtTransformer(nn.Module):
         inp.feats_cf, inp.lens, inp.T = self._batch_cf(video_list, is_training)
         inp.text_cf = inp.text_lens = inp.narr = inp.narr_cf = inp.narr_lens = inp.narr_mask = None
         inp.dist_tgt = inp.dist_lens = inp.dist_kind = None        # filled by the caller that replays the step (graph.GraphedStep)
-        inp.der_tab = inp.pod_tab = inp.erd_tab = None
+        inp.der_tab = inp.pod_tab = inp.erd_tab = inp.ace_lo = None
         if self.use_cross_modal:
             inp.text_cf, inp.text_lens, narr = self._query_batch_cf(video_list, narr_pad=narr_pad)
             if isinstance(narr, dict):
@@ -701,6 +702,10 @@ class PtTransformer(nn.Module):
             # likewise: the maps and the selected rows are named by the table in `inp.erd_tab`
             if getattr(inp, "erd_tab", None) is None or prev_out_cls_logits:
                 return False
+        elif self.n_known > 0 and self.cl_name == 'er_ace':
+            # the replayed loss kernels read the clips' class windows from `inp.ace_lo` (GraphedStep._prepare fills the slot)
+            if getattr(inp, "ace_lo", None) is None or prev_out_cls_logits:
+                return False
         elif prev_out_cls_logits:
             return False
         if isinstance(getattr(self, 'prompt', None), CodaPrompt):
@@ -725,6 +730,7 @@ class PtTransformer(nn.Module):
         self._der_step = (getattr(inp, "der_tab", None), video_list)
         self._pod_tab_step = (getattr(inp, "pod_tab", None), video_list)      # a 'pod' step: likewise (_pod_loss)
         self._erd_tab_step = (getattr(inp, "erd_tab", None), video_list)      # an 'erd' step: likewise (_erd_loss)
+        self._ace_step = (getattr(inp, "ace_lo", None), video_list)      # an 'er_ace' step: likewise (_ace_window)
         if self.use_cross_modal:
             text_tm, text_lens = ops.transpose(inp.text_cf), inp.text_lens
 
@@ -990,14 +996,34 @@ class PtTransformer(nn.Module):
             norm = torch.full((1,), float(norm), dtype=torch.float32, device=dev)
             self._loss_norm = norm
         radius = self.train_center_sample_radius if self.train_center_sample == 'radius' else 0.0
-        cls_loss, reg_loss, al_loss, final_loss = ops.mq_loss(
-            logits, offsets, scale, gauss, tables, level_len, gt, norm, radius, self.train_label_smoothing,
-            self.loss_normalizer_momentum, self.train_loss_weight, self.al_loss_weight, logits.shape[-1] != 1)
+        ace_lo = self._ace_window()
+        if ace_lo is not None:       # cl_name 'er_ace' with known classes: the same kernels over the clips' class windows
+            cls_loss, reg_loss, al_loss, final_loss = ops.mq_loss_ace(
+                logits, offsets, scale, gauss, tables, level_len, gt, norm, radius, self.train_label_smoothing,
+                self.loss_normalizer_momentum, self.train_loss_weight, self.al_loss_weight, logits.shape[-1] != 1, ace_lo)
+        else:
+            cls_loss, reg_loss, al_loss, final_loss = ops.mq_loss(
+                logits, offsets, scale, gauss, tables, level_len, gt, norm, radius, self.train_label_smoothing,
+                self.loss_normalizer_momentum, self.train_loss_weight, self.al_loss_weight, logits.shape[-1] != 1)
         level_T = [int(p.shape[0]) for p in points]
         level_row = cat.off if cat is not None else [sum(level_T[:i]) for i in range(len(level_T))]
         return self._cl_terms({'cls_loss': cls_loss, 'reg_loss': reg_loss, 'al_loss': al_loss}, final_loss,
                               out_cls_logits, prev_out_cls_logits, reduce_sim, cat_logits=(logits, level_row),
                               level_len=level_len, fpn_feats=fpn_feats, cat_offsets=(offsets, scale))
+
+    def _ace_window(self):
+        """cl_name 'er_ace' (ours; cl_methods/ace.py) with known classes: int32 [B], the first class column each clip's
+        classification terms visit -- the table the caller attached (StepInputs.ace_lo) or one built from the step's clips;
+        None for every other step, which takes the plain loss."""
+        (tab, video_list), self._ace_step = getattr(self, "_ace_step", None) or (None, None), None
+        if not (self.n_known > 0 and self.cl_name == 'er_ace'):
+            return None
+        if tab is None:
+            if video_list is None:
+                raise ValueError("a cl_name 'er_ace' step needs StepInputs.ace_lo or the list of its clips")
+            from ..cl_methods import ace
+            tab = ace.step_table(self, video_list)
+        return tab
 
     # ------------------------------------------------------------------ losses
     @property
@@ -1030,6 +1056,12 @@ class PtTransformer(nn.Module):
         gt_off_all = torch.stack(gt_offsets)
         gt_target = gt_cls * (1 - self.train_label_smoothing) + self.train_label_smoothing / (self.num_classes + 1)
         w_cls = torch.where(pos_mask, w_cls, torch.ones_like(w_cls))           # negatives weigh 1
+        # cl_name 'er_ace' with known classes (ours; cl_methods/ace.py): bool [B, 1, C], the class columns each clip's
+        # classification terms visit -- what ops.mq_loss_ace does in the kernels, in tensor ops
+        ace_lo, ace_cols = self._ace_window(), None
+        if ace_lo is not None:
+            from ..cl_methods import ace
+            ace_cols = ace.column_mask(ace_lo.to(logits_all.device), logits_all.shape[-1]).unsqueeze(1)
 
         if self.sync_free_loss:
             # Same sums as the reference, evaluated densely over all points with 0/1 weights instead of boolean
@@ -1041,6 +1073,8 @@ class PtTransformer(nn.Module):
             self._loss_norm = norm.detach()
             vf, pf = valid_mask.to(logits_all.dtype), pos_mask.to(logits_all.dtype)
             cls_loss = sigmoid_focal_loss(logits_all, gt_target, reduction='None')
+            if ace_cols is not None:
+                cls_loss = cls_loss * ace_cols.to(cls_loss.dtype)
             cls_loss = (cls_loss.sum(-1) * w_cls * vf).sum() / norm
             one = torch.ones_like(gt_off_all)
             reg = ctr_diou_loss_1d(torch.where(pos_mask[..., None], offsets_all, one).reshape(-1, 2),
@@ -1055,6 +1089,8 @@ class PtTransformer(nn.Module):
                 1 - self.loss_normalizer_momentum) * max(num_pos, 1)
             norm = self.loss_normalizer
             cls_loss = sigmoid_focal_loss(logits_all[valid_mask], gt_target[valid_mask], reduction='None')
+            if ace_cols is not None:
+                cls_loss = cls_loss * ace_cols.expand_as(logits_all)[valid_mask].to(cls_loss.dtype)
             cls_loss = (cls_loss.sum(-1) * w_cls[valid_mask]).sum() / norm
             if num_pos == 0:
                 reg_loss = 0 * pred_offsets.sum()
@@ -1065,11 +1101,20 @@ class PtTransformer(nn.Module):
 
         if label_list is not None and (out_cls_logits[0].shape[-1] != 1):
             score = logits_all.masked_fill(valid_mask.unsqueeze(-1) == False, -1e7)   # noqa: E712
+            if ace_cols is not None:       # the softmax of a clip's rows is over its window: a masked row scores 1 / (C - lo)
+                score = score.masked_fill(~ace_cols, float('-inf'))
             score = torch.max(score.softmax(-1), dim=1)[0]
             involved = torch.zeros_like(score)
             for i in range(involved.shape[0]):
                 involved[i, label_list[i]] = 1
-            al_loss = (-involved * score.log() - (1 - involved) * (1 - score).log()).sum() / norm
+            if ace_cols is not None:
+                # the masked sum, one logarithm per (clip, class) as in the kernels: of the score for an involved class, of its
+                # complement otherwise (a window of one class scores exactly 1: 0 * log(0) must not enter); the columns below
+                # the window (score 0) take 1 and add -log(1) = 0
+                q = torch.where(involved > 0, score, 1 - score)
+                al_loss = -torch.where(ace_cols.squeeze(1), q, torch.ones_like(q)).log().sum() / norm
+            else:
+                al_loss = (-involved * score.log() - (1 - involved) * (1 - score).log()).sum() / norm
         else:
             al_loss = torch.zeros((1,), device=cls_loss.device)
 

@@ -1981,6 +1981,74 @@ def mq_loss(logits, offsets, level_scale, gauss, tables, level_len, gt, loss_nor
                          loss_norm, cfg)
 
 
+class _MQLossAce(torch.autograd.Function):
+    """_MQLoss with ER-ACE's class window per clip (vilco_mq_loss_ace_fwd / _bwd): `cls_lo` is read by the kernels when they run,
+    forward and backward alike, so a captured step follows the table its replay wrote"""
+
+    @staticmethod
+    def forward(ctx, logits, offsets, level_scale, gauss, tables, level_len, gt, loss_norm, cfg, cls_lo):
+        _chk(logits, offsets, level_scale, gauss)
+        lib = _lib.load()
+        B, R, Cn = logits.shape
+        points, row_level, row_pos = tables
+        d = _lib.LossDesc()
+        d.logits, d.offsets, d.level_scale = logits.data_ptr(), offsets.data_ptr(), _p(level_scale)
+        d.points, d.row_level, d.row_pos = points.data_ptr(), row_level.data_ptr(), row_pos.data_ptr()
+        d.level_len, d.gt, d.gauss, d.loss_norm = level_len.data_ptr(), gt.data_ptr(), gauss.data_ptr(), loss_norm.data_ptr()
+        d.B, d.R, d.C, d.L, d.Nmax = B, R, Cn, level_len.shape[1], (gt.shape[1] - 1) // 3
+        d.center_radius, d.label_smoothing, d.momentum = cfg['radius'], cfg['smoothing'], cfg['momentum']
+        d.loss_weight, d.al_weight, d.use_al = cfg['loss_weight'], cfg['al_weight'], int(cfg['use_al'])
+        key = (logits.device.index, B * Cn)         # the plain op's state: both leave it zero
+        st = _almax_state.get(key)
+        if st is None:
+            st = _almax_state[key] = torch.zeros(B * Cn, dtype=torch.int64, device=logits.device)
+        nws = lib.vilco_mq_loss_workspace(B, R, Cn)
+        ws = _ws(nws, logits.device)
+        out = torch.empty(4, dtype=torch.float32, device=logits.device)
+        saved = torch.empty(1, dtype=torch.float32, device=logits.device)
+        _lib.check(lib.vilco_mq_loss_ace_fwd(C.byref(d), cls_lo.data_ptr(), out.data_ptr(), saved.data_ptr(), st.data_ptr(),
+                                             ws.data_ptr(), nws, _stream()))
+        ctx.desc, ctx.keep = d, (points, row_level, row_pos, level_len, gt, loss_norm)
+        ctx.save_for_backward(logits, offsets, level_scale, gauss, saved, ws, cls_lo)
+        return out[0], out[1], out[2], out[3]
+
+    @staticmethod
+    def backward(ctx, g_cls, g_reg, g_al, g_final):
+        logits, offsets, level_scale, gauss, saved, ws, cls_lo = ctx.saved_tensors
+        lib = _lib.load()
+        d = ctx.desc
+        dl, do = torch.empty_like(logits), torch.empty_like(offsets)
+        dsc = torch.empty_like(level_scale) if level_scale is not None else None
+        dg = torch.empty_like(gauss)
+        gs = [None if g is None else g.contiguous().float() for g in (g_cls, g_reg, g_al, g_final)]
+        _lib.check(lib.vilco_mq_loss_ace_bwd(C.byref(d), cls_lo.data_ptr(), _p(gs[0]), _p(gs[1]), _p(gs[2]), _p(gs[3]),
+                                             saved.data_ptr(), ws.data_ptr(), dl.data_ptr(), do.data_ptr(), _p(dsc),
+                                             dg.data_ptr(), _stream()))
+        return dl, do, dsc, dg, None, None, None, None, None, None
+
+
+def mq_loss_ace(logits, offsets, level_scale, gauss, tables, level_len, gt, loss_norm, radius, smoothing, momentum, loss_weight,
+                al_weight, use_al, cls_lo):
+    """ops.mq_loss under ER-ACE's asymmetric window (cl_methods/ace.py; include/vilco_hip.h: vilco_mq_loss_ace_fwd): cls_lo int32
+    [B] on the logits' device, contiguous -- clip b's classification and al terms visit the classes [cls_lo[b], C) only (a value
+    outside [0, C): all of them).  The kernels read the table when they run: rewrite it in place before a replay."""
+    if not float(loss_weight) > 0:
+        raise ValueError("mq_loss_ace: loss_weight must be > 0 (got %r): the adaptive weight is not implemented by the fused op" % (loss_weight,))
+    if not torch.is_tensor(cls_lo) or cls_lo.dtype != torch.int32 or cls_lo.dim() != 1 or logits.dim() != 3 or \
+            cls_lo.shape[0] != logits.shape[0]:
+        raise ValueError("mq_loss_ace: cls_lo must be an int32 tensor [%s], got %s" % (
+            logits.shape[0] if logits.dim() == 3 else 'B',
+            "%s %s" % (cls_lo.dtype, tuple(cls_lo.shape)) if torch.is_tensor(cls_lo) else type(cls_lo).__name__))
+    if cls_lo.device != logits.device:
+        raise RuntimeError("mq_loss_ace: cls_lo lives on %s, the logits on %s" % (cls_lo.device, logits.device))
+    if not cls_lo.is_contiguous():
+        raise ValueError("mq_loss_ace: cls_lo must be contiguous (the kernels read the caller's table, not a copy)")
+    cfg = dict(radius=float(radius), smoothing=float(smoothing), momentum=float(momentum), loss_weight=float(loss_weight),
+               al_weight=float(al_weight), use_al=bool(use_al))
+    return _MQLossAce.apply(logits.contiguous(), offsets.contiguous(), level_scale, gauss.contiguous(), tables, level_len, gt,
+                            loss_norm, cfg, cls_lo)
+
+
 # ---------------------------------------------------------------------------------------- iCaRL / BiC distillation
 DISTILL_ICARL, DISTILL_BIC = 0, 1
 _distill_tabs = {}
